@@ -8,7 +8,10 @@ One "step" = one cold QP solve (implicit Hankel -> Gram -> reduced KKT -> Choles
 batch.  Consecutive steps alternate between two resident data sets of the batch (a pointer swap through ddmpc_set_data),
 so no step can reuse anything a previous step derived from its data.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step computed (optimal_u, cost, status, iters; the gathered arrays on rank 0
+at N > 1) as DIR/<name>.npy in float64, for comparing two builds output for output: the inputs are seeded by instance id.
 
 With --gpus N > 1 (or --force-dist) and no WORLD_SIZE in the environment the script starts its own ranks
 (python -m torch.distributed.run, one process per GPU, RCCL) BEFORE anything touches the GPU
@@ -341,6 +344,23 @@ def other_configs_device(jobs, dev, steps=10):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write each per-instance array (leading axis = instance) as out_dir/<name>.npy in float64.  When the whole set would
+    exceed `limit` bytes, every array keeps the same fixed, seeded, sorted sample of instances."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(8 * int(np.prod(v.shape[1:])) for v in arrays.values())
+    keep = None
+    if rows * row_bytes > limit:
+        keep = np.sort(np.random.default_rng(seed).choice(rows, size=limit // row_bytes, replace=False))
+    for name, v in arrays.items():
+        v = np.asarray(v, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), v if keep is None else v[keep])
+
+
 def default_batch_per_gpu(gpus):
     """--gpus 1: BASELINE configs[1] (4096 seeds on one GPU).  --gpus N > 1: BASELINE configs[2]'s shard, 32,768 seeds
     per GPU (262,144 over 8), the batch at which a GPU is 9 % faster per instance than at 4096 (profiles/)."""
@@ -382,7 +402,12 @@ def main():
                          "multi-rank code path on a one-GPU box; numbers are meaningless)")
     ap.add_argument("--dump-gathered", default=None,
                     help="rank 0 saves the gathered optimal_u/cost/status to this .npz (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the outputs of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all: "
+                         "larger batches keep a fixed, seeded sample of instances)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if a.batch_per_gpu is None:
         a.batch_per_gpu = default_batch_per_gpu(a.gpus)
@@ -506,6 +531,12 @@ def main():
             np.savez(a.dump_gathered, u=g_u.cpu().numpy(), cost=g_c.cpu().numpy(), status=g_s.cpu().numpy())
     elif a.dump_gathered:
         np.savez(a.dump_gathered, u=u_opt.cpu().numpy(), cost=cost.cpu().numpy(), status=st)
+    if a.dump_outputs and rank == 0:           # before the warm-step section below reuses the output buffers
+        if use_dist:
+            outs = dict(optimal_u=g_u, cost=g_c, status=g_s)
+        else:
+            outs = dict(optimal_u=u_opt, cost=cost, status=status, iters=iters)
+        dump_outputs(a.dump_outputs, {k: v.cpu().numpy() for k, v in outs.items()})
 
     # ---- secondary metric (SURVEY 8d "warm" step), outside the timed region: rank 0, one GPU's share.
     # After ddmpc_prepare a control step only evaluates the per-instance affine law (slack NONE).

@@ -70,3 +70,24 @@ def test_bench_batch_defaults_name_the_baseline_configs():
     assert [mod.default_batch_per_gpu(g) * g for g in (2, 4, 8)] == [65536, 131072, 262144]
     from direct_data_driven_mpc_amd.distributed import shard_bounds
     assert shard_bounds(262144, 5, 8) == (5 * 32768, 6 * 32768)
+
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_under_the_size_limit(tmp_path):
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    u = np.arange(1000 * 6, dtype=np.float64).reshape(1000, 6)
+    st = np.arange(1000, dtype=np.int32)
+    mod.dump_outputs(str(tmp_path / "all"), dict(optimal_u=u, status=st))
+    assert np.array_equal(np.load(tmp_path / "all" / "optimal_u.npy"), u)
+    s = np.load(tmp_path / "all" / "status.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, st)
+    limit = 100 * 7 * 8                                     # room for 100 of the 1000 instances
+    for name in ("a", "b"):
+        mod.dump_outputs(str(tmp_path / name), dict(optimal_u=u, status=st), limit=limit)
+    ua, sa = np.load(tmp_path / "a" / "optimal_u.npy"), np.load(tmp_path / "a" / "status.npy")
+    assert ua.shape == (100, 6) and ua.nbytes + sa.nbytes <= limit
+    assert np.array_equal(ua, u[sa.astype(int)]) and np.all(np.diff(sa) > 0)
+    assert np.array_equal(ua, np.load(tmp_path / "b" / "optimal_u.npy"))

@@ -208,6 +208,29 @@ def test_bench_rccl_branch_at_world_size_one(gpu, tmp_path):
     assert np.array_equal(a["u"], b["u"]) and np.array_equal(a["cost"], b["cost"]) and np.array_equal(a["status"], b["status"])
 
 
+def test_bench_dumps_the_outputs_of_its_last_timed_step(gpu, tmp_path):
+    # --dump-outputs DIR: the arrays the timed solve hands back after its last step, as float64 .npy; the same arguments with a
+    # different number of steps give the same inputs to the last step, hence the same outputs bit for bit
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    common = ["--gpus", "1", "--batch-per-gpu", "160", "--warmup", "1", "--no-cpu-baseline", "--no-warm"]
+    dumps = []
+    for steps in (3, 4):
+        d, g = tmp_path / ("d%d" % steps), tmp_path / ("g%d.npz" % steps)
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--dump-outputs", str(d),
+                              "--dump-gathered", str(g)] + common, capture_output=True, text=True, timeout=900, env=env)
+        assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
+        rec = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0
+        z = {k: np.load(d / (k + ".npy")) for k in ("optimal_u", "cost", "status", "iters")}
+        assert all(v.dtype == np.float64 for v in z.values())
+        assert z["optimal_u"].shape == (160, 60) and z["cost"].shape == z["status"].shape == z["iters"].shape == (160,)
+        gz = np.load(g)
+        assert np.array_equal(z["optimal_u"], gz["u"]) and np.array_equal(z["cost"], gz["cost"])
+        assert np.array_equal(z["status"], gz["status"]) and not np.count_nonzero(z["status"])
+        dumps.append(z)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
 # ------------------------------------------------------------------ nominal rescue behind every entry point
 def _exact_nominal(B=6):
     from direct_data_driven_mpc_amd.harness import FOUR_TANK, generate_batch
