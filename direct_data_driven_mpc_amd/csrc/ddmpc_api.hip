@@ -201,6 +201,10 @@ struct ddmpc_handle {
   int nF = 0;                              // fixed components (hard constraints), nominal scheme
   int large_pipeline = DDMPC_PIPELINE_PHASES;   // DDMPC_OPT_LARGE_PIPELINE
   int convex_update = 1;                        // DDMPC_OPT_CONVEX_UPDATE: active-set iterations keep the first factor (rank-k update)
+  int convex_warm = 0;                     // DDMPC_OPT_CONVEX_WARM_LAW: warm steps under the slack box run the active-set iteration on the law
+  DevBuf d_mcol, d_cwl_tab, d_cwl_sg, d_cwl_ref;   // ... M = K0^-1 E_box [batch][nbox][r]; [box_rho | box_of]; k x k scratch; refined-law flags (+ count)
+  int cwl_nbox = 0;                        // ... boxed components
+  int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch)
   bool rescue_ran = false;
   int epoch = 0;                           // cold launches so far (KParams::epoch)
   int prep_epoch = 0;                      // stamp of the flags recorded by ddmpc_prepare's factor-export launch (AUTO)
@@ -1092,6 +1096,8 @@ static int launch_cold(ddmpc_handle* h, const double* up, const double* yp, doub
   return DDMPC_OK;
 }
 
+static bool convex_warm_on(const ddmpc_handle* h) { return h->convex_warm && h->kp.convex && !h->large; }
+
 static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost,
                        int32_t* status, int32_t* iters) {
   int rc;
@@ -1099,6 +1105,25 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
   if ((rc = h->d_act.ensure((size_t)h->batch * h->kp.rE))) return rc;
   const int nf = h->prm.n * h->kp.nch;
   const unsigned threads = (unsigned)(((h->kp.r + 63) / 64) * 64 > 1024 ? 1024 : ((h->kp.r + 63) / 64) * 64);
+  if (convex_warm_on(h)) {
+    // DDMPC_OPT_CONVEX_WARM_LAW: the whole active-set iteration on the law and M; only instances whose law came from refining
+    // solves and leaves the box go to the filtered cold launch (none unless ddmpc_prepare refined some)
+    int* need = nullptr;
+    if (h->cwl_nref > 0) {
+      if ((rc = h->d_need.ensure((size_t)h->batch * sizeof(int)))) return rc;
+      need = (int*)h->d_need.p;
+    }
+    hipLaunchKernelGGL(ddmpc_warm_convex_step_kernel, dim3((unsigned)h->batch), dim3(threads), 0, h->stream, h->kp,
+                       16 * h->kc.NT, nf, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo, cost,
+                       (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->cwl_nbox,
+                       (const int*)h->d_cwl_tab.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                       need ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, need);
+    HIP_TRY(hipGetLastError());
+    h->beta_stale = false;
+    h->ws_stale = false;
+    if (need) return launch_cold(h, up, yp, uo, cost, status, iters, nullptr, need);
+    return DDMPC_OK;
+  }
   int* need = nullptr;
   if (h->kp.convex) {
     if ((rc = h->d_need.ensure((size_t)h->batch * sizeof(int)))) return rc;
@@ -1754,6 +1779,27 @@ int ddmpc_prepare(ddmpc_handle* h) {
   const size_t ntiles = B * (size_t)(NT * (NT + 1) / 2);
   if (ntiles > 0x7fffffffULL) return fail(DDMPC_ERR_INVALID, "batch too large for ddmpc_prepare");
   if ((rc = h->d_beta.ensure(B * k.rE * sizeof(double)))) return rc;     // beta of the cold launch above
+  // DDMPC_OPT_CONVEX_WARM_LAW: the boxed components and M = K0^-1 E_box, nbox more right-hand sides of the gain kernel
+  const bool cwl = convex_warm_on(h);
+  int nbox = 0;
+  if (cwl) {
+    const int RP = 16 * NT;
+    std::vector<int> ti(3 * (size_t)RP);
+    HIP_TRY(hipMemcpy(ti.data(), h->d_tabi.p, ti.size() * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int> tab;
+    std::vector<int> box_of((size_t)k.r, -1);
+    for (int rho = 0; rho < k.r; ++rho)
+      if (ti[rho] == K_WPRED || ti[rho] == K_WTERM) { box_of[rho] = (int)tab.size(); tab.push_back(rho); }
+    nbox = (int)tab.size();
+    tab.insert(tab.end(), box_of.begin(), box_of.end());
+    if ((rc = h->d_cwl_tab.ensure(tab.size() * sizeof(int))) || (rc = h->d_mcol.ensure(B * (size_t)nbox * k.r * sizeof(double))) ||
+        (rc = h->d_cwl_ref.ensure((B + 1) * sizeof(int))))
+      return rc;
+    if (nbox > CWL_KLDS && (rc = h->d_cwl_sg.ensure(B * (size_t)(nbox * (nbox + 1) / 2) * sizeof(double)))) return rc;
+    HIP_TRY(hipMemcpy(h->d_cwl_tab.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(h->d_cwl_ref.p, 0, (B + 1) * sizeof(int), h->stream));
+  }
+  h->cwl_nbox = nbox;
   bool launched = false;
 #define DDMPC_INSTANCE(NT_, W_)                                                                              \
   if (!launched && NT == NT_) {                                                                               \
@@ -1762,7 +1808,7 @@ int ddmpc_prepare(ddmpc_handle* h) {
       HIP_TRY(raise_lds_limit((const void*)ddmpc_gain_kernel<NT_>, glds)); \
     hipLaunchKernelGGL(ddmpc_gain_kernel<NT_>, dim3((unsigned)B), dim3(256), glds, h->stream, k, 16 * NT, nf, \
                        (const double*)h->d_lfac.p, (const double*)h->d_lfacT.p, (const double*)h->d_beta.p,  \
-                       (double*)h->d_gain.p);                                                                 \
+                       (double*)h->d_gain.p, nbox, (const int*)h->d_cwl_tab.p, (double*)h->d_mcol.p);         \
     launched = true;                                                                                          \
   }
 #include "ddmpc_instances.inc"
@@ -1807,7 +1853,17 @@ int ddmpc_prepare(ddmpc_handle* h) {
     }
     HIP_TRY(hipGetLastError());
   }
+  if (cwl) {
+    // M comes from the unrefined factor: instances whose law was refined keep the filtered cold launch for their box
+    // (ddmpc_step), and their presence sends ddmpc_closed_loop to the per-step path
+    const int mode = (k.lam != 0.0) ? k.refine : DDMPC_REFINE_OFF;
+    hipLaunchKernelGGL(ddmpc_cwl_mark_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, (long long)B, mode,
+                       h->prep_epoch, (const int*)h->d_rflag.p, (int*)h->d_cwl_ref.p);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipStreamSynchronize(h->stream));
+  h->cwl_nref = 0;
+  if (cwl) HIP_TRY(hipMemcpy(&h->cwl_nref, (const int*)h->d_cwl_ref.p + B, sizeof(int), hipMemcpyDeviceToHost));
   h->d_lfac.release();                           // the factor is only needed to form the gain
   h->d_lfacT.release();
   h->prepared = true;
@@ -1883,6 +1939,28 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       return DDMPC_OK;
     case DDMPC_OPT_CONVEX_UPDATE:
       h->convex_update = value != 0;
+      return DDMPC_OK;
+    case DDMPC_OPT_CONVEX_WARM_LAW:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_CONVEX_WARM_LAW must be 0 or 1");
+      if (value == 1 && h->kp.convex) {
+        if (h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
+          return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_CONVEX_WARM_LAW: dense weighting matrices are not supported with the slack box");
+        if (h->large)
+          return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_CONVEX_WARM_LAW: %d rows, the option covers the register-resident kernels "
+                      "((m+p)(L+n) <= 271)", h->kp.r);
+        // every boxed component must change its diagonal entry when its slack reaches the bound (d_s > 0): a zero output
+        // weight makes 1/q swallow 1/lamb_sigma
+        const int RP = 16 * h->kc.NT;
+        std::vector<double> td(4 * (size_t)RP);
+        std::vector<int> ti(3 * (size_t)RP);
+        HIP_TRY(hipMemcpy(td.data(), h->d_tabd.p, td.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ti.data(), h->d_tabi.p, ti.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int rho = 0; rho < h->kp.r; ++rho)
+          if ((ti[rho] == K_WPRED || ti[rho] == K_WTERM) && !(td[rho] - td[RP + rho] > 0.0))
+            return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_CONVEX_WARM_LAW: a boxed output component has no weight (Q entry 0)");
+      }
+      h->convex_warm = value;
+      h->prepared = false;
       return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
@@ -2159,6 +2237,20 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
                        (double*)h->d_beta.p, (signed char*)h->d_act.p);
     HIP_TRY(hipGetLastError());
     h->ws_stale = false;
+  }
+  if (warm_box && convex_warm_on(h) && h->cwl_nref == 0) {
+    // DDMPC_OPT_CONVEX_WARM_LAW: the whole loop of an instance in one workgroup, active-set iterations included
+    if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
+    const unsigned threads = (unsigned)(((h->kp.r + 63) / 64) * 64 > 1024 ? 1024 : ((h->kp.r + 63) / 64) * 64);
+    hipLaunchKernelGGL(ddmpc_closed_loop_convex_warm_kernel, dim3((unsigned)B), dim3(threads), 0, h->stream, h->kp,
+                       16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
+                       (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
+                       (double*)h->d_beta.p, (signed char*)h->d_act.p, h->cwl_nbox, (const int*)h->d_cwl_tab.p,
+                       (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p);
+    HIP_TRY(hipGetLastError());
+    h->ws_stale = false;
+    h->beta_stale = false;
+    warm = true;                                    // (no per-step launches below)
   }
   const unsigned pblocks = (unsigned)((B + 127) / 128);
   // The per-step paths are loops of two or three small launches per control step.  Optionally

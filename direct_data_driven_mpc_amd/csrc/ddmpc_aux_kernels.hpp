@@ -199,10 +199,13 @@ __device__ __forceinline__ double row16_sum(double v) {
 // current one are processed, so HBM latency is paid once per 16 rows; the 16 reciprocal pivots of a tile
 // row are formed once, by lane.  Column 0 of the gain (the offset A^-1 t0) is the beta of the cold solve
 // that exported the factor (zero past window).
+// DDMPC_OPT_CONVEX_WARM_LAW: `nbox` > 0 appends the right-hand sides e_rho for the boxed components rho = box_rho[s]
+// to the same pass; their solutions are the columns of M = K0^-1 E_box, mcol[b][s][rho] (nbox = 0: the gain alone).
 template <int NT>
 __global__ __launch_bounds__(256) void ddmpc_gain_kernel(KParams P, int RPs, int nf, const double* __restrict__ lfac,
                                                          const double* __restrict__ lfacT,
-                                                         const double* __restrict__ beta0, double* __restrict__ gain) {
+                                                         const double* __restrict__ beta0, double* __restrict__ gain,
+                                                         int nbox, const int* __restrict__ box_rho, double* __restrict__ mcol) {
   extern __shared__ __attribute__((aligned(16))) double gsm[];      // 2 x NT x 256 (tile rows) + 2 x 16 (reciprocal pivots)
   auto Lbuf = [&](int buf) __attribute__((always_inline)) -> double* { return gsm + buf * (NT * 256); };
   auto rinv = [&](int buf) __attribute__((always_inline)) -> double* { return gsm + 2 * NT * 256 + buf * 16; };
@@ -226,7 +229,7 @@ __global__ __launch_bounds__(256) void ddmpc_gain_kernel(KParams P, int RPs, int
   auto commit = [&](int buf, int lo, int hi) __attribute__((always_inline)) {      // slots lo..hi of `stage` -> LDS
     static_for<NT>([&](auto J) __attribute__((always_inline)) { if (J >= lo && J <= hi) Lbuf(buf)[J * 256 + tid] = stage[J]; });
   };
-  for (int f0 = 0; f0 < nf; f0 += 16) {
+  for (int f0 = 0; f0 < nf + nbox; f0 += 16) {
     const int f = f0 + wave * 4 + grp;                 // this group's right-hand side (idle groups ride along)
     int rho_f = -1;
     for (int rho = kk; rho < r; rho += 16) rho_f = (P.tabi[1 * RPs + rho] == f) ? rho : rho_f;
@@ -236,6 +239,7 @@ __global__ __launch_bounds__(256) void ddmpc_gain_kernel(KParams P, int RPs, int
       t = fmax(t, dpp_f64<0x122>(t)); t = fmax(t, dpp_f64<0x121>(t));
       rho_f = (int)t;
     }
+    if (f >= nf && f < nf + nbox) rho_f = box_rho[f - nf];   // (group-uniform)
     double y[NT];
     static_for<NT>([&](auto J) __attribute__((always_inline)) { y[J] = 0.0; });
     // ---- forward substitution L y = e ------------------------------------------------------
@@ -292,6 +296,9 @@ __global__ __launch_bounds__(256) void ddmpc_gain_kernel(KParams P, int RPs, int
     }
     if (f < nf) {
       double* g = gain + (b * nrhs + 1 + f) * (long long)r;
+      static_for<NT>([&](auto J) __attribute__((always_inline)) { if (16 * J + kk < r) g[16 * J + kk] = y[J]; });
+    } else if (f < nf + nbox) {
+      double* g = mcol + (b * nbox + (f - nf)) * (long long)r;
       static_for<NT>([&](auto J) __attribute__((always_inline)) { if (16 * J + kk < r) g[16 * J + kk] = y[J]; });
     }
   }
@@ -723,6 +730,395 @@ __global__ void ddmpc_closed_loop_warm_kernel(KParams P, int RPs, int nf, const 
   }
   if (tid < ns) x[b * ns + tid] = xs[tid];
   if (tid == 0) status_out[b] = st;
+}
+// --------------------------------------------------------------------------
+// Warm path under the CONVEX slack box (DDMPC_OPT_CONVEX_WARM_LAW, controller.py:631-677).  The system of an active set
+// A is a diagonal rank-k change of the empty set's K0 (rank_update in ddmpc_cold2.hpp):
+//     K(A) = K0 - E_A diag(d_A) E_A',  d_s = lam (D0_s - D1_s)        t(A) = t0 + bound E_A sgn_A
+//     beta(A) = beta0 + M_A ev,   ev = bound sgn_A + (diag(1/d_A) - M[A,A])^-1 (beta0[A] + M[A,A] bound sgn_A)
+// beta0 is the affine law (the empty active set's iterate) and M = K0^-1 E_box its companion, both formed once per data
+// set by ddmpc_prepare (ddmpc_gain_kernel).  The primal-dual iteration of the cold kernel -- active_set_test: a switch
+// in either direction on every boxed component, the same max_iter cap, the same count of solves -- then runs on the boxed
+// rows alone, without the trajectories, a Gram matrix or a factorisation; the other rows get the M_A ev correction once.
+// Boxed components s = 0 .. nbox-1 in ascending row order; `tab` = [box_rho (nbox) | box_of (r): s, or -1].  The k x k
+// system (packed lower) lives in LDS up to CWL_KLDS and beyond that in the instance's slice of `sg` (nbox (nbox + 1) / 2
+// doubles); the first CWL_CC columns of M that enter A are kept in LDS, further ones are read from global memory.
+// --------------------------------------------------------------------------
+constexpr int CWL_KLDS = 16;
+constexpr int CWL_CC = 4;
+
+struct CwlLds {
+  double bc[WARM_MAX_R];             // current beta of the boxed components (by s)
+  double ev[WARM_MAX_R];             // right-hand side, then coefficients, of the active columns (by position in al)
+  double S[CWL_KLDS * (CWL_KLDS + 1) / 2];
+  double Mc[CWL_CC][WARM_MAX_R];     // cached columns of M
+  int al[WARM_MAX_R];                // the active set: s in ascending order
+  int slot[WARM_MAX_R];              // LDS slot of column s of M, or -1
+  int slotj[CWL_CC];
+  signed char act[WARM_MAX_R];       // sign of the bound component s is held at (0: inside the box)
+  int wcnt[16];
+  int kfin, changed, fail, nslots;
+  __device__ __forceinline__ double m(const double* __restrict__ Mb, int r, int j, int rho) const {
+    const int sl = slot[j];
+    return sl >= 0 ? Mc[sl][rho] : Mb[(long long)j * r + rho];
+  }
+  // beta of row rho after the last solve (b0 = the law's value there)
+  __device__ __forceinline__ double beta(const double* __restrict__ Mb, int r, double b0, int rho) const {
+    double v = b0;
+    for (int i = 0; i < kfin; ++i) v += m(Mb, r, al[i], rho) * ev[i];
+    return v;
+  }
+};
+
+// The active-set iteration of one instance, by the whole workgroup (uniform control flow; blockDim.x >= r > nbox).  b0: the
+// law by row (LDS; the boxed rows at least).  Returns the status it sets (4 at the iteration cap or on a non-positive pivot
+// of the k x k system -- K(A) not positive definite, where the cold kernel's factorisation fails; the beta of the empty set
+// is kept then), 0 otherwise; *iters = the solves, counted as the cold kernel counts them.  s.act / s.al / s.ev / s.kfin
+// describe the result (at the cap: the new active set with the beta of the last solve, as in the cold kernel).
+__device__ int cwl_iterate(const KParams& P, int RPs, int nbox, const int* __restrict__ box_rho, const double* __restrict__ Mb,
+                           double* __restrict__ Sg, const double* b0, CwlLds& s, int* iters) {
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, r = P.r;
+  for (int j = tid; j < nbox; j += nthr) { s.bc[j] = b0[box_rho[j]]; s.act[j] = 0; s.slot[j] = -1; }
+  if (tid == 0) { s.kfin = 0; s.fail = 0; s.nslots = 0; }
+  int iter = 1, st = 0;
+  for (;;) {
+    if (tid == 0) s.changed = 0;
+    __syncthreads();
+    for (int j = tid; j < nbox; j += nthr) {                          // active_set_test
+      const double sh = P.sig_scale * s.bc[j];
+      const int ns = (sh > P.bound) ? 1 : (sh < -P.bound) ? -1 : 0;
+      if (ns != s.act[j]) { s.act[j] = (signed char)ns; s.changed = 1; }
+    }
+    __syncthreads();
+    if (!s.changed) break;
+    if (iter >= P.max_iter) { st = 4; break; }
+    ++iter;
+    // the active set in ascending order: one ballot per wave (nbox < blockDim.x: thread s looks at component s)
+    const bool a = tid < nbox && s.act[tid] != 0;
+    const unsigned long long mk = __ballot(a);
+    if (lane == 0) s.wcnt[wave] = __popcll(mk);
+    __syncthreads();
+    int off = 0, k = 0;
+    for (int w = 0; w < (nthr >> 6); ++w) { off += (w < wave) ? s.wcnt[w] : 0; k += s.wcnt[w]; }
+    if (a) s.al[off + __popcll(mk & ((1ull << lane) - 1ull))] = tid;
+    const int n0 = s.nslots;                                          // (read by all before thread 0 changes it)
+    __syncthreads();
+    if (tid == 0) {                                                   // LDS slots for columns that enter A for the first time
+      int ns_ = n0;
+      for (int i = 0; i < k && ns_ < CWL_CC; ++i) {
+        const int j = s.al[i];
+        if (s.slot[j] < 0) { s.slot[j] = ns_; s.slotj[ns_] = j; ++ns_; }
+      }
+      s.nslots = ns_;
+    }
+    __syncthreads();
+    const int n1 = s.nslots;
+    for (int e = tid; e < (n1 - n0) * r; e += nthr) {                 // coalesced r-vectors
+      const int sl = n0 + e / r, rho = e - (e / r) * r;
+      s.Mc[sl][rho] = Mb[(long long)s.slotj[sl] * r + rho];
+    }
+    __syncthreads();
+    // S = diag(1/d_A) - M[A,A] (lower triangle) and the right-hand side beta0[A] + M[A,A] bound sgn_A
+    double* Sp = (k <= CWL_KLDS) ? s.S : Sg;
+    for (int e = tid; e < k * k; e += nthr) {
+      const int i = e / k, l = e - i * k;
+      if (l <= i) {
+        const int ri = box_rho[s.al[i]];
+        double v = -s.m(Mb, r, s.al[l], ri);
+        if (l == i) v += 1.0 / (P.lam * (P.tabd[0 * RPs + ri] - P.tabd[1 * RPs + ri]));
+        Sp[i * (i + 1) / 2 + l] = v;
+      }
+    }
+    for (int i = tid; i < k; i += nthr) {
+      const int ri = box_rho[s.al[i]];
+      double g = b0[ri];
+      for (int l = 0; l < k; ++l) g += s.m(Mb, r, s.al[l], ri) * ((double)s.act[s.al[l]] * P.bound);
+      s.ev[i] = g;
+    }
+    __syncthreads();
+    // Cholesky, right-looking, one column per step
+    for (int c = 0; c < k; ++c) {
+      if (tid == 0) {
+        const double pv = Sp[c * (c + 1) / 2 + c];
+        if (!(pv > 0.0)) s.fail = 1; else Sp[c * (c + 1) / 2 + c] = sqrt(pv);
+      }
+      __syncthreads();
+      if (s.fail) break;
+      const double dc = Sp[c * (c + 1) / 2 + c];
+      for (int i = c + 1 + tid; i < k; i += nthr) Sp[i * (i + 1) / 2 + c] /= dc;
+      __syncthreads();
+      const int nt = k - c - 1;
+      for (int e = tid; e < nt * nt; e += nthr) {
+        const int ii = e / nt, jj = e - ii * nt;
+        if (jj <= ii) {
+          const int i = c + 1 + ii, j = c + 1 + jj;
+          Sp[i * (i + 1) / 2 + j] -= Sp[i * (i + 1) / 2 + c] * Sp[j * (j + 1) / 2 + c];
+        }
+      }
+      __syncthreads();
+    }
+    if (s.fail) { if (tid == 0) s.kfin = 0; st = 4; __syncthreads(); break; }
+    if (tid == 0) {                                                   // L y = g, L' x = y, ev = bound sgn + x
+      for (int i = 0; i < k; ++i) {
+        double v = s.ev[i];
+        for (int l = 0; l < i; ++l) v -= Sp[i * (i + 1) / 2 + l] * s.ev[l];
+        s.ev[i] = v / Sp[i * (i + 1) / 2 + i];
+      }
+      for (int i = k - 1; i >= 0; --i) {
+        double v = s.ev[i];
+        for (int l = i + 1; l < k; ++l) v -= Sp[l * (l + 1) / 2 + i] * s.ev[l];
+        s.ev[i] = v / Sp[i * (i + 1) / 2 + i];
+      }
+      for (int i = 0; i < k; ++i) s.ev[i] += (double)s.act[s.al[i]] * P.bound;
+      s.kfin = k;
+    }
+    __syncthreads();
+    for (int j = tid; j < nbox; j += nthr) s.bc[j] = s.beta(Mb, r, b0[box_rho[j]], box_rho[j]);
+  }
+  *iters = iter;
+  return st;
+}
+
+// Output stage of one component with its active flag: the formulas of the cold kernel's output stage (scalar / diagonal
+// weights); z_out = ubar / w of the component, the return value its share of the cost.
+__device__ __forceinline__ double cwl_component(const KParams& P, int RPs, int rho, double beta, int sa, const double* pv,
+                                                double* z_out) {
+  const int kind = P.tabi[0 * RPs + rho];
+  const int pidx = P.tabi[1 * RPs + rho];
+  const double D = sa ? P.tabd[1 * RPs + rho] : P.tabd[0 * RPs + rho];
+  const double tb = P.tabd[2 * RPs + rho];
+  const double wq = P.tabd[3 * RPs + rho];
+  const double tp = (pidx >= 0) ? pv[pidx] : tb;
+  const double z = tp + sa * P.bound - P.lam * D * beta;
+  double contrib = P.lam * beta * z;
+  if (kind == K_UFREE || kind == K_YFREE) { const double dlt = z - tb; contrib += wq * dlt * dlt; }
+  else if (kind == K_WINT) { const double sg = z - tp; contrib += P.lamb_sigma * sg * sg; }
+  else if (kind == K_WTERM) { const double sg = z - tb; contrib += P.lamb_sigma * sg * sg; }
+  else if (kind == K_WPRED) {
+    const double sg = (sa != 0) ? sa * P.bound : -P.lam * beta / P.lamb_sigma;
+    const double dlt = z - sg - tb;
+    contrib += wq * dlt * dlt + P.lamb_sigma * sg * sg;
+  }
+  *z_out = z;
+  return contrib;
+}
+
+// One warm step under the slack box for the batch: grid = batch, block = r rounded up to 64 (the geometry of
+// ddmpc_warm_step_kernel).  Mcol [batch][nbox][r], sg [batch][nbox (nbox + 1) / 2] (used for k > CWL_KLDS only).
+// `refined` (may be null): instances whose law came from refining solves (ddmpc_prepare); their M is the unrefined
+// factor's, so one whose law leaves the box is flagged in need_cold and left to the filtered cold launch, as without
+// the option.
+__global__ void ddmpc_warm_convex_step_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
+                                              const int* __restrict__ prep_status, const double* __restrict__ u_past,
+                                              const double* __restrict__ y_past, double* __restrict__ u_opt,
+                                              double* __restrict__ cost, int* __restrict__ status, int* __restrict__ iters,
+                                              double* __restrict__ beta_ws, signed char* __restrict__ act_ws, int nbox,
+                                              const int* __restrict__ tab, const double* __restrict__ Mcol,
+                                              double* __restrict__ sg, const int* __restrict__ refined,
+                                              int* __restrict__ need_cold) {
+  __shared__ double pv[WARM_MAX_NF];
+  __shared__ double red[32];
+  __shared__ double bsh[WARM_MAX_R];
+  __shared__ CwlLds s;
+  const long long b = blockIdx.x;
+  const int tid = threadIdx.x, r = P.r, nrhs = nf + 1;
+  const int nyp = nf - P.npu;
+  for (int f = tid; f < nf; f += blockDim.x)
+    pv[f] = (f < P.npu) ? u_past[b * P.npu + f] : y_past[b * nyp + (f - P.npu)];
+  __syncthreads();
+  const double* g = gain + b * (long long)nrhs * r;
+  int viol = 0;
+  for (int rho = tid; rho < r; rho += blockDim.x) {
+    // all loads of a chunk of 8 columns are issued before they are consumed (HBM-bound: keep bytes in flight)
+    double beta = g[rho];
+    const double* gc = g + r + rho;
+    int f = 0;
+    for (; f + 8 <= nf; f += 8) {
+      double v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = gc[(long long)(f + q) * r];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) beta += pv[f + q] * v[q];
+    }
+    for (; f < nf; ++f) beta += pv[f] * gc[(long long)f * r];
+    bsh[rho] = beta;
+    const int kind = P.tabi[0 * RPs + rho];
+    if ((kind == K_WPRED || kind == K_WTERM) && fabs(P.sig_scale * beta) > P.bound) viol = 1;
+  }
+  viol = __syncthreads_or(viol);
+  const bool cold_route = refined != nullptr && refined[b] != 0;
+  if (need_cold != nullptr && tid == 0) need_cold[b] = cold_route ? viol : 0;
+  if (cold_route && viol) return;                     // uniform: the filtered cold launch produces this instance's outputs
+  int st = prep_status[b], it = 1;
+  const double* Mb = Mcol + b * (long long)nbox * r;
+  const bool iterate = viol && st <= 1;               // (a failed factorisation: the cold kernel stops after its first solve)
+  if (iterate) {
+    const int dst = cwl_iterate(P, RPs, nbox, tab, Mb, sg + b * (long long)(nbox * (nbox + 1) / 2), bsh, s, &it);
+    if (dst) st = dst;
+  }
+  const int* box_of = tab + nbox;
+  double part = 0.0;
+  bool finite = true;
+  for (int rho = tid; rho < r; rho += blockDim.x) {
+    double beta = bsh[rho], z;
+    int sa = 0;
+    if (!iterate) {
+      part += warm_component(P, RPs, rho, beta, pv, bsh, &z);
+    } else {
+      const int j = box_of[rho];
+      sa = (j >= 0) ? s.act[j] : 0;
+      beta = s.beta(Mb, r, beta, rho);
+      part += cwl_component(P, RPs, rho, beta, sa, pv, &z);
+    }
+    finite = finite && (fabs(beta) < 1e300);
+    const int oidx = P.tabi[2 * RPs + rho];
+    if (oidx >= 0) u_opt[b * (long long)((P.Ln - P.npu / P.m) * P.m) + oidx] = z;
+    beta_ws[b * (long long)P.rE + rho] = beta;
+    act_ws[b * (long long)P.rE + rho] = (signed char)sa;
+  }
+  part = wave_sum(part);
+  const unsigned long long okmask = __ballot(finite);
+  if ((tid & 63) == 0) { red[tid >> 6] = part; red[16 + (tid >> 6)] = (okmask == ~0ull) ? 0.0 : 1.0; }
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0, bad = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { tot += red[w]; bad += red[16 + w]; }
+    if (bad != 0.0 || !(fabs(tot) < 1e300)) st = 4;
+    cost[b] = tot;
+    status[b] = st;
+    if (iters) iters[b] = it;
+  }
+}
+
+// Whole closed loop of one instance in one workgroup under the slack box (DDMPC_OPT_CONVEX_WARM_LAW): per solve the law on
+// the boxed rows and the n_mpc_step*m input rows in use, the active-set iteration of ddmpc_warm_convex_step_kernel, the
+// M_A ev correction of the input rows, then the plant/FIFO steps of ddmpc_plant_kernel.  Same loop order as
+// utilities/controller/controller_operation.py:263-305; an instance whose solve is not optimal stops evolving (NaN from
+// there on), as with the per-step path.  No cold fall-back: every k is served here.
+__global__ void ddmpc_closed_loop_convex_warm_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
+                                                     const int* __restrict__ prep_status, int ns, const double* __restrict__ pl,
+                                                     int n_steps, int n_mpc_step, double* __restrict__ x,
+                                                     double* __restrict__ u_past, double* __restrict__ y_past,
+                                                     const double* __restrict__ w, double* __restrict__ u_sys,
+                                                     double* __restrict__ y_sys, int* __restrict__ status_out,
+                                                     double* __restrict__ beta_ws, signed char* __restrict__ act_ws, int nbox,
+                                                     const int* __restrict__ tab, const double* __restrict__ Mcol,
+                                                     double* __restrict__ sg) {
+  __shared__ double pv[WARM_MAX_NF];
+  __shared__ double uo[WARM_MAX_NF];      // the first n_mpc_step*m entries of optimal_u
+  __shared__ double xs[16], yv[16], xn[16];   // (the plant's vectors in LDS: no scratch)
+  __shared__ double bsh[WARM_MAX_R];
+  __shared__ CwlLds s;
+  const long long b = blockIdx.x;
+  const int tid = threadIdx.x, r = P.r, nrhs = nf + 1, m = P.m, p = P.p;
+  const int n = P.npu / m, nyp = nf - P.npu;
+  const double* A = pl;
+  const double* Bm = A + ns * ns;
+  const double* C = Bm + ns * m;
+  const double* Dm = C + p * ns;
+  for (int f = tid; f < nf; f += blockDim.x)
+    pv[f] = (f < P.npu) ? u_past[b * P.npu + f] : y_past[b * nyp + (f - P.npu)];
+  if (tid < ns) xs[tid] = x[b * ns + tid];
+  const int st0 = prep_status[b];
+  const double nanv = __longlong_as_double(0x7ff8000000000000LL);
+  const double* g = gain + b * (long long)nrhs * r;
+  const double* Mb = Mcol + b * (long long)nbox * r;
+  double* Sg = sg + b * (long long)(nbox * (nbox + 1) / 2);
+  const int* box_of = tab + nbox;
+  const int nuse = n_mpc_step * m;
+  double* up = pv;
+  double* yp = pv + P.npu;
+  int stc = 0;                                        // worst status so far (ddmpc_plant_kernel's st_acc)
+  for (int t0 = 0; t0 < n_steps; t0 += n_mpc_step) {
+    __syncthreads();
+    const bool last = (t0 + n_mpc_step >= n_steps);
+    int viol = 0;
+    for (int rho = tid; rho < r; rho += blockDim.x) {
+      const int oidx = P.tabi[2 * RPs + rho];
+      const bool boxed = box_of[rho] >= 0;
+      if ((oidx >= 0 && oidx < nuse) || boxed || last) {
+        double beta = g[rho];
+        for (int f = 0; f < nf; ++f) beta += pv[f] * g[(long long)(1 + f) * r + rho];
+        bsh[rho] = beta;
+        if (boxed && fabs(P.sig_scale * beta) > P.bound) viol = 1;
+      }
+    }
+    viol = __syncthreads_or(viol);
+    int st = st0, it = 1;
+    const bool iterate = viol && st <= 1;
+    if (iterate) {
+      const int dst = cwl_iterate(P, RPs, nbox, tab, Mb, Sg, bsh, s, &it);
+      if (dst) st = dst;
+    }
+    int nonfin = 0;
+    for (int rho = tid; rho < r; rho += blockDim.x) {
+      const int oidx = P.tabi[2 * RPs + rho];
+      const int j = box_of[rho];
+      const bool use = oidx >= 0 && oidx < nuse;
+      if (use || j >= 0 || last) {
+        const int sa = (iterate && j >= 0) ? s.act[j] : 0;
+        const double beta = iterate ? s.beta(Mb, r, bsh[rho], rho) : bsh[rho];
+        nonfin |= !(fabs(beta) < 1e300);
+        if (use) {
+          double z;
+          (void)cwl_component(P, RPs, rho, beta, sa, pv, &z);
+          uo[oidx] = z;
+        }
+        if (last && beta_ws) { beta_ws[b * (long long)P.rE + rho] = beta; act_ws[b * (long long)P.rE + rho] = (signed char)sa; }
+      }
+    }
+    if (__syncthreads_or(nonfin)) st = 4;
+    stc = (st > stc) ? st : stc;
+    if (tid == 0) {
+      const int nsub = (t0 + n_mpc_step <= n_steps) ? n_mpc_step : n_steps - t0;
+      for (int j = 0; j < nsub; ++j) {
+        const int k = t0 + j;
+        double* us = u_sys + (b * n_steps + k) * m;
+        double* ys = y_sys + (b * n_steps + k) * p;
+        if (stc > 1) {
+          for (int i = 0; i < m; ++i) us[i] = nanv;
+          for (int i = 0; i < p; ++i) ys[i] = nanv;
+          continue;
+        }
+        const double* uk = uo + j * m;
+        const double* wk = w + (b * n_steps + k) * p;
+        for (int i = 0; i < p; ++i) {              // y = C x + D u + w with the state BEFORE the update
+          double sum = wk[i];
+          for (int q = 0; q < ns; ++q) sum += C[i * ns + q] * xs[q];
+          for (int q = 0; q < m; ++q) sum += Dm[i * m + q] * uk[q];
+          yv[i] = sum;
+          ys[i] = sum;
+        }
+        for (int i = 0; i < ns; ++i) {
+          double sum = 0.0;
+          for (int q = 0; q < ns; ++q) sum += A[i * ns + q] * xs[q];
+          for (int q = 0; q < m; ++q) sum += Bm[i * m + q] * uk[q];
+          xn[i] = sum;
+        }
+        for (int i = 0; i < ns; ++i) xs[i] = xn[i];
+        for (int i = 0; i < m; ++i) us[i] = uk[i];
+        for (int i = 0; i < (n - 1) * m; ++i) up[i] = up[i + m];       // FIFO shift
+        for (int i = 0; i < m; ++i) up[(n - 1) * m + i] = uk[i];
+        for (int i = 0; i < (n - 1) * p; ++i) yp[i] = yp[i + p];
+        for (int i = 0; i < p; ++i) yp[(n - 1) * p + i] = yv[i];
+      }
+    }
+  }
+  __syncthreads();
+  for (int f = tid; f < nf; f += blockDim.x) {
+    if (f < P.npu) u_past[b * P.npu + f] = pv[f]; else y_past[b * nyp + (f - P.npu)] = pv[f];
+  }
+  if (tid < ns) x[b * ns + tid] = xs[tid];
+  if (tid == 0) status_out[b] = stc;
+}
+// ddmpc_prepare with DDMPC_OPT_CONVEX_WARM_LAW: which instances' laws come from refining solves (ALWAYS: all; AUTO: those
+// the factor-export launch flagged, stamp `epoch`).  refined[batch] counts them.
+__global__ void ddmpc_cwl_mark_kernel(long long batch, int mode, int epoch, const int* __restrict__ rflag, int* __restrict__ refined) {
+  const long long b = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (b >= batch) return;
+  const int v = (mode == 2 || (mode == 1 && rflag != nullptr && rflag[b] == epoch)) ? 1 : 0;
+  refined[b] = v;
+  if (v) atomicAdd(refined + batch, 1);
 }
 // --------------------------------------------------------------------------
 // Persistent-excitation guard (controller.py:275-296, hankel_matrix.py:55-87) for a batch.

@@ -256,6 +256,12 @@ class BatchedDDMPC:
         factor (rank-k update), False = every iteration factors the system again (DDMPC_OPT_CONVEX_UPDATE)."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_CONVEX_UPDATE, 1 if on else 0))
 
+    def set_convex_warm_law(self, on: bool) -> None:
+        """Slack CONVEX: True = `prepare` also forms M = K0^-1 E_box and `step` / `closed_loop` run the active-set iterations
+        on the law and M, without cold re-solves (DDMPC_OPT_CONVEX_WARM_LAW; costs nbox * r doubles per instance), False
+        (default) = instances whose law leaves the box are re-solved cold.  No effect without the slack box."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_CONVEX_WARM_LAW, 1 if on else 0))
+
     def set_gram_launch(self, kind: str) -> None:
         """Structured Gram of plants with other than two or four channels on the register-resident kernels: "matrix_pipe"
         (default: streaming launch, lag sums and window walk by MFMA) or "staged" (round 4's launch with the whole trajectory

@@ -135,6 +135,18 @@ extern "C" {
                                          launch of round 4 that stages the whole trajectory and walks on the vector units (the default
                                          up to five channels).  Same tiles to rounding; DDMPC_ERR_UNSUPPORTED when the requested launch
                                          cannot hold the shape */
+#define DDMPC_OPT_CONVEX_WARM_LAW 10     /* ROBUST controllers with the CONVEX slack box on the register-resident kernels: 1 = ddmpc_prepare
+                                         also forms M = K0^-1 E_box per instance (K0 the system of the empty active set, E_box the unit
+                                         vectors of the p*L boxed slack components; [batch][p*L][(m+p)(L+n)] doubles, 65 KB per instance
+                                         at L = 30, m = p = 2, plus p*L(p*L+1)/2 doubles of k x k scratch when p*L > 16), and ddmpc_step /
+                                         ddmpc_closed_loop (paths AUTO and WARM) run the whole primal-dual active-set iteration on the law
+                                         and M: no cold re-solve, no read of the trajectories.  Same active sets, iteration counts, status
+                                         and -- to rounding -- solutions as ddmpc_solve.  Instances whose law ddmpc_prepare formed from
+                                         refining solves (DDMPC_REFINE_ALWAYS: all; AUTO: those it flags) keep today's route: ddmpc_step
+                                         re-solves those whose law leaves the box with the filtered cold launch, and ddmpc_closed_loop
+                                         takes the per-step path when there is any.  0 (default) = the filtered cold re-solve.  Setting
+                                         it invalidates the prepared law.  DDMPC_ERR_UNSUPPORTED with dense weights, beyond 271 rows and
+                                         for a boxed output component without weight (Q entry 0); no effect without the slack box */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -235,9 +247,12 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
  *   bound), i.e. the first primal-dual active-set iterate.
  * ddmpc_step: same contract and outputs as ddmpc_solve; uses the affine law (preparing on first
  *   use).  With slack CONVEX an instance whose affine iterate keeps every boxed sigma inside
- *   |sigma| <= c*eps_max is optimal as it is (iters = 1); the others are re-solved by the cold kernel
- *   in the same call (full active-set iteration, iters >= 2), so the results equal ddmpc_solve's.
- *   The status of a warm step is the status of the factorisation it rests on.
+ *   |sigma| <= c*eps_max is optimal as it is (iters = 1); by default the others are re-solved by the cold
+ *   kernel in the same call (full active-set iteration, iters >= 2), so the results equal ddmpc_solve's.
+ *   With DDMPC_OPT_CONVEX_WARM_LAW = 1 the active-set iteration runs on the law and M = K0^-1 E_box
+ *   instead (rank-k changes of the empty set's system, no cold re-solve; see that option).
+ *   The status of a warm step is the status of the factorisation it rests on (solver_error at the
+ *   active-set iteration cap, as for ddmpc_solve).
  * ddmpc_get_gain: out [batch, nf+1, r] doubles, r = (m+p)(L+n) components in the internal
  *   time-major order rho = k*(m+p) + ch (ch < m: ubar, else ybar+sigma).
  * Beyond 271 rows: see the note on problem sizes at ddmpc_create (the data-dependent factors are kept, no law). */
