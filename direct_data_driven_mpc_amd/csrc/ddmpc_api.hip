@@ -147,6 +147,19 @@ size_t lds_doubles_for(const KernelChoice& kc, int xs_len) { return ((size_t)kc.
 
 }  // namespace
 
+// The implementation that serves a handle's solves (select_route).
+enum class Route {
+  Cold,             // the register-resident cold kernels (trajectories beyond the LDS included) + the NOMINAL rescue kernel
+  RobustPhases,     // ROBUST beyond the register-resident kernels: the phase kernels (ddmpc_rr3.hpp)
+  RobustOneWg,      // ... the one-workgroup kernel (ddmpc_large_solve_kernel)
+  NominalPhases,    // NOMINAL beyond the register-resident kernels: the phase kernels (ddmpc_rr2*.hpp)
+  NominalOneWg,     // ... the one-workgroup kernel (ddmpc_nominal_rr_kernel)
+};
+
+// What a launch of the global-workspace routes does: the whole solve, the data-dependent factors alone (ddmpc_prepare), or a
+// solve on the factors ddmpc_prepare kept (ddmpc_step).  The values are the template argument of the one-workgroup kernels.
+enum class Stage { Solve = 0, Factors = 1, OnFactors = 2 };
+
 struct ddmpc_handle {
   ddmpc_params prm{};
   std::vector<double> Qh, Rh, us_h, ys_h;
@@ -214,16 +227,33 @@ struct ddmpc_handle {
   HostBuf h_flag;                          // one pinned word: the "factor again" count of the rank decision (launch_rr2_factors)
   hipEvent_t ev_flag = nullptr;            // ... and the event behind its copy
   bool prepared = false;
+  Route prep_route = Route::Cold;          // the route ddmpc_prepare formed what it kept on (it serves no other)
+  Route solve_route = Route::Cold;         // the route of the last solve or step (Cold until the first one)
   int closed_loop_path = DDMPC_PATH_AUTO;
   bool closed_loop_graph = false;
   bool large = false;                      // r beyond the register-resident cold kernels: global-workspace kernels only
-  bool large_nominal = false;              // ... NOMINAL: every solve is the rank-revealing kernel; else ddmpc_large_solve_kernel
+  bool large_nominal = false;              // ... NOMINAL (the rank-revealing kernels); else ROBUST
   int n_free = 0;                          // weighted (free) components, nominal scheme: rows of the reduced normal matrix
-  bool stamps_on = false;
+  bool stamps_on = false;                  // ddmpc_debug_stamps (the phase kernels carry no stamps)
   bool beta_stale = false;                 // the last solve was a warm step that skipped the beta / active-set workspace
   const double* last_up = nullptr;
   const double* last_yp = nullptr;
 };
+
+// The one decision of which implementation serves a handle.  Beyond the register-resident kernels the phase kernels take
+// batches up to 65535 (grid rows), up to 1024 rows (64-bit masks over 16-column chunks) and no diagnostic stamps
+// (DDMPC_OPT_LARGE_PIPELINE selects them by default); the one-workgroup kernels serve everything else at that size.
+static Route select_route(const ddmpc_handle* h) {
+  if (!h->large) return Route::Cold;
+  const bool phases = h->large_pipeline == DDMPC_PIPELINE_PHASES && h->batch <= 65535 && !h->stamps_on && h->kp.r <= 1024;
+  if (h->large_nominal) return phases ? Route::NominalPhases : Route::NominalOneWg;
+  return phases ? Route::RobustPhases : Route::RobustOneWg;
+}
+
+static bool nominal_route(Route r) { return r == Route::NominalPhases || r == Route::NominalOneWg; }
+
+// What ddmpc_prepare kept is the input of the route it was formed on only (the routes keep different things next to the factors).
+static bool prep_valid(const ddmpc_handle* h) { return h->prepared && h->prep_route == select_route(h); }
 
 extern "C" {
 
@@ -633,9 +663,9 @@ int ddmpc_create(const ddmpc_params* params, int64_t batch, int device, ddmpc_ha
   if (h->lds_bytes > 160 * 1024) {
     // hankel_matrix.py:39-51 takes any N >= L.  A trajectory beyond the LDS is never staged: G = H H' comes from the streaming
     // Gram kernel of the phase pipeline (trajectory in chunks), written into the kernel's tiles (rr2_gram_tiles*_kernel), and the
-    // cold kernel runs in its `gpre` mode with no trajectory region at all.  What needs the trajectory on chip -- the
-    // exact-Hankel residual check of AUTO refinement and the refining variant -- is not available at such N: an instance the
-    // a-priori bound cannot dismiss is reported "optimal_inaccurate" (launch_cold), DDMPC_REFINE_ALWAYS is refused.
+    // cold kernel runs in its `gpre` mode with no trajectory region at all.  Refinement goes without the whole trajectory on
+    // chip: AUTO's exact-Hankel residual check is streamed by the Hankel kernel of the phase pipeline (long_data_residual_check),
+    // and the refining variant passes the trajectory through a window chunk by chunk (ld_window below).
     const int tch = ((RR2_XCAP / k.nch) - k.Ln - 3) & ~3;
     if (k.r > 1024 || tch < 4 || p.weight_kind == DDMPC_WEIGHT_DENSE) {
       const size_t need = h->lds_bytes;
@@ -785,8 +815,18 @@ static unsigned large_threads(size_t r) {   // workgroup size of the global-work
   return r <= 256 ? 256u : (r <= 1024 ? 512u : 1024u);           // r <= PSD_RPT * threads (blocked substitutions)
 }
 
-// want_ws: also write the beta / active-set workspace (what ddmpc_get_solution, the gain kernel and the slack-box warm
-// step read).  A plain cold solve skips it (1.2 KB of HBM writes per instance) and ddmpc_get_solution re-solves on demand.
+// Workgroup size of the warm-path kernels (the affine law): a thread per component, 1024 at most.
+static unsigned warm_threads(int r) { return (unsigned)std::min(((r + 63) / 64) * 64, 1024); }
+
+// AUTO refinement: the per-instance flags + one counter word behind them, cleared once when they are first allocated.
+static int ensure_rflag(ddmpc_handle* h) {
+  const size_t bytes = ((size_t)h->batch + 1) * sizeof(int);
+  const bool fresh = h->d_rflag.bytes < bytes;
+  const int rc = h->d_rflag.ensure(bytes);
+  if (!rc && fresh) HIP_TRY(hipMemsetAsync(h->d_rflag.p, 0, bytes, h->stream));
+  return rc;
+}
+
 // Next launch stamp of the AUTO refinement flags (flag[b] == stamp <=> instance b was flagged by THIS launch; the counter word
 // holds the largest stamp that flagged anything).  Stamps only grow, so nothing is cleared between launches -- except
 // before the 32-bit stamp would wrap, when the flags and the counter are zeroed once and the stamps restart.
@@ -805,8 +845,6 @@ static void launch_rr2_gram(hipStream_t st, const KParams& k, const double* ud, 
   else hipLaunchKernelGGL(rr2_gram_kernel, grid, dim3(256), 0, st, k, ud, yd, iperm, ws, stride, n16, dd);
 }
 
-// large_mode (ROBUST controllers beyond the register-resident kernels only): 0 whole solve, 1 the data-dependent part alone
-// (ddmpc_prepare), 2 a solve on what that left in the workspace (ddmpc_step) -- see ddmpc_large_solve_kernel.
 // Structured Gram for channel counts other than four: the Gram tiles of `nb` instances (data at ud / yd) into slots b0 .. of
 // the handle's buffer, and the pointers into `kq`.  cacheable: the data set is the handle's (h->ud / h->yd) -- one launch serves
 // every cold-kernel launch until the data may have changed (ddmpc_set_data, ddmpc_solve, ddmpc_solve_from_host, ddmpc_prepare
@@ -843,15 +881,61 @@ static int gram_pre_launch(ddmpc_handle* h, KParams& kq, const double* ud, const
   return DDMPC_OK;
 }
 
-// ---- ROBUST controllers beyond the register-resident kernels on the phase kernels (ddmpc_rr3.hpp) ----------------------------
+// The product H (H' v) of the phase pipelines: on the matrix pipe when the shape allows it (up to 16 channels, at most 8 tiles
+// per half, LDS within reach), with as many workgroups per instance as leave >= 64 columns each; else the plain kernel (ng 0).
+struct HankelLaunch { int ng = 0; size_t lds = 0; };
+static int pick_hankel_launch(const KParams& k, HankelLaunch* hk) {
+  if (k.nch > 16) return DDMPC_OK;
+  for (int ng = RR2_NG; ng >= 1 && hk->ng == 0; --ng) {
+    const Rr2HankelGeom G = rr2_hankel_geom(k.c, k.Ln, k.nch, ng);
+    const size_t bytes = rr2_hankel_mfma_lds(G, k.Ln) * sizeof(double);
+    if ((G.cg >= 64 || ng == 1) && bytes <= 80 * 1024 && G.ntA <= 8 && G.ntZ <= 8) { hk->ng = ng; hk->lds = bytes; }
+  }
+  if (hk->ng && hk->lds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)rr2_hankel_mfma_kernel, hk->lds));
+  return DDMPC_OK;
+}
+// (RR2_NG workgroups per instance whatever hk.ng is: the consumers sum RR2_NG partial results, and a workgroup past the last
+//  column group writes the zeros they expect -- launched with hk.ng < RR2_NG workgroups, short trajectories summed whatever the
+//  allocator had left in the other slots)
+static void launch_hankel(const HankelLaunch& hk, hipStream_t st, unsigned nb, const Rr2Solve& S, const KParams& k,
+                          const double* ud, const double* yd, int slot, int pass) {
+  if (hk.ng) hipLaunchKernelGGL(rr2_hankel_mfma_kernel, dim3((unsigned)RR2_NG, nb), dim3(512), hk.lds, st, S, k, ud, yd, slot, pass, hk.ng);
+  else hipLaunchKernelGGL(rr2_hankel_kernel, dim3((unsigned)RR2_NG, nb), dim3(512), 0, st, S, k, ud, yd, slot, pass);
+}
+
+// Doubles of the Minv blocks (64 x 64 diagonal blocks) of one instance's factor of n16 rows (ddmpc_rr2.hpp).
+static long long rr2_m64(int n16) { return (long long)((n16 + RR2_NB - 1) / RR2_NB) * RR2_NB * RR2_NB; }
+// Per-instance workspace slices of the phase pipelines (whole 16-row tiles): the packed factor of G (ROBUST), those of G and T
+// (NOMINAL; the one-workgroup kernel keeps the same slices when they do not fit its LDS).
 static long long rr3_ndbl(const ddmpc_handle* h) { return (long long)pk_size(((size_t)h->kp.r + 15) & ~(size_t)15); }
+static long long rr2_ndbl(const ddmpc_handle* h) { return rr3_ndbl(h) + (long long)pk_size(((size_t)h->n_free + 15) & ~(size_t)15); }
+// Per-instance workspace slice of ddmpc_large_solve_kernel (packed rows, then the lag sums or the Schur block of the components
+// the slack box acts on), on a 128-byte boundary.
+static size_t large_robust_stride(const KParams& k, const ddmpc_params& p) {
+  const size_t nB = k.convex ? (size_t)p.p * p.L : 0, nlag = (size_t)k.Ln * k.nch * k.nch, sb = 2 * pk_size(nB);
+  return (pk_size((size_t)k.r) + (nlag > sb ? nlag : sb) + 15) & ~(size_t)15;
+}
+
+// Lock-step Cholesky of the phase pipelines by 64-column panels: a panel launch, then the update of the row tiles below it.
+static void launch_rr2_cholesky(hipStream_t st, const Rr2Chol& F, int n16, size_t B) {
+  const int nt = n16 >> 4;
+  for (int c0 = 0; c0 < n16; c0 += RR2_NB) {
+    hipLaunchKernelGGL(rr2_chol_panel_kernel, dim3(1, (unsigned)B), dim3(256), 0, st, F, c0);
+    const int nbelow = nt - (c0 >> 4) - 4;                 // row tiles below the diagonal block
+    if (nbelow > 0)
+      hipLaunchKernelGGL(rr2_chol_update_kernel<RR2_UT>, dim3((unsigned)((nbelow + 4 * RR2_UT - 1) / (4 * RR2_UT)), (unsigned)B),
+                         dim3(256), 0, st, F, c0);
+  }
+}
+
+// ---- ROBUST controllers beyond the register-resident kernels on the phase kernels (ddmpc_rr3.hpp) ----------------------------
 // What depends on the data and the weights alone: G (boxed components last) + lam D0, its Cholesky factor with the Minv blocks.
 static int launch_rr3_factors(ddmpc_handle* h) {
   const KParams& k = h->kp;
   const int r = k.r, n16 = (r + 15) & ~15, rv = (r + 1) & ~1;
   const long long ndbl = rr3_ndbl(h), mstride = 2 * (long long)rv + 2;
   const size_t B = (size_t)h->batch;
-  const long long m64G = (long long)((n16 + RR2_NB - 1) / RR2_NB) * RR2_NB * RR2_NB;
+  const long long m64G = rr2_m64(n16);
   int rc;
   if ((rc = h->d_rr.ensure(B * (size_t)ndbl * sizeof(double))) || (rc = h->d_rrmeta.ensure(B * (size_t)mstride * sizeof(int))) ||
       (rc = h->d_rr2d.ensure(B * 4 * sizeof(unsigned long long))) || (rc = h->d_rr2mt.ensure(B * (size_t)m64G * sizeof(double))))
@@ -867,14 +951,7 @@ static int launch_rr3_factors(ddmpc_handle* h) {
   FG.dmax = dd + 0; FG.d_stride = 4; FG.tol_rel = 0.0; FG.skip = (int*)h->d_rrmeta.p; FG.s_stride = mstride; FG.nflag = r;
   FG.live = dd + 2; FG.l_stride = 4; FG.m64 = (double*)h->d_rr2mt.p; FG.m64_stride = m64G;
   FG.res = nullptr; FG.res_stride = 0; FG.dead = nullptr; FG.dead_stride = 0;
-  const int nt = n16 >> 4;
-  for (int c0 = 0; c0 < n16; c0 += RR2_NB) {
-    hipLaunchKernelGGL(rr2_chol_panel_kernel, dim3(1, (unsigned)B), dim3(256), 0, h->stream, FG, c0);
-    const int nbelow = nt - (c0 >> 4) - 4;
-    if (nbelow > 0)
-      hipLaunchKernelGGL(rr2_chol_update_kernel<RR2_UT>, dim3((unsigned)((nbelow + 4 * RR2_UT - 1) / (4 * RR2_UT)), (unsigned)B),
-                         dim3(256), 0, h->stream, FG, c0);
-  }
+  launch_rr2_cholesky(h->stream, FG, n16, B);
   HIP_TRY(hipGetLastError());
   return DDMPC_OK;
 }
@@ -884,7 +961,7 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
                             int32_t* status, int32_t* iters) {
   const int r = kq.r, n16 = (r + 15) & ~15, rv = (r + 1) & ~1, VL = (r + 63) & ~63;
   const size_t B = (size_t)h->batch;
-  const long long m64G = (long long)((n16 + RR2_NB - 1) / RR2_NB) * RR2_NB * RR2_NB;
+  const long long m64G = rr2_m64(n16);
   const int nA = kq.convex ? h->nA3 : r, n0 = nA & ~63;
   const int ldw = ((r - n0) + 63) & ~63;
   const Rr3Lds LD = Rr3Lds::make(r);
@@ -918,19 +995,9 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     // H (H' beta) with exact products (the Hankel kernels of the NOMINAL pipeline: they read slot R3_X of the vectors)
     Rr2Solve H{};
     H.V = S.V; H.vstride = S.vstride; H.VL = VL; H.ZP = S.ZP; H.fdiv = 1; H.r = r;
-    int hk_ng = 0;
-    size_t hk_lds = 0;
-    if (kq.nch <= 16) {
-      for (int ng = RR2_NG; ng >= 1 && hk_ng == 0; --ng) {
-        const Rr2HankelGeom G = rr2_hankel_geom(kq.c, kq.Ln, kq.nch, ng);
-        const size_t bytes = rr2_hankel_mfma_lds(G, kq.Ln) * sizeof(double);
-        if ((G.cg >= 64 || ng == 1) && bytes <= 80 * 1024 && G.ntA <= 8 && G.ntZ <= 8) { hk_ng = ng; hk_lds = bytes; }
-      }
-      if (hk_ng && hk_lds > 64 * 1024)
-        HIP_TRY(raise_lds_limit((const void*)rr2_hankel_mfma_kernel, hk_lds));
-    }
-    if (hk_ng) hipLaunchKernelGGL(rr2_hankel_mfma_kernel, dim3((unsigned)RR2_NG, (unsigned)B), dim3(512), hk_lds, h->stream, H, kq, h->ud, h->yd, (int)R3_X, 0, hk_ng);
-    else hipLaunchKernelGGL(rr2_hankel_kernel, dim3(RR2_NG, (unsigned)B), dim3(512), 0, h->stream, H, kq, h->ud, h->yd, (int)R3_X, 0);
+    HankelLaunch hk;
+    if ((rc = pick_hankel_launch(kq, &hk))) return rc;
+    launch_hankel(hk, h->stream, (unsigned)B, H, kq, h->ud, h->yd, (int)R3_X, 0);
     hipLaunchKernelGGL(rr3_solve_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), lds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
                        (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0);
   }
@@ -938,10 +1005,7 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
   {
     // instances the phase solve marked 5 (more switched components than W holds, a failed pivot of the k x k system): the
     // one-workgroup kernel of rounds 1-4 solves them from scratch in a workspace of its own; every other workgroup leaves at once
-    const size_t rr = (size_t)r, npk = pk_size(rr), rvv = (rr + 1) & ~(size_t)1;
-    const size_t nB = kq.convex ? (size_t)h->prm.p * h->prm.L : 0;
-    const size_t nlag = (size_t)kq.Ln * kq.nch * kq.nch, sb = 2 * pk_size(nB);
-    const size_t stride = (npk + (nlag > sb ? nlag : sb) + 15) & ~(size_t)15;
+    const size_t rr = (size_t)r, rvv = (rr + 1) & ~(size_t)1, stride = large_robust_stride(kq, h->prm);
     const size_t nfb = B < 8 ? B : 8;                       // (one slice of workspace per workgroup of the fall-back grid)
     if ((rc = h->d_rr_fb.ensure(nfb * stride * sizeof(double))) || (rc = h->d_rrmeta_fb.ensure(nfb * sizeof(int)))) return rc;
     const size_t flds = 6 * rvv * sizeof(double) + 4 * rvv * sizeof(int) + (size_t)PSD_PAN * sizeof(double);
@@ -964,72 +1028,61 @@ static int long_data_residual_check(ddmpc_handle* h, const KParams& kq, int* fla
   if ((rc = h->d_rr2zp.ensure((size_t)h->batch * (size_t)RR2_NG * VL * sizeof(double)))) return rc;
   Rr2Solve H{};
   H.V = const_cast<double*>(beta); H.vstride = kq.rE; H.VL = VL; H.ZP = (double*)h->d_rr2zp.p; H.fdiv = 1; H.r = r;
-  int hk_ng = 0;
-  size_t hk_lds = 0;
-  if (kq.nch <= 16) {
-    for (int ng = RR2_NG; ng >= 1 && hk_ng == 0; --ng) {
-      const Rr2HankelGeom G = rr2_hankel_geom(kq.c, kq.Ln, kq.nch, ng);
-      const size_t bytes = rr2_hankel_mfma_lds(G, kq.Ln) * sizeof(double);
-      if ((G.cg >= 64 || ng == 1) && bytes <= 80 * 1024 && G.ntA <= 8 && G.ntZ <= 8) { hk_ng = ng; hk_lds = bytes; }
-    }
-    if (hk_ng && hk_lds > 64 * 1024)
-      HIP_TRY(raise_lds_limit((const void*)rr2_hankel_mfma_kernel, hk_lds));
-  }
-  if (hk_ng) hipLaunchKernelGGL(rr2_hankel_mfma_kernel, dim3((unsigned)RR2_NG, (unsigned)nb), dim3(512), hk_lds, h->stream, H, kq, ud, yd, 0, 0, hk_ng);
-  else hipLaunchKernelGGL(rr2_hankel_kernel, dim3(RR2_NG, (unsigned)nb), dim3(512), 0, h->stream, H, kq, ud, yd, 0, 0);
+  HankelLaunch hk;
+  if ((rc = pick_hankel_launch(kq, &hk))) return rc;
+  launch_hankel(hk, h->stream, (unsigned)nb, H, kq, ud, yd, 0, 0);
   hipLaunchKernelGGL(ddmpc_flag_inaccurate_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, kq, 16 * h->kc.NT, kq.epoch, flags, up, yp, beta, act,
                      (const double*)h->d_rr2zp.p, (int)RR2_NG, VL, status);
   HIP_TRY(hipGetLastError());
   return DDMPC_OK;
 }
 
+// ROBUST controllers beyond the register-resident kernels (Route::RobustPhases, Route::RobustOneWg).
+static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const double* up, const double* yp, double* uo,
+                               double* cost, int32_t* status, int32_t* iters) {
+  int rc;
+  h->beta_stale = h->rescue_ran = h->ws_stale = false;
+  if (route == Route::RobustPhases) {
+    // lock-step factorisation of the whole batch, then one workgroup per instance that streams the factor twice and runs the
+    // active-set iterations on its trailing block
+    if (stage != Stage::OnFactors && (rc = launch_rr3_factors(h))) return rc;
+    if (stage != Stage::Factors && (rc = launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters))) return rc;
+    return DDMPC_OK;
+  }
+  // the one-workgroup kernel: matrices in a per-instance slice of a global workspace
+  const size_t r = (size_t)h->kp.r, rv = (r + 1) & ~(size_t)1, stride = large_robust_stride(h->kp, h->prm);
+  if ((rc = h->d_rr.ensure((size_t)h->batch * stride * sizeof(double))) ||
+      (rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure((size_t)h->batch * h->kp.rE)))
+    return rc;
+  const size_t lds = 6 * rv * sizeof(double) + 4 * rv * sizeof(int) + (size_t)PSD_PAN * sizeof(double);
+  if (lds + 1024 > 160 * 1024) return fail(DDMPC_ERR_UNSUPPORTED, "problem too large: %zu rows", r);
+  if ((rc = h->d_rrmeta.ensure((size_t)h->batch * sizeof(int)))) return rc;
+  auto launch = [&](auto fn) -> int {
+    if (lds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)fn, lds));
+    hipLaunchKernelGGL(fn, dim3((unsigned)h->batch), dim3(large_threads(r)), lds, h->stream, h->kp, 16 * h->kc.NT, h->ud, h->yd,
+                       up, yp, uo, cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p,
+                       (double*)h->d_rr.p, (long long)stride, (int*)h->d_rrmeta.p, 0, (long long)h->batch);
+    return DDMPC_OK;
+  };
+  auto staged = [&](auto k0, auto k1, auto k2) { return stage == Stage::Factors ? launch(k1) : stage == Stage::OnFactors ? launch(k2) : launch(k0); };
+  if (r > 1024)                  // 1025 .. 2048 rows: the 1024-thread instance
+    rc = staged(ddmpc_large_solve_wide_kernel<0>, ddmpc_large_solve_wide_kernel<1>, ddmpc_large_solve_wide_kernel<2>);
+  else
+    rc = staged(ddmpc_large_solve_kernel<0>, ddmpc_large_solve_kernel<1>, ddmpc_large_solve_kernel<2>);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
+// The register-resident cold kernels (Route::Cold).  want_ws: also write the beta / active-set workspace (what
+// ddmpc_get_solution, the gain kernel and the slack-box warm step read).  A plain cold solve skips it (1.2 KB of HBM writes per
+// instance) and ddmpc_get_solution re-solves on demand.
 static int launch_cold(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost,
                        int32_t* status, int32_t* iters, double* lfac = nullptr, const int* only = nullptr,
-                       const KParams* kp_override = nullptr, bool want_ws = true, double* lfacT = nullptr, int large_mode = 0) {
+                       const KParams* kp_override = nullptr, bool want_ws = true, double* lfacT = nullptr) {
   int rc;
-  h->beta_stale = false;
-  h->rescue_ran = false;
-  h->ws_stale = !want_ws && !h->large;
-  if (h->large_nominal) {          // no cold kernel at this size: every instance goes to the rank-revealing kernel
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)status, 4, (size_t)h->batch, h->stream));
-    return DDMPC_OK;
-  }
-  if (h->large && h->large_pipeline == DDMPC_PIPELINE_PHASES && h->batch <= 65535 && !h->stamps_on && h->kp.r <= 1024) {
-    // ... on the phase kernels (ddmpc_rr3.hpp; up to 1024 rows: 64-bit chunk masks): lock-step factorisation of the whole batch, then one workgroup per instance
-    // that streams the factor twice and runs the active-set iterations on its trailing block
-    if (large_mode != 2 && (rc = launch_rr3_factors(h))) return rc;
-    if (large_mode != 1 && (rc = launch_rr3_solve(h, kp_override ? *kp_override : h->kp, up, yp, uo, cost, status, iters))) return rc;
-    return DDMPC_OK;
-  }
-  if (h->large) {                  // robust scheme beyond the register-resident kernels: matrices in a global workspace
-    const size_t r = (size_t)h->kp.r, npk = pk_size(r), rv = (r + 1) & ~(size_t)1;      // (packed rows on 128-byte boundaries)
-    const size_t nB = h->kp.convex ? (size_t)h->prm.p * h->prm.L : 0;      // components the slack box acts on
-    const size_t nlag = (size_t)h->kp.Ln * h->kp.nch * h->kp.nch, sb = 2 * pk_size(nB);
-    const size_t stride = (npk + (nlag > sb ? nlag : sb) + 15) & ~(size_t)15;      // every instance's slice on a 128-byte boundary
-    if ((rc = h->d_rr.ensure((size_t)h->batch * stride * sizeof(double)))) return rc;
-    if ((rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double)))) return rc;
-    if ((rc = h->d_act.ensure((size_t)h->batch * h->kp.rE))) return rc;
-    const size_t lds = 6 * rv * sizeof(double) + 4 * rv * sizeof(int) + (size_t)PSD_PAN * sizeof(double);
-    if (lds + 1024 > 160 * 1024) return fail(DDMPC_ERR_UNSUPPORTED, "problem too large: %zu rows", r);
-    if ((rc = h->d_rrmeta.ensure((size_t)h->batch * sizeof(int)))) return rc;
-    auto launch = [&](auto fn) -> int {
-      if (lds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)fn, lds));
-      hipLaunchKernelGGL(fn, dim3((unsigned)h->batch), dim3(large_threads(r)), lds, h->stream,
-                         kp_override ? *kp_override : h->kp, 16 * h->kc.NT, h->ud, h->yd, up, yp, uo, cost, (int*)status,
-                         (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, (double*)h->d_rr.p, (long long)stride,
-                         (int*)h->d_rrmeta.p, 0, (long long)h->batch);
-      return DDMPC_OK;
-    };
-    if (r > 1024)                  // 1025 .. 2048 rows: the 1024-thread instance
-      rc = large_mode == 1 ? launch(ddmpc_large_solve_wide_kernel<1>) : large_mode == 2 ? launch(ddmpc_large_solve_wide_kernel<2>)
-                                                                                       : launch(ddmpc_large_solve_wide_kernel<0>);
-    else
-      rc = large_mode == 1 ? launch(ddmpc_large_solve_kernel<1>) : large_mode == 2 ? launch(ddmpc_large_solve_kernel<2>)
-                                                                                   : launch(ddmpc_large_solve_kernel<0>);
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return DDMPC_OK;
-  }
+  h->beta_stale = h->rescue_ran = false;
+  h->ws_stale = !want_ws;
   if (h->long_data) { want_ws = true; h->ws_stale = false; }       // (the streamed residual check reads beta and the active set)
   if (want_ws) {
     if ((rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double)))) return rc;
@@ -1059,9 +1112,7 @@ static int launch_cold(ddmpc_handle* h, const double* up, const double* yp, doub
                        (int*)iters, bws, aws, stp, lfac, lfacT, (int*)nullptr, only, 0LL, (int*)nullptr);
   } else if (mode == DDMPC_REFINE_AUTO) {
     // flags [batch] + one counter word behind them (the largest stamp that flagged anything)
-    const bool fresh = h->d_rflag.bytes < ((size_t)h->batch + 1) * sizeof(int);
-    if ((rc = h->d_rflag.ensure(((size_t)h->batch + 1) * sizeof(int)))) return rc;
-    if (fresh) HIP_TRY(hipMemsetAsync(h->d_rflag.p, 0, ((size_t)h->batch + 1) * sizeof(int), h->stream));
+    if ((rc = ensure_rflag(h))) return rc;
     int* rcount = (int*)h->d_rflag.p + h->batch;
     if (only) HIP_TRY(hipMemsetAsync(h->d_rflag.p, 0, (size_t)h->batch * sizeof(int), h->stream));   // filtered-out instances: no flag
     kq.epoch = next_refine_epoch(h);
@@ -1082,9 +1133,7 @@ static int launch_cold(ddmpc_handle* h, const double* up, const double* yp, doub
     // (their columns of the affine law are then formed from refining solves, see ddmpc_prepare)
     int *rf = nullptr, *rcount = nullptr;
     if (lfac != nullptr && kq.lam != 0.0 && kq.refine == DDMPC_REFINE_AUTO && only == nullptr) {
-      const bool fresh = h->d_rflag.bytes < ((size_t)h->batch + 1) * sizeof(int);
-      if ((rc = h->d_rflag.ensure(((size_t)h->batch + 1) * sizeof(int)))) return rc;
-      if (fresh) HIP_TRY(hipMemsetAsync(h->d_rflag.p, 0, ((size_t)h->batch + 1) * sizeof(int), h->stream));
+      if ((rc = ensure_rflag(h))) return rc;
       rf = (int*)h->d_rflag.p; rcount = rf + h->batch;
       kq.epoch = h->prep_epoch = next_refine_epoch(h);
       h->flag_epoch = kq.epoch;
@@ -1104,7 +1153,7 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
   if ((rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double)))) return rc;
   if ((rc = h->d_act.ensure((size_t)h->batch * h->kp.rE))) return rc;
   const int nf = h->prm.n * h->kp.nch;
-  const unsigned threads = (unsigned)(((h->kp.r + 63) / 64) * 64 > 1024 ? 1024 : ((h->kp.r + 63) / 64) * 64);
+  const unsigned threads = warm_threads(h->kp.r);
   if (convex_warm_on(h)) {
     // DDMPC_OPT_CONVEX_WARM_LAW: the whole active-set iteration on the law and M; only instances whose law came from refining
     // solves and leaves the box go to the filtered cold launch (none unless ddmpc_prepare refined some)
@@ -1145,15 +1194,16 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
 }
 
 // Nominal scheme: instances whose Gram matrix is singular (exact data) are re-solved by the rank-revealing
-// kernel; it only touches instances the fast path marked SOLVER_ERROR.
-// rr_mode (problems whose matrices live in the global workspace only): 0 whole solve, 1 the data-dependent factors alone
-// (ddmpc_prepare), 2 a solve on the factors already in the workspace (ddmpc_step) -- see ddmpc_nominal_rr_kernel.
+// kernel; it only touches instances the fast path marked SOLVER_ERROR.  Beyond the register-resident kernels (the NOMINAL
+// routes) every instance is marked and this is the whole solve.
+// stage (problems whose matrices live in the global workspace only): see Stage and ddmpc_nominal_rr_kernel.
 static int launch_rr2_factors(ddmpc_handle* h, double* scratch, long long ndbl, double rank_tol);
 static int launch_rr2_solve(ddmpc_handle* h, double* scratch, long long ndbl, const double* up, const double* yp, double* uo,
                             double* cost, int32_t* status, int32_t* iters, double feas_tol);
-static int launch_nominal_rescue(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost,
-                                 int32_t* status, int32_t* iters, int rr_mode = 0) {
-  if (h->prm.controller_type != DDMPC_NOMINAL || (h->prm.weight_kind == DDMPC_WEIGHT_DENSE && !h->large_nominal)) return DDMPC_OK;
+static int launch_nominal_rescue(ddmpc_handle* h, Route route, const double* up, const double* yp, double* uo, double* cost,
+                                 int32_t* status, int32_t* iters, Stage stage = Stage::Solve) {
+  if (h->prm.controller_type != DDMPC_NOMINAL || (h->prm.weight_kind == DDMPC_WEIGHT_DENSE && route == Route::Cold)) return DDMPC_OK;
+  if (route != Route::Cold) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)status, 4, (size_t)h->batch, h->stream));   // (all SOLVER_ERROR)
   const size_t r = (size_t)h->kp.r, nR = (size_t)h->n_free;
   size_t ndbl = pk_size(r) + pk_size(nR);                         // packed rows on 128-byte boundaries (ddmpc_workspace_kernels.hpp)
   const size_t rv = (r + 1) & ~(size_t)1;
@@ -1162,14 +1212,14 @@ static int launch_nominal_rescue(ddmpc_handle* h, const double* up, const double
   size_t lds = vec_bytes + ndbl * sizeof(double);
   double* scratch = nullptr;
   if (lds + 1024 > 160 * 1024) {                              // matrices too big for LDS: per-instance slices of a global workspace
-    ndbl = pk_size((r + 15) & ~(size_t)15) + pk_size((nR + 15) & ~(size_t)15);   // (whole 16-row tiles: the phase kernels of ddmpc_rr2.hpp)
+    ndbl = (size_t)rr2_ndbl(h);                               // (whole 16-row tiles: the phase kernels of ddmpc_rr2.hpp)
     int rc = h->d_rr.ensure((size_t)h->batch * ndbl * sizeof(double));
     if (rc) return rc;
     scratch = (double*)h->d_rr.p;
     lds = vec_bytes;
     if ((rc = h->d_rrmeta.ensure((size_t)h->batch * (2 * rv + 2) * sizeof(int)))) return rc;
   }
-  if (!scratch) rr_mode = 0;
+  if (!scratch) stage = Stage::Solve;
   if (lds + 1024 > 160 * 1024) return fail(DDMPC_ERR_UNSUPPORTED, "problem too large: %zu rows", r);
   {   // per instance: the r-vector w of the refinement passes
     int rca = h->d_alpha.ensure((size_t)h->batch * (size_t)h->kp.r * sizeof(double));
@@ -1180,9 +1230,9 @@ static int launch_nominal_rescue(ddmpc_handle* h, const double* up, const double
     if (!rcz) rcz = h->d_resc.ensure((size_t)h->batch * sizeof(int));
     if (!rcz) rcz = h->d_xws.ensure((size_t)h->batch * h->kp.rE * sizeof(double));
     if (rcz) return rcz;
-    // (a factors-only launch, rr_mode 1, writes neither z_ws, x_ws nor the flags: what the previous solve left there stays
-    //  readable by ddmpc_get_solution, so the flags must not be cleared -- ddmpc_solve -> ddmpc_prepare -> ddmpc_get_solution)
-    if (rr_mode != 1 || !h->rescue_ran)
+    // (a factors-only launch writes neither z_ws, x_ws nor the flags: what the previous solve left there stays readable by
+    //  ddmpc_get_solution, so the flags must not be cleared -- ddmpc_solve -> ddmpc_prepare -> ddmpc_get_solution)
+    if (stage != Stage::Factors || !h->rescue_ran)
       HIP_TRY(hipMemsetAsync(h->d_resc.p, 0, (size_t)h->batch * sizeof(int), h->stream));
   }
   // rank tolerance 1e-8 (relative to the largest diagonal entry of the Gram): with the fixed-first ordering the
@@ -1203,17 +1253,16 @@ static int launch_nominal_rescue(ddmpc_handle* h, const double* up, const double
   int rcl = DDMPC_OK;
   if (!scratch) rcl = launch(ddmpc_nominal_rr_kernel<0>);                 // matrices in LDS: one launch
   else {                                                                  // global workspace: factors, then the solve on them
-    // (the phase kernels address 16-column chunks with 64-bit masks: 1024 rows; beyond that the 1024-thread instance of the
-    //  one-workgroup kernel)
+    // (the one-workgroup kernel beyond 1024 rows: its 1024-thread instance)
     const bool wide = r > 1024;
-    const bool phases = h->large_pipeline == DDMPC_PIPELINE_PHASES && h->large_nominal && h->batch <= 65535 && !h->stamps_on && !wide;
+    const bool phases = route == Route::NominalPhases;
     const bool wdense = h->prm.weight_kind == DDMPC_WEIGHT_DENSE;
     if (wdense && !phases)
       return fail(DDMPC_ERR_UNSUPPORTED, "dense weighting matrices of a NOMINAL controller beyond 271 rows run on the phase kernels only "
                   "(batches up to 65535, no diagnostic stamps)");
-    if (rr_mode != 2) rcl = phases ? launch_rr2_factors(h, scratch, (long long)ndbl, 1e-8)
-                                   : (wide ? launch(ddmpc_nominal_rr_wide_kernel<1>) : launch(ddmpc_nominal_rr_kernel<1>));
-    if (!rcl && rr_mode != 1) {
+    if (stage != Stage::OnFactors) rcl = phases ? launch_rr2_factors(h, scratch, (long long)ndbl, 1e-8)
+                                                : (wide ? launch(ddmpc_nominal_rr_wide_kernel<1>) : launch(ddmpc_nominal_rr_kernel<1>));
+    if (!rcl && stage != Stage::Factors) {
       h->rr2_x_pending = false;
       rcl = phases ? launch_rr2_solve(h, scratch, (long long)ndbl, up, yp, uo, cost, status, iters, 1e-7)
                    : (wide ? launch(ddmpc_nominal_rr_wide_kernel<2>) : launch(ddmpc_nominal_rr_kernel<2>));
@@ -1221,7 +1270,7 @@ static int launch_nominal_rescue(ddmpc_handle* h, const double* up, const double
     }
   }
   if (rcl) return rcl;
-  if (rr_mode != 1) h->rescue_ran = true;
+  if (stage != Stage::Factors) h->rescue_ran = true;
   return DDMPC_OK;
 }
 
@@ -1234,8 +1283,7 @@ static int launch_rr2_factors(ddmpc_handle* h, double* scratch, long long ndbl, 
   const int rv = (r + 1) & ~1;
   const long long mstride = 2 * (long long)rv + 2;
   const size_t B = (size_t)h->batch;
-  const long long m64G = (long long)((n16 + RR2_NB - 1) / RR2_NB) * RR2_NB * RR2_NB;       // Minv blocks of G's factor per instance
-  const long long m64T = (long long)((nR16 + RR2_NB - 1) / RR2_NB) * RR2_NB * RR2_NB;      // ... and of T's factor, behind them
+  const long long m64G = rr2_m64(n16), m64T = rr2_m64(nR16);       // Minv blocks of G's factor per instance, T's behind them
   int rc;
   const long long rstride = (long long)n16 + 2;              // per instance: two words of retired-tile bits, then the residual diagonal
   if ((rc = h->d_rr2d.ensure(B * 4 * sizeof(unsigned long long))) || (rc = h->d_rr2mt.ensure(B * (size_t)(m64G + m64T) * sizeof(double))) ||
@@ -1250,17 +1298,6 @@ static int launch_rr2_factors(ddmpc_handle* h, double* scratch, long long ndbl, 
     launch_rr2_gram(h->stream, k, h->ud, h->yd, iperm, scratch, ndbl, n16, dd, B);
   };
   gram();
-  auto cholesky = [&](const Rr2Chol& F, int nmax16) {
-    const int nt = nmax16 >> 4;
-    for (int c0 = 0; c0 < nmax16; c0 += RR2_NB) {
-      const int tp = c0 >> 4;
-      hipLaunchKernelGGL(rr2_chol_panel_kernel, dim3(1, (unsigned)B), dim3(256), 0, h->stream, F, c0);
-      const int nbelow = nt - tp - 4;                       // row tiles below the diagonal block
-      if (nbelow > 0)
-        hipLaunchKernelGGL(rr2_chol_update_kernel<RR2_UT>, dim3((unsigned)((nbelow + 4 * RR2_UT - 1) / (4 * RR2_UT)), (unsigned)B),
-                           dim3(256), 0, h->stream, F, c0);
-    }
-  };
   Rr2Chol FG{};
   FG.ws = scratch; FG.stride = ndbl; FG.off = 0; FG.n16 = n16; FG.n_inst = nullptr; FG.n_stride = 0;
   FG.dmax = dd + 0; FG.d_stride = 4; FG.tol_rel = rank_tol; FG.skip = meta; FG.s_stride = mstride; FG.nflag = r;
@@ -1268,7 +1305,7 @@ static int launch_rr2_factors(ddmpc_handle* h, double* scratch, long long ndbl, 
   FG.res = (double*)h->d_rr2res.p + 2; FG.res_stride = rstride; FG.dead = (unsigned long long*)h->d_rr2res.p; FG.dead_stride = rstride;
   if ((rc = h->d_rr2cand.ensure(B * (size_t)n16 * sizeof(double)))) return rc;
   FG.cand = (double*)h->d_rr2cand.p; FG.cand_stride = n16;
-  cholesky(FG, n16);
+  launch_rr2_cholesky(h->stream, FG, n16, B);
   // what follows the factor of G: pivot counts, T = C'WC, its factor
   auto downstream = [&]() -> int {
     hipLaunchKernelGGL(rr2_meta_kernel, dim3((unsigned)B), dim3(256), 0, h->stream, meta, mstride, rv, r, nF, nR);
@@ -1296,7 +1333,7 @@ static int launch_rr2_factors(ddmpc_handle* h, double* scratch, long long ndbl, 
       if (nR16 <= 384)            // a few panels: one launch, one workgroup per instance walks them (rr2_chol_small_kernel)
         hipLaunchKernelGGL(rr2_chol_small_kernel<2>, dim3((unsigned)B), dim3(256), 0, h->stream, FT);
       else
-        cholesky(FT, nR16);
+        launch_rr2_cholesky(h->stream, FT, nR16, B);
     }
     HIP_TRY(hipGetLastError());
     return DDMPC_OK;
@@ -1331,7 +1368,7 @@ static int launch_rr2_factors(ddmpc_handle* h, double* scratch, long long ndbl, 
       HIP_TRY(hipMemset2DAsync(h->d_rr2res.p, (size_t)rstride * sizeof(double), 0, 2 * sizeof(unsigned long long), B, h->stream));
       gram();
       FG.tol_inst = (const double*)h->d_rr2tol.p;
-      cholesky(FG, n16);
+      launch_rr2_cholesky(h->stream, FG, n16, B);
       hipLaunchKernelGGL(rr2_rank_margin_kernel, dim3((unsigned)B), dim3(256), 0, h->stream, (const double*)h->d_rr2cand.p, (long long)n16, r, bound,
                          rank_tol, (const double*)h->d_rr2tol.p, safe, 0, (double*)h->d_rr2tol.p, rec, rec + 2 * B, (double*)h->d_rr2tol.p + B);
       if ((rc = downstream())) return rc;
@@ -1347,8 +1384,7 @@ static int rr2_solve_desc(ddmpc_handle* h, double* scratch, long long ndbl, Rr2S
   const int r = k.r, n16 = (r + 15) & ~15, nR = h->n_free, nF = h->nF, nR16 = (nR + 15) & ~15;
   const int rv = (r + 1) & ~1, VL = (r + 63) & ~63;
   const size_t B = vbatch ? vbatch : (size_t)h->batch;           // (the gain build runs the solve on a virtual batch)
-  const long long m64G = (long long)((n16 + RR2_NB - 1) / RR2_NB) * RR2_NB * RR2_NB;
-  const long long m64T = (long long)((nR16 + RR2_NB - 1) / RR2_NB) * RR2_NB * RR2_NB;
+  const long long m64G = rr2_m64(n16), m64T = rr2_m64(nR16);
   int rc;
   if ((rc = h->d_rr2v.ensure(B * (size_t)V_NV * VL * sizeof(double))) || (rc = h->d_rr2zp.ensure(B * (size_t)RR2_NG * VL * sizeof(double))) ||
       (rc = h->d_rr2sc.ensure(B * (4 * sizeof(double) + 2 * sizeof(int) + sizeof(unsigned long long)))))
@@ -1380,25 +1416,10 @@ static int rr2_solve_sequence(ddmpc_handle* h, const Rr2Solve& S, unsigned B, co
   const int RPs = 16 * h->kc.NT, nF = S.nF, nR = S.nR;
   auto grp = [](int n, int per) { return (unsigned)((n + per - 1) / per < 1 ? 1 : (n + per - 1) / per); };
   hipStream_t st = h->stream;
-  // H (H' x): on the matrix pipe when the shape allows it (up to 16 channels, at most 8 tiles per half, LDS within reach)
-  int hk_ng = 0;
-  size_t hk_lds = 0;
-  if (k.nch <= 16) {
-    for (int ng = RR2_NG; ng >= 1 && hk_ng == 0; --ng) {                     // as many workgroups per instance as leave >= 64 columns each
-      const Rr2HankelGeom G = rr2_hankel_geom(k.c, k.Ln, k.nch, ng);
-      const size_t bytes = rr2_hankel_mfma_lds(G, k.Ln) * sizeof(double);
-      if ((G.cg >= 64 || ng == 1) && bytes <= 80 * 1024 && G.ntA <= 8 && G.ntZ <= 8) { hk_ng = ng; hk_lds = bytes; }
-    }
-    if (hk_ng && hk_lds > 64 * 1024)
-      HIP_TRY(raise_lds_limit((const void*)rr2_hankel_mfma_kernel, hk_lds));
-  }
-  auto hankel = [&](int slot, int pass) {
-    // (RR2_NG workgroups per instance whatever hk_ng is: the consumers sum RR2_NG partial results, and a workgroup past the
-    //  last column group writes the zeros they expect -- launched with hk_ng < RR2_NG workgroups, short trajectories summed
-    //  whatever the allocator had left in the other slots)
-    if (hk_ng) hipLaunchKernelGGL(rr2_hankel_mfma_kernel, dim3((unsigned)RR2_NG, B), dim3(512), hk_lds, st, S, k, h->ud, h->yd, slot, pass, hk_ng);
-    else hipLaunchKernelGGL(rr2_hankel_kernel, dim3(RR2_NG, B), dim3(512), 0, st, S, k, h->ud, h->yd, slot, pass);
-  };
+  HankelLaunch hk;                                                        // H (H' x)
+  const int rc = pick_hankel_launch(k, &hk);
+  if (rc) return rc;
+  auto hankel = [&](int slot, int pass) { launch_hankel(hk, st, B, S, k, h->ud, h->yd, slot, pass); };
   hipLaunchKernelGGL(rr2_s1_kernel, dim3(B), dim3(RR2_TS), 0, st, S, k, RPs, up, yp);
   hipLaunchKernelGGL(rr2_rows_kernel<0>, dim3(grp(nF + nR, 32), B), dim3(256), 0, st, S, k, RPs, (double*)nullptr, (double*)nullptr, 0);
   if (S.wd) hipLaunchKernelGGL(rr2_wapply_kernel<0>, dim3(B), dim3(RR2_TS), 0, st, S, 0);
@@ -1481,18 +1502,10 @@ static int launch_rr2_gain_build(ddmpc_handle* h, double* scratch, long long ndb
   return DDMPC_OK;
 }
 
-typedef int (*launch_fn)(ddmpc_handle*, const double*, const double*, double*, double*, int32_t*, int32_t*);
-// ROBUST controller beyond the register-resident kernels, warm: a solve on what ddmpc_prepare left in the workspace
-static int launch_large_robust_warm(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost,
-                                    int32_t* status, int32_t* iters) {
-  return launch_cold(h, up, yp, uo, cost, status, iters, nullptr, nullptr, nullptr, true, nullptr, 2);
-}
 // NOMINAL controller beyond the register-resident kernels, warm: a solve on the factors ddmpc_prepare left in the workspace
-static int launch_large_nominal_warm(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost,
+static int launch_large_nominal_warm(ddmpc_handle* h, Route route, const double* up, const double* yp, double* uo, double* cost,
                                      int32_t* status, int32_t* iters) {
-  h->beta_stale = false;
-  h->ws_stale = false;
-  h->gain_step_last = false;
+  h->beta_stale = h->ws_stale = h->gain_step_last = false;
   if (h->large_gain_ready && h->large_affine) {                        // the affine law of ddmpc_prepare: one HBM-bound launch
     const KParams& k = h->kp;
     const int nf = h->prm.n * k.nch, nFp = (h->nF + 63) & ~63;
@@ -1508,20 +1521,34 @@ static int launch_large_nominal_warm(ddmpc_handle* h, const double* up, const do
     h->gain_step_last = true;
     return DDMPC_OK;
   }
-  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)status, 4, (size_t)h->batch, h->stream));
-  return launch_nominal_rescue(h, up, yp, uo, cost, status, iters, 2);
-}
-static int launch_cold_plain(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost,
-                             int32_t* status, int32_t* iters) {
-  int rc = launch_cold(h, up, yp, uo, cost, status, iters, nullptr, nullptr, nullptr, /*want_ws=*/false);
-  return rc ? rc : launch_nominal_rescue(h, up, yp, uo, cost, status, iters);
+  return launch_nominal_rescue(h, route, up, yp, uo, cost, status, iters, Stage::OnFactors);
 }
 
-static int launch_warm_plain(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost,
-                             int32_t* status, int32_t* iters) {
-  int rc = launch_warm(h, up, yp, uo, cost, status, iters);
-  return rc ? rc : launch_nominal_rescue(h, up, yp, uo, cost, status, iters);
+// A cold solve of the whole batch on the handle's route (ddmpc_solve, the cold closed loop).
+static int solve_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
+                          int32_t* iters) {
+  const Route route = h->solve_route = select_route(h);
+  if (route != h->prep_route) h->prepared = false;              // (its workspace is the one ddmpc_prepare kept things in)
+  if (route == Route::RobustPhases || route == Route::RobustOneWg)
+    return launch_large_robust(h, route, Stage::Solve, up, yp, uo, cost, status, iters);
+  int rc = DDMPC_OK;
+  if (route == Route::Cold) rc = launch_cold(h, up, yp, uo, cost, status, iters, nullptr, nullptr, nullptr, /*want_ws=*/false);
+  else h->beta_stale = h->rescue_ran = h->ws_stale = false;        // (no cold kernel at this size: the rescue is the solve)
+  return rc ? rc : launch_nominal_rescue(h, route, up, yp, uo, cost, status, iters);
 }
+
+// A control step on what ddmpc_prepare kept (ddmpc_step, the per-step closed loop): the callers have prepared on this route.
+static int step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
+                         int32_t* iters) {
+  const Route route = h->solve_route = select_route(h);
+  if (route == Route::RobustPhases || route == Route::RobustOneWg)
+    return launch_large_robust(h, route, Stage::OnFactors, up, yp, uo, cost, status, iters);
+  if (route != Route::Cold) return launch_large_nominal_warm(h, route, up, yp, uo, cost, status, iters);
+  const int rc = launch_warm(h, up, yp, uo, cost, status, iters);
+  return rc ? rc : launch_nominal_rescue(h, route, up, yp, uo, cost, status, iters);
+}
+
+typedef int (*launch_fn)(ddmpc_handle*, const double*, const double*, double*, double*, int32_t*, int32_t*);
 
 static int solve_impl(ddmpc_handle* h, const double* u_past, const double* y_past, double* u_opt, double* cost,
                       int32_t* status, int32_t* iters, int mem, launch_fn launch) {
@@ -1573,7 +1600,7 @@ static int solve_impl(ddmpc_handle* h, const double* u_past, const double* y_pas
 int ddmpc_solve(ddmpc_handle* h, const double* u_past, const double* y_past, double* u_opt, double* cost,
                 int32_t* status, int32_t* iters, int mem) {
   if (h) h->gpre_valid = false;           // (borrowed device data may have changed since the last call)
-  return solve_impl(h, u_past, y_past, u_opt, cost, status, iters, mem, &launch_cold_plain);
+  return solve_impl(h, u_past, y_past, u_opt, cost, status, iters, mem, &solve_on_route);
 }
 
 int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d, const double* u_past,
@@ -1582,7 +1609,7 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
     return fail(DDMPC_ERR_INVALID, "null argument");
   if (h->batch > 0x7fffffffLL) return fail(DDMPC_ERR_INVALID, "batch too large for one launch");
   h->gpre_valid = false;
-  if (h->large) {                         // no chunked cold launches at this size: plain upload + solve
+  if (select_route(h) != Route::Cold) {   // no chunked cold launches beyond the register-resident kernels: plain upload + solve
     int rcs = ddmpc_set_data(h, u_d, y_d, DDMPC_MEM_HOST);
     return rcs ? rcs : ddmpc_solve(h, u_past, y_past, u_opt, cost, status, iters, DDMPC_MEM_HOST);
   }
@@ -1624,10 +1651,8 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
   const bool always = refinable && h->kp.refine == DDMPC_REFINE_ALWAYS;
   int* rflag = nullptr;
   if (refinable && h->kp.refine == DDMPC_REFINE_AUTO) {
-    const bool fresh = h->d_rflag.bytes < (B + 1) * sizeof(int);
-    if ((rc = h->d_rflag.ensure((B + 1) * sizeof(int)))) return rc;
+    if ((rc = ensure_rflag(h))) return rc;
     rflag = (int*)h->d_rflag.p;
-    if (fresh) HIP_TRY(hipMemsetAsync(rflag, 0, (B + 1) * sizeof(int), h->stream));
   }
   double* lbeta = nullptr;                // trajectories beyond the LDS: the chunks write beta / the active set for the streamed residual check
   signed char* lact = nullptr;
@@ -1680,7 +1705,7 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
   }
   if (rcl == DDMPC_OK) {            // NOMINAL on exact data: same rank-revealing rescue as ddmpc_solve (all chunks are uploaded
     h->ud = dud; h->yd = dyd;       // and solved by now in stream order)
-    rcl = launch_nominal_rescue(h, dup, dyp, duo, dco, dst, dit);
+    rcl = launch_nominal_rescue(h, Route::Cold, dup, dyp, duo, dco, dst, dit);
   }
   if (rcl == DDMPC_OK) {
     if (hipMemcpyAsync(u_opt, duo, B * suo * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
@@ -1705,35 +1730,29 @@ int ddmpc_prepare(ddmpc_handle* h) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
   if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_prepare");
   if (h->batch > 0x7fffffffLL) return fail(DDMPC_ERR_INVALID, "batch too large for one launch");
-  if (h->prepared) return DDMPC_OK;
+  if (prep_valid(h)) return DDMPC_OK;
   h->gpre_valid = false;
-  if (h->large_nominal) {
+  const Route route = select_route(h);
+  h->prepared = false;                    // (until the route's preparation below has been queued in full)
+  h->prep_route = route;
+  HIP_TRY(hipSetDevice(h->device));
+  if (nominal_route(route)) {
     // no affine law at this size, but everything that depends on the data alone -- Gram, its rank-revealing factor, the
     // reduced normal matrix and its factor, 70 % of a solve -- is formed once and kept in the workspace; ddmpc_step and
     // the per-step closed loop then only redo the substitutions and the refinement passes
-    HIP_TRY(hipSetDevice(h->device));
     int rc = h->d_prep_status.ensure((size_t)h->batch * sizeof(int32_t));
-    if (rc) return rc;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->d_prep_status.p, 4, (size_t)h->batch, h->stream));
     h->large_gain_ready = false;
-    if ((rc = launch_nominal_rescue(h, h->ud, h->yd, nullptr, nullptr, (int32_t*)h->d_prep_status.p, nullptr, 1))) return rc;
-    if (h->large_affine && h->large_pipeline == DDMPC_PIPELINE_PHASES && h->batch <= 65535 && !h->stamps_on && h->kp.r <= 1024 && h->d_rr.p) {
-      const size_t r_ = (size_t)h->kp.r, nR_ = (size_t)h->n_free;
-      const long long ndbl_ = (long long)(pk_size((r_ + 15) & ~(size_t)15) + pk_size((nR_ + 15) & ~(size_t)15));
-      if ((rc = launch_rr2_gain_build(h, (double*)h->d_rr.p, ndbl_))) return rc;
-    }
-    h->prepared = true;
-    return DDMPC_OK;
+    if (!rc) rc = launch_nominal_rescue(h, route, h->ud, h->yd, nullptr, nullptr, (int32_t*)h->d_prep_status.p, nullptr, Stage::Factors);
+    if (!rc && h->large_affine && route == Route::NominalPhases && h->d_rr.p) rc = launch_rr2_gain_build(h, (double*)h->d_rr.p, rr2_ndbl(h));
+    h->prepared = rc == DDMPC_OK;
+    return rc;
   }
-  if (h->large) {                         // ROBUST at this size: Gram + lam D, the factor of the columns outside the slack box and
+  if (route != Route::Cold) {             // ROBUST at this size: Gram + lam D, the factor of the columns outside the slack box and
                                           // the Schur complement of the boxed block are formed once and kept
-    HIP_TRY(hipSetDevice(h->device));
-    int rc = launch_cold(h, h->ud, h->yd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, nullptr, 1);
-    if (rc) return rc;
-    h->prepared = true;
-    return DDMPC_OK;
+    const int rc = launch_large_robust(h, route, Stage::Factors, h->ud, h->yd, nullptr, nullptr, nullptr, nullptr);
+    h->prepared = rc == DDMPC_OK;
+    return rc;
   }
-  HIP_TRY(hipSetDevice(h->device));
   const ddmpc_params& p = h->prm;
   const KParams& k = h->kp;
   const int nf = p.n * k.nch, nrhs = nf + 1, NT = h->kc.NT;
@@ -1875,28 +1894,22 @@ int ddmpc_step(ddmpc_handle* h, const double* u_past, const double* y_past, doub
                int32_t* status, int32_t* iters, int mem) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
   if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_step");
-  if (!h->prepared) {
+  if (!prep_valid(h)) {
     int rc = ddmpc_prepare(h);
     if (rc) return rc;
   }
-  return solve_impl(h, u_past, y_past, u_opt, cost, status, iters, mem,
-                    h->large_nominal ? &launch_large_nominal_warm : h->large ? &launch_large_robust_warm : &launch_warm_plain);
+  return solve_impl(h, u_past, y_past, u_opt, cost, status, iters, mem, &step_on_route);
 }
 
 int ddmpc_get_gain(ddmpc_handle* h, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
   if (h->large && !(h->large_nominal && h->large_affine))
     return fail(DDMPC_ERR_UNSUPPORTED, "no affine law at this problem size (NOMINAL controllers: DDMPC_OPT_LARGE_AFFINE_LAW)");
-  if (!h->prepared || (h->large && !h->large_gain_ready)) return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare must be called before ddmpc_get_gain");
+  if (!prep_valid(h) || (h->large && !h->large_gain_ready)) return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare must be called before ddmpc_get_gain");
   HIP_TRY(hipSetDevice(h->device));
-  if (h->large) {            // z = [ubar; ybar] (component order) = gain[:,0] + gain[:,1:]' [u_past; y_past]
-    const size_t bytesz = (size_t)h->batch * (h->prm.n * h->kp.nch + 1) * h->kp.r * sizeof(double);
-    HIP_TRY(hipMemcpyAsync(out, h->d_gz.p, bytesz, mem == DDMPC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return DDMPC_OK;
-  }
+  // (beyond the register-resident kernels: z = [ubar; ybar] (component order) = gain[:,0] + gain[:,1:]' [u_past; y_past])
   const size_t bytes = (size_t)h->batch * (h->prm.n * h->kp.nch + 1) * h->kp.r * sizeof(double);
-  HIP_TRY(hipMemcpyAsync(out, h->d_gain.p, bytes, mem == DDMPC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+  HIP_TRY(hipMemcpyAsync(out, h->large ? h->d_gz.p : h->d_gain.p, bytes, mem == DDMPC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                          h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return DDMPC_OK;
@@ -1976,7 +1989,6 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value == DDMPC_PIPELINE_ONE_WORKGROUP && h->large_nominal && h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
         return fail(DDMPC_ERR_UNSUPPORTED, "dense weighting matrices of a NOMINAL controller beyond 271 rows run on the phase kernels only");
       h->large_pipeline = value;
-      h->prepared = false;
       return DDMPC_OK;
     default: return fail(DDMPC_ERR_INVALID, "unknown option %d", option);
   }
@@ -2001,7 +2013,7 @@ int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
   if (!h->solved) return fail(DDMPC_ERR_NOT_READY, "no solve to read a solution from");
   HIP_TRY(hipSetDevice(h->device));
   const KParams& k = h->kp;
-  if (h->ws_stale && !(h->rescue_ran && h->large_nominal)) {
+  if (h->ws_stale) {
     // last solve = a cold solve that skipped the workspace: solve once more at the same past window, keeping beta / active set
     const size_t B = (size_t)h->batch;
     int rc;
@@ -2021,8 +2033,7 @@ int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
         (rc = h->d_status.ensure(B * sizeof(int32_t))) || (rc = h->d_iters.ensure(B * sizeof(int32_t))) ||
         (rc = h->d_beta.ensure(B * k.rE * sizeof(double))) || (rc = h->d_act.ensure(B * k.rE)))
       return rc;
-    const unsigned threads = (unsigned)(((k.r + 63) / 64) * 64 > 1024 ? 1024 : ((k.r + 63) / 64) * 64);
-    hipLaunchKernelGGL(ddmpc_warm_step_kernel, dim3((unsigned)h->batch), dim3(threads), 0, h->stream, k, 16 * h->kc.NT,
+    hipLaunchKernelGGL(ddmpc_warm_step_kernel, dim3((unsigned)h->batch), dim3(warm_threads(k.r)), 0, h->stream, k, 16 * h->kc.NT,
                        h->prm.n * k.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, h->last_up, h->last_yp,
                        (double*)h->d_uopt.p, (double*)h->d_cost.p, (int*)h->d_status.p, (int*)h->d_iters.p,
                        (double*)h->d_beta.p, (signed char*)h->d_act.p, (int*)nullptr);
@@ -2050,15 +2061,14 @@ int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
   // instances solved by the NOMINAL rescue kernel have no beta: ubar / ybar come from the z it exported, alpha = H' x from
   // the vector x it exported
   if (h->large_nominal && h->gain_step_last && what == DDMPC_SOL_ALPHA) {
-    // the last solve was a step on the affine law, which keeps no w: solve once more on the factors at the same past window
+    // the last solve was a step on the affine law, which keeps no w: solve once more on its route's factors at the same past window
     const size_t B = (size_t)h->batch;
     int rc;
     if ((rc = h->d_uopt.ensure(B * h->prm.L * k.m * sizeof(double))) || (rc = h->d_cost.ensure(B * sizeof(double))) ||
         (rc = h->d_status.ensure(B * sizeof(int32_t))) || (rc = h->d_iters.ensure(B * sizeof(int32_t))))
       return rc;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->d_status.p, 4, B, h->stream));
-    if ((rc = launch_nominal_rescue(h, h->last_up, h->last_yp, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p,
-                                    (int32_t*)h->d_iters.p, 2)))
+    if ((rc = launch_nominal_rescue(h, h->solve_route, h->last_up, h->last_yp, (double*)h->d_uopt.p, (double*)h->d_cost.p,
+                                    (int32_t*)h->d_status.p, (int32_t*)h->d_iters.p, Stage::OnFactors)))
       return rc;
     h->gain_step_last = false;
   }
@@ -2066,10 +2076,8 @@ int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
   if (h->large_nominal && !resc) return fail(DDMPC_ERR_NOT_READY, "no solve to read a solution from");
   if (h->large_nominal && h->rr2_x_pending && what == DDMPC_SOL_ALPHA) {
     // phase-kernel solve: x = L_I^-T w (alpha = H' x) is formed here, on demand, from the final w the solve kept
-    const size_t r_ = (size_t)k.r, nR_ = (size_t)h->n_free;
-    const long long ndbl_ = (long long)(pk_size((r_ + 15) & ~(size_t)15) + pk_size((nR_ + 15) & ~(size_t)15));
     Rr2Solve S;
-    int rcx = rr2_solve_desc(h, (double*)h->d_rr.p, ndbl_, &S);
+    int rcx = rr2_solve_desc(h, (double*)h->d_rr.p, rr2_ndbl(h), &S);
     if (rcx) return rcx;
     hipLaunchKernelGGL(rr2_xws_kernel, dim3((unsigned)h->batch), dim3(RR2_TS), 0, h->stream, S, k, (double*)h->d_xws.p);
     HIP_TRY(hipGetLastError());
@@ -2170,7 +2178,7 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   if (!h || !plant || !x || !u_past || !y_past || !w || !u_sys || !y_sys || !status)
     return fail(DDMPC_ERR_INVALID, "null argument");
   if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_closed_loop");
-  if (!h->prepared) h->gpre_valid = false;      // (borrowed device data may have changed since the last solve; a kept law pins it)
+  if (!prep_valid(h)) h->gpre_valid = false;    // (borrowed device data may have changed since the last solve; a kept law pins it)
   if (n_steps <= 0 || n_mpc_step <= 0) return fail(DDMPC_ERR_INVALID, "n_steps and n_mpc_step must be positive");
   const ddmpc_params& p = h->prm;
   if (n_mpc_step > p.L) return fail(DDMPC_ERR_INVALID, "n_mpc_step must not exceed the prediction horizon L");
@@ -2213,10 +2221,9 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   const bool warm_ok = h->closed_loop_path != DDMPC_PATH_COLD &&
                        (size_t)n_mpc_step * m <= (size_t)WARM_MAX_NF && n * h->kp.nch <= WARM_MAX_NF;
   const bool warm_large = h->large && h->closed_loop_path != DDMPC_PATH_COLD;           // per step, on what ddmpc_prepare kept
-  if (warm_large && (rc = ddmpc_prepare(h))) return rc;
   bool warm = warm_ok && !h->kp.convex && !h->large;   // no inequality: fused loop, one launch
   const bool warm_box = warm_ok && h->kp.convex && !h->large;     // slack box: per step, affine iterate + cold re-solve where a bound is active
-  if (warm_box && (rc = ddmpc_prepare(h))) return rc;
+  if ((warm_large || warm_box) && (rc = ddmpc_prepare(h))) return rc;
   if (warm && p.controller_type == DDMPC_NOMINAL) {
     // nominal scheme: an instance with a singular Gram matrix (exact data) has no affine law; if there is one,
     // run the per-step path, whose solves go through the rank-revealing rescue kernel
@@ -2230,8 +2237,7 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
     // affine control law: the whole loop of an instance runs inside one workgroup
     if ((rc = ddmpc_prepare(h))) return rc;
     if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
-    const unsigned threads = (unsigned)(((h->kp.r + 63) / 64) * 64 > 1024 ? 1024 : ((h->kp.r + 63) / 64) * 64);
-    hipLaunchKernelGGL(ddmpc_closed_loop_warm_kernel, dim3((unsigned)B), dim3(threads), 0, h->stream, h->kp,
+    hipLaunchKernelGGL(ddmpc_closed_loop_warm_kernel, dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
                        16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
                        (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
                        (double*)h->d_beta.p, (signed char*)h->d_act.p);
@@ -2241,8 +2247,7 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   if (warm_box && convex_warm_on(h) && h->cwl_nref == 0) {
     // DDMPC_OPT_CONVEX_WARM_LAW: the whole loop of an instance in one workgroup, active-set iterations included
     if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
-    const unsigned threads = (unsigned)(((h->kp.r + 63) / 64) * 64 > 1024 ? 1024 : ((h->kp.r + 63) / 64) * 64);
-    hipLaunchKernelGGL(ddmpc_closed_loop_convex_warm_kernel, dim3((unsigned)B), dim3(threads), 0, h->stream, h->kp,
+    hipLaunchKernelGGL(ddmpc_closed_loop_convex_warm_kernel, dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
                        16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
                        (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
                        (double*)h->d_beta.p, (signed char*)h->d_act.p, h->cwl_nbox, (const int*)h->d_cwl_tab.p,
@@ -2266,11 +2271,8 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   if (!warm) {
     if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
     if (warm_box && (rc = h->d_need.ensure(B * sizeof(int)))) return rc;
-    if (!h->large) {       // AUTO refinement flags of launch_cold: sized (and cleared once) before a capture starts
-      const bool fresh = h->d_rflag.bytes < (B + 1) * sizeof(int);
-      if ((rc = h->d_rflag.ensure((B + 1) * sizeof(int)))) return rc;
-      if (fresh) HIP_TRY(hipMemsetAsync(h->d_rflag.p, 0, (B + 1) * sizeof(int), h->stream));
-    }
+    // AUTO refinement flags of launch_cold: sized (and cleared once) before a capture starts
+    if (select_route(h) == Route::Cold && (rc = ensure_rflag(h))) return rc;
   }
   if (use_graph && hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
     (void)hipGetLastError();                          // e.g. a caller-provided legacy stream: launch the steps directly
@@ -2278,9 +2280,8 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   }
   auto enqueue_steps = [&]() -> int {
     for (int t = 0; !warm && t < n_steps; t += n_mpc_step) {
-      int rcs = warm_box ? launch_warm(h, dup, dyp, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p, nullptr)
-                : warm_large ? (h->large_nominal ? launch_large_nominal_warm : launch_large_robust_warm)(h, dup, dyp, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p, nullptr)
-                         : launch_cold_plain(h, dup, dyp, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p, nullptr);
+      int rcs = (warm_box || warm_large ? step_on_route : solve_on_route)(h, dup, dyp, (double*)h->d_uopt.p, (double*)h->d_cost.p,
+                                                                          (int32_t*)h->d_status.p, nullptr);
       if (rcs) return rcs;
       const int nsub = (t + n_mpc_step <= n_steps) ? n_mpc_step : n_steps - t;
       hipLaunchKernelGGL(ddmpc_plant_kernel, dim3(pblocks), dim3(128), 0, h->stream, (long long)B, ns, m, pp, n,
@@ -2357,13 +2358,7 @@ int ddmpc_debug_stamps(ddmpc_handle* h, int enable, uint64_t* out) {
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(h->d_stamps.p, 0, bytes, h->stream));
   }
-  if (h->large_nominal && h->stamps_on != (enable != 0)) {
-    // the stamps switch selects the pipeline of NOMINAL controllers beyond 271 rows (phase kernels / one workgroup), and the two
-    // keep different things next to the factors (Minv blocks, live masks): what ddmpc_prepare left is not the other's input
-    h->prepared = false;
-    h->large_gain_ready = false;
-  }
-  h->stamps_on = enable != 0;
+  h->stamps_on = enable != 0;          // (beyond 271 rows this selects the route: select_route, prep_valid)
   return DDMPC_OK;
 }
 
@@ -2376,7 +2371,8 @@ int ddmpc_debug_poison_allocations(int byte) {
 int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws_count, int32_t* meta_out, int64_t meta_count,
                           int64_t* ws_avail, int64_t* meta_avail) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
-  if (h->large && !h->large_nominal && h->d_rr3k.p) {
+  // what the last solve left, read on the route that served it
+  if (h->solve_route == Route::RobustPhases && h->d_rr3k.p) {
     // ROBUST on the phase kernels (ddmpc_rr3.hpp): the per-instance record of the last solve --
     // [k, state, iterations, k, switched positions (RR3_KMAX), active set (rv), start tick, ticks] -- into meta_out
     const int rv = (h->kp.r + 1) & ~1;
@@ -2390,7 +2386,8 @@ int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws
       HIP_TRY(hipMemcpy(meta_out, (const int*)h->d_rr3k.p + b * kstride, (size_t)(meta_count < kstride ? meta_count : kstride) * sizeof(int), hipMemcpyDeviceToHost));
     return DDMPC_OK;
   }
-  if (h->large_nominal && ws_count < 0 && h->d_rr2cand.p) {
+  if (!nominal_route(h->solve_route) || !h->d_rr.p || !h->d_rrmeta.p) return fail(DDMPC_ERR_NOT_READY, "no global workspace to read");
+  if (ws_count < 0 && h->d_rr2cand.p) {
     // diagnostics: the pivot candidates of G's factorisation (phase kernels), n16 doubles, relative to nothing (dmax is meta's business)
     const int n16 = (h->kp.r + 15) & ~15;
     if (ws_avail) *ws_avail = n16;
@@ -2400,11 +2397,10 @@ int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws
     if (ws_out) HIP_TRY(hipMemcpy(ws_out, (const double*)h->d_rr2cand.p + b * n16, (size_t)n16 * sizeof(double), hipMemcpyDeviceToHost));
     return DDMPC_OK;
   }
-  if (!h->large_nominal || !h->d_rr.p || !h->d_rrmeta.p) return fail(DDMPC_ERR_NOT_READY, "no global workspace to read");
   if (b < 0 || b >= h->batch) return fail(DDMPC_ERR_INVALID, "instance out of range");
   HIP_TRY(hipSetDevice(h->device));
-  const size_t r = (size_t)h->kp.r, nR = (size_t)h->n_free, rv = (r + 1) & ~(size_t)1;
-  const size_t ndbl = pk_size((r + 15) & ~(size_t)15) + pk_size((nR + 15) & ~(size_t)15), nmeta = 2 * rv + 2;
+  const size_t rv = ((size_t)h->kp.r + 1) & ~(size_t)1;
+  const size_t ndbl = (size_t)rr2_ndbl(h), nmeta = 2 * rv + 2;
   if (ws_avail) *ws_avail = (int64_t)ndbl;
   if (meta_avail) *meta_avail = (int64_t)nmeta;
   HIP_TRY(hipStreamSynchronize(h->stream));

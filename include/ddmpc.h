@@ -344,7 +344,9 @@ int ddmpc_debug_stamps(ddmpc_handle* h, int enable, uint64_t* out);
  * (16 ceil(r / 16) doubles: the pivot where a column was accepted, the residue where it was skipped; tools/pivot_gap_study.py).
  * ROBUST controllers beyond 271 rows on the phase kernels: meta_out receives the per-instance record of the last solve
  * [k, state, iterations, k, switched positions (64), active set (r rounded up to 2), start tick, ticks (100 MHz), -, -] and
- * *ws_avail = 0 (tools/rr3_schedule.py). */
+ * *ws_avail = 0 (tools/rr3_schedule.py).  What is read is what the last solve left, on the implementation that served it:
+ * DDMPC_ERR_NOT_READY when that was none of the above (no solve yet, the register-resident kernels, the one-workgroup ROBUST
+ * kernel). */
 int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws_count, int32_t* meta_out, int64_t meta_count,
                           int64_t* ws_avail, int64_t* meta_avail);
 

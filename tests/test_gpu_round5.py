@@ -97,27 +97,63 @@ def test_explicit_structured_gram_on_a_trajectory_beyond_the_gram_launch_lds(gpu
 
 
 # ------------------------------------------------------------------ pipeline switch between ddmpc_prepare and ddmpc_step
-def test_prepare_under_stamps_then_step_without_them(gpu):
-    # NOMINAL controller beyond 271 rows.  ddmpc_debug_stamps selects the one-workgroup pipeline; its ddmpc_prepare leaves no
-    # Minv blocks / live masks, which the phase-kernel solve of a later ddmpc_step (stamps off again) would read -- null or
-    # stale (advisor finding of round 4).  The switch now forgets the kept factors: the step re-prepares on its own pipeline.
-    from test_gpu_round3 import _config5
+@pytest.mark.parametrize("case", ["nominal_cfg5", "robust_convex_296"])
+def test_prepare_under_stamps_then_step_without_them(gpu, case):
+    # Controllers beyond 271 rows.  ddmpc_debug_stamps selects the one-workgroup route (the phase kernels carry no stamps), and the
+    # two routes keep different things next to the factors (Minv blocks, live masks; ROBUST: other slices altogether): what
+    # ddmpc_prepare kept serves only the route it was formed on, and a step on the other route prepares again (advisor findings of
+    # rounds 4 and 5 -- for ROBUST the step read the other layout: a GPU memory fault, or wrong results).  The cold solve on the
+    # phase route comes first: it sizes every workspace of that route, so a step that mixed the layouts fails an assertion here.
     B = 3
-    spec, plant, N, d, up, yp = _config5(B)
+    if case == "nominal_cfg5":
+        from test_gpu_round3 import _config5
+        spec, plant, N, d, up, yp = _config5(B)
+    else:
+        N = 700
+        spec, d, up, yp = _four_tank_long(B, 70, N, "convex")
     with _spec_engine(spec, N, B) as eng:
         eng.set_data(d["u_d"], d["y_d"])
-        ref = tuple(x.copy() for x in eng.solve(up, yp))
-    with _spec_engine(spec, N, B) as eng:
-        eng.set_data(d["u_d"], d["y_d"])
+        ref = tuple(x.copy() for x in eng.solve(up, yp))                 # phase route
         eng.debug_stamps(True)
+        ref1 = tuple(x.copy() for x in eng.solve(up, yp))                # one-workgroup route
         eng.prepare()
         eng.debug_stamps(False)
         w = tuple(x.copy() for x in eng.step(up, yp))
-        eng.debug_stamps(True)                           # ... and the other way round
+        eng.debug_stamps(True)                                           # ... and the other way round
         w2 = tuple(x.copy() for x in eng.step(up, yp))
-    assert np.all(ref[2] == 0) and np.array_equal(w[2], ref[2]) and np.array_equal(w2[2], ref[2])
-    assert np.array_equal(w[0], ref[0]) and np.array_equal(w[1], ref[1])          # same pipeline, same factors: bit-equal
-    assert np.max(np.abs(w2[0] - ref[0])) <= 1e-8 * np.max(np.abs(ref[0]))        # the other pipeline: inside the bar
+        eng.debug_stamps(False)
+        eng.prepare()
+        eng.debug_stamps(True)
+        c1 = tuple(x.copy() for x in eng.solve(up, yp))                  # a cold solve on the other route overwrites the workspace ...
+        eng.debug_stamps(False)
+        w3 = tuple(x.copy() for x in eng.step(up, yp))                   # ... so the step prepares again
+    assert np.all(ref[2] == 0) and np.all(ref1[2] == 0)
+    assert all(np.array_equal(a, b_) for a, b_ in zip(w, ref))           # same route, same factors: bit-equal
+    assert all(np.array_equal(a, b_) for a, b_ in zip(w3, ref))
+    assert all(np.array_equal(a, b_) for a, b_ in zip(w2, ref1)) and all(np.array_equal(a, b_) for a, b_ in zip(c1, ref1))
+    assert np.max(np.abs(w2[0] - w[0])) <= TOL_U * np.max(np.abs(w[0]))  # the other route: inside the bars
+    assert np.max(np.abs(w2[1] - w[1]) / np.abs(w[1])) < TOL_COST
+
+
+def test_debug_workspace_reads_the_route_of_the_last_solve(gpu):
+    # ddmpc_debug_workspace returned the rr3 record whenever one had ever been allocated, also after the pipeline changed (advisor
+    # finding of round 5).  It reads what the last solve left on the route that served it: ROBUST at 296 rows on the phase kernels
+    # leaves the rr3 record; the one-workgroup kernel leaves nothing this call reads.
+    import ctypes as C
+    B, N = 2, 700
+    spec, d, up, yp = _four_tank_long(B, 70, N, "convex")
+    rv = ((spec.m + spec.p) * (spec.L + spec.n) + 1) & ~1
+    RR3_KMAX = 64                                                        # ddmpc_rr3.hpp
+    lib = L.load()
+    na, nm = C.c_int64(-1), C.c_int64(-1)
+    with _spec_engine(spec, N, B) as eng:
+        eng.set_data(d["u_d"], d["y_d"])
+        eng.solve(up, yp)
+        L.check(lib.ddmpc_debug_workspace(eng._h, 0, None, 0, None, 0, C.byref(na), C.byref(nm)))
+        assert na.value == 0 and nm.value == 4 + RR3_KMAX + rv + 4
+        eng.set_large_pipeline("one_workgroup")
+        eng.solve(up, yp)
+        assert lib.ddmpc_debug_workspace(eng._h, 0, None, 0, None, 0, C.byref(na), C.byref(nm)) == L.ERR_NOT_READY
 
 
 # ------------------------------------------------------------------ solve -> prepare (affine law) -> get_solution(alpha)
