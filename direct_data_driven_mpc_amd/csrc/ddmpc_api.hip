@@ -2,7 +2,7 @@
 // Host-side responsibilities: parameter validation with the reference's error
 // conditions (direct_data_driven_mpc_controller.py:165-168,211-222,298-343,664-670),
 // device buffer ownership, kernel-instance selection, launch.
-#include "ddmpc_rr3.hpp"
+#include "ddmpc_rr3_law.hpp"
 #include "../../include/ddmpc.h"
 
 #include <cmath>
@@ -198,6 +198,10 @@ struct ddmpc_handle {
   DevBuf d_rr3w, d_rr3k, d_rr_fb, d_rrmeta_fb;   // ROBUST beyond 271 rows on the phase kernels (ddmpc_rr3.hpp): W + the k x k factor, the per-instance
                                           // ints; workspace / record of the fall-back (ddmpc_large_solve_kernel on instances marked 5)
   int nA3 = 0;                            // ... first position of the slack-box components in the "boxed last" order
+  DevBuf d_r3y, d_r3res, d_r3zp, d_r3flag; // ... DDMPC_OPT_LARGE_AFFINE_LAW (ddmpc_rr3_law.hpp; the law itself in d_gz): substitution
+                                          //   vectors, residuals and Hankel sums of a chunk of instances; [no law | re-solve | refine] flags,
+                                          //   then the re-solve flags again as Rr2Solve::si (2 ints per instance)
+  int r3_nolaw = 0;                       // ... instances whose law missed the refinement threshold (their steps take the filtered re-solve)
   DevBuf d_gpre;                          // Gram tiles of ddmpc_gram_tiles_kernel (structured Gram, m + p != 4), see gram_pre_launch
   bool gram_pre = false, gpre_valid = false;
   int gram_launch = 0;                     // DDMPC_OPT_GRAM_LAUNCH: 0 streaming matrix-pipe kernel (rr2_gram_tiles*_kernel), 1 ddmpc_gram_tiles_kernel
@@ -956,23 +960,21 @@ static int launch_rr3_factors(ddmpc_handle* h) {
   return DDMPC_OK;
 }
 
-// The solve on those factors (what a control step repeats, controller.py:389-407).
-static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up, const double* yp, double* uo, double* cost,
-                            int32_t* status, int32_t* iters) {
+// The descriptor of the kept factors and of the solve's workspace (sized here).
+static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
   const int r = kq.r, n16 = (r + 15) & ~15, rv = (r + 1) & ~1, VL = (r + 63) & ~63;
   const size_t B = (size_t)h->batch;
   const long long m64G = rr2_m64(n16);
   const int nA = kq.convex ? h->nA3 : r, n0 = nA & ~63;
   const int ldw = ((r - n0) + 63) & ~63;
-  const Rr3Lds LD = Rr3Lds::make(r);
-  const size_t lds = (size_t)LD.total * sizeof(double);
   const long long wstride = (long long)RR3_KMAX * ldw + (long long)RR3_KMAX * (RR3_KMAX + 1), kstride = 4 + RR3_KMAX + rv + 4;
   int rc;
   if ((rc = h->d_rr2v.ensure(B * (size_t)R3_NV * VL * sizeof(double))) || (rc = h->d_rr2zp.ensure(B * (size_t)RR2_NG * VL * sizeof(double))) ||
       (rc = h->d_rr3w.ensure(B * (size_t)wstride * sizeof(double))) || (rc = h->d_rr3k.ensure(B * (size_t)kstride * sizeof(int))) ||
       (rc = h->d_beta.ensure(B * (size_t)kq.rE * sizeof(double))) || (rc = h->d_act.ensure(B * (size_t)kq.rE)))
     return rc;
-  Rr3 S{};
+  Rr3& S = *out;
+  S = Rr3{};
   S.ws = (const double*)h->d_rr.p; S.stride = rr3_ndbl(h);
   S.m64 = (const double*)h->d_rr2mt.p; S.m64_stride = m64G;
   S.skip = (const int*)h->d_rrmeta.p; S.s_stride = 2 * (long long)rv + 2;
@@ -983,6 +985,20 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
   S.ZP = (double*)h->d_rr2zp.p;
   S.Wg = (double*)h->d_rr3w.p; S.wstride = wstride; S.ldw = ldw;
   S.kq = (int*)h->d_rr3k.p; S.kstride = kstride;
+  return DDMPC_OK;
+}
+
+// The solve on those factors (what a control step repeats, controller.py:389-407).  only (nullptr: the whole batch): per-instance
+// flags of the law step, the solve launches leave every other instance alone.
+static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up, const double* yp, double* uo, double* cost,
+                            int32_t* status, int32_t* iters, const int* only = nullptr, int* only_si = nullptr) {
+  const int r = kq.r, VL = (r + 63) & ~63;
+  const size_t B = (size_t)h->batch;
+  const Rr3Lds LD = Rr3Lds::make(r);
+  const size_t lds = (size_t)LD.total * sizeof(double);
+  Rr3 S;
+  int rc;
+  if ((rc = rr3_desc(h, kq, &S))) return rc;
   const int RPs = 16 * h->kc.NT;
   const bool refine = kq.refine != DDMPC_REFINE_OFF && kq.lam != 0.0;
   if (lds > 64 * 1024) {
@@ -990,16 +1006,17 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     HIP_TRY(raise_lds_limit((const void*)rr3_solve_kernel<true>, lds));
   }
   hipLaunchKernelGGL(rr3_solve_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), lds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
-                     (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0);
+                     (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, only);
   if (refine) {
     // H (H' beta) with exact products (the Hankel kernels of the NOMINAL pipeline: they read slot R3_X of the vectors)
     Rr2Solve H{};
     H.V = S.V; H.vstride = S.vstride; H.VL = VL; H.ZP = S.ZP; H.fdiv = 1; H.r = r;
+    H.si = only_si;                                       // (the filtered re-solve: only the flagged instances, pass > 0 skips the rest)
     HankelLaunch hk;
     if ((rc = pick_hankel_launch(kq, &hk))) return rc;
-    launch_hankel(hk, h->stream, (unsigned)B, H, kq, h->ud, h->yd, (int)R3_X, 0);
+    launch_hankel(hk, h->stream, (unsigned)B, H, kq, h->ud, h->yd, (int)R3_X, only_si != nullptr ? 1 : 0);
     hipLaunchKernelGGL(rr3_solve_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), lds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
-                       (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0);
+                       (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, only);
   }
   HIP_TRY(hipGetLastError());
   {
@@ -1015,6 +1032,94 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
                        (int*)h->d_rrmeta_fb.p, 5, (long long)B);
     HIP_TRY(hipGetLastError());
   }
+  return DDMPC_OK;
+}
+
+// DDMPC_OPT_LARGE_AFFINE_LAW on Route::RobustPhases (ddmpc_rr3_law.hpp): the law beta(w) = g0 + G' w of every instance on the
+// kept factor -- all n(m+p) + 1 right-hand sides by multi-column substitutions on the matrix pipe, then (refinement on) passes of
+// exact-Hankel residuals and corrections through the same kernels.  Chunks of instances bound the virtual batch of the Hankel
+// product (grid rows) and the scratch.  An instance whose law misses the threshold after refine_max passes is marked "no law".
+static int launch_rr3_law_build(ddmpc_handle* h) {
+  const KParams& k = h->kp;
+  const int r = k.r, nf = h->prm.n * k.nch, nrhs = nf + 1, ncb = (nrhs + 63) / 64, VL = (r + 63) & ~63;
+  if (nf > WARM_MAX_NF) return fail(DDMPC_ERR_UNSUPPORTED, "the affine law supports n*(m+p) <= %d", WARM_MAX_NF);
+  const size_t B = (size_t)h->batch;
+  const size_t Bc = std::min<size_t>(B, std::min<size_t>(32, (size_t)(65535 / nrhs)));
+  const bool refine = k.refine != DDMPC_REFINE_OFF && k.lam != 0.0;
+  Rr3 S;
+  int rc;
+  if ((rc = rr3_desc(h, k, &S))) return rc;
+  if ((rc = h->d_gz.ensure((B * nrhs * (size_t)r + VL) * sizeof(double))) || (rc = h->d_r3flag.ensure(5 * B * sizeof(int))) ||
+      (rc = h->d_r3y.ensure(Bc * ncb * (size_t)VL * 64 * sizeof(double))))
+    return rc;
+  if (refine && ((rc = h->d_r3res.ensure(Bc * nrhs * (size_t)r * sizeof(double))) ||
+                 (rc = h->d_r3zp.ensure(Bc * nrhs * (size_t)RR2_NG * VL * sizeof(double)))))
+    return rc;
+  HankelLaunch hk;
+  if (refine && (rc = pick_hankel_launch(k, &hk))) return rc;
+  const int RPs = 16 * h->kc.NT;
+  double* law = (double*)h->d_gz.p;
+  double* Y = (double*)h->d_r3y.p;
+  int* nolaw = (int*)h->d_r3flag.p;
+  int* rfl = nolaw + 2 * B;
+  HIP_TRY(hipMemsetAsync(nolaw, 0, B * sizeof(int), h->stream));
+  std::vector<int> fl(Bc);
+  for (size_t b0 = 0; b0 < B; b0 += Bc) {
+    const size_t nb = std::min(Bc, B - b0);
+    const dim3 grid((unsigned)ncb, (unsigned)nb);
+    hipLaunchKernelGGL(rr3_law_fwd_kernel<false>, grid, dim3(RR2_TS), 0, h->stream, S, k, RPs, (long long)b0, nf, (const double*)nullptr,
+                       (const int*)nullptr, Y, nolaw);
+    hipLaunchKernelGGL(rr3_law_bwd_kernel<false>, grid, dim3(RR2_TS), 0, h->stream, S, (long long)b0, nf, (const int*)nullptr, Y, law, nolaw);
+    HIP_TRY(hipGetLastError());
+    if (!refine) continue;
+    Rr2Solve H{};
+    H.V = law + b0 * nrhs * (size_t)r; H.vstride = r; H.VL = VL; H.ZP = (double*)h->d_r3zp.p; H.fdiv = nrhs; H.r = r;
+    for (int pass = 0;; ++pass) {
+      const bool last = pass == k.refine_max, force = pass == 0 && k.refine == DDMPC_REFINE_ALWAYS;
+      HIP_TRY(hipMemsetAsync(rfl + b0, 0, nb * sizeof(int), h->stream));
+      launch_hankel(hk, h->stream, (unsigned)(nb * nrhs), H, k, h->ud + b0 * (size_t)k.N * k.m, h->yd + b0 * (size_t)k.N * k.p, 0, 0);
+      hipLaunchKernelGGL(rr3_law_resid_kernel, dim3((unsigned)nrhs, (unsigned)nb), dim3(256), 0, h->stream, k, RPs, (long long)b0, nf,
+                         (const double*)law, (const double*)h->d_r3zp.p, VL, (double*)h->d_r3res.p, rfl, force ? 1 : 0,
+                         last ? nolaw : nullptr);
+      HIP_TRY(hipGetLastError());
+      if (last) break;
+      HIP_TRY(hipMemcpyAsync(fl.data(), rfl + b0, nb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      bool any = false;
+      for (size_t i = 0; i < nb; ++i) any = any || fl[i] != 0;
+      if (!any) break;                                      // every law of the chunk is within the threshold
+      hipLaunchKernelGGL(rr3_law_fwd_kernel<true>, grid, dim3(RR2_TS), 0, h->stream, S, k, RPs, (long long)b0, nf,
+                         (const double*)h->d_r3res.p, (const int*)rfl, Y, nolaw);
+      hipLaunchKernelGGL(rr3_law_bwd_kernel<true>, grid, dim3(RR2_TS), 0, h->stream, S, (long long)b0, nf, (const int*)rfl, Y, law, nolaw);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  std::vector<int> nl(B);
+  HIP_TRY(hipMemcpyAsync(nl.data(), nolaw, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->r3_nolaw = 0;
+  for (size_t i = 0; i < B; ++i) h->r3_nolaw += nl[i] != 0;
+  h->large_gain_ready = true;
+  return DDMPC_OK;
+}
+
+// A control step on that law: one launch over the batch, then -- under the slack box, or when some instance has no law -- the solve
+// on the kept factor restricted to the instances the step left to it.
+static int launch_rr3_law_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
+                               int32_t* iters) {
+  const KParams& k = h->kp;
+  const size_t B = (size_t)h->batch;
+  Rr3 S;
+  int rc;
+  if ((rc = rr3_desc(h, k, &S))) return rc;
+  const int* nolaw = (const int*)h->d_r3flag.p;
+  int* need = (int*)h->d_r3flag.p + B;
+  int* si = (int*)h->d_r3flag.p + 3 * B;                   // [2 B]: need in the layout of Rr2Solve::si
+  hipLaunchKernelGGL(rr3_law_step_kernel, dim3((unsigned)B), dim3(RR2_TS), 0, h->stream, S, k, 16 * h->kc.NT, h->prm.n * k.nch,
+                     (const double*)h->d_gz.p, nolaw, up, yp, uo, cost, (int*)status, (int*)iters, (double*)h->d_beta.p,
+                     (signed char*)h->d_act.p, need, si);
+  HIP_TRY(hipGetLastError());
+  if (k.convex || h->r3_nolaw > 0) return launch_rr3_solve(h, k, up, yp, uo, cost, status, iters, need, si);
   return DDMPC_OK;
 }
 
@@ -1046,6 +1151,7 @@ static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const 
     // lock-step factorisation of the whole batch, then one workgroup per instance that streams the factor twice and runs the
     // active-set iterations on its trailing block
     if (stage != Stage::OnFactors && (rc = launch_rr3_factors(h))) return rc;
+    if (stage == Stage::OnFactors && h->large_affine && h->large_gain_ready) return launch_rr3_law_step(h, up, yp, uo, cost, status, iters);
     if (stage != Stage::Factors && (rc = launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters))) return rc;
     return DDMPC_OK;
   }
@@ -1749,7 +1855,9 @@ int ddmpc_prepare(ddmpc_handle* h) {
   }
   if (route != Route::Cold) {             // ROBUST at this size: Gram + lam D, the factor of the columns outside the slack box and
                                           // the Schur complement of the boxed block are formed once and kept
-    const int rc = launch_large_robust(h, route, Stage::Factors, h->ud, h->yd, nullptr, nullptr, nullptr, nullptr);
+    h->large_gain_ready = false;
+    int rc = launch_large_robust(h, route, Stage::Factors, h->ud, h->yd, nullptr, nullptr, nullptr, nullptr);
+    if (!rc && h->large_affine && route == Route::RobustPhases) rc = launch_rr3_law_build(h);   // ... and the affine law on that factor
     h->prepared = rc == DDMPC_OK;
     return rc;
   }
@@ -1903,11 +2011,12 @@ int ddmpc_step(ddmpc_handle* h, const double* u_past, const double* y_past, doub
 
 int ddmpc_get_gain(ddmpc_handle* h, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
-  if (h->large && !(h->large_nominal && h->large_affine))
-    return fail(DDMPC_ERR_UNSUPPORTED, "no affine law at this problem size (NOMINAL controllers: DDMPC_OPT_LARGE_AFFINE_LAW)");
+  if (h->large && !h->large_affine)
+    return fail(DDMPC_ERR_UNSUPPORTED, "no affine law at this problem size without DDMPC_OPT_LARGE_AFFINE_LAW");
   if (!prep_valid(h) || (h->large && !h->large_gain_ready)) return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare must be called before ddmpc_get_gain");
   HIP_TRY(hipSetDevice(h->device));
-  // (beyond the register-resident kernels: z = [ubar; ybar] (component order) = gain[:,0] + gain[:,1:]' [u_past; y_past])
+  // (beyond the register-resident kernels, NOMINAL: z = [ubar; ybar] (component order) = gain[:,0] + gain[:,1:]' [u_past; y_past];
+  //  ROBUST: beta of the empty active set (component order) = gain[:,0] + gain[:,1:]' [u_past; y_past], as below 272 rows)
   const size_t bytes = (size_t)h->batch * (h->prm.n * h->kp.nch + 1) * h->kp.r * sizeof(double);
   HIP_TRY(hipMemcpyAsync(out, h->large ? h->d_gz.p : h->d_gain.p, bytes, mem == DDMPC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                          h->stream));
@@ -1935,6 +2044,7 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
     case DDMPC_OPT_REFINE_MAX:
       if (value < 1 || value > 10) return fail(DDMPC_ERR_INVALID, "refinement passes must be within [1, 10]");
       h->kp.refine_max = value;
+      if (h->large_affine) h->prepared = false;   // the ROBUST law beyond 271 rows marks "no law" after refine_max passes
       return DDMPC_OK;
     case DDMPC_OPT_REFINE_RES_LOG10:
       if (value < 0 || value > 3000)
@@ -1946,6 +2056,11 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       // (the law's step kernel evaluates the cost with the diagonal weights, and the law is built by the phase kernels: 1024 rows)
       if (value != 0 && h->large_nominal && (h->prm.weight_kind == DDMPC_WEIGHT_DENSE || h->kp.r > 1024))
         return fail(DDMPC_ERR_UNSUPPORTED, "the affine law of NOMINAL controllers beyond 271 rows takes scalar / diagonal weights and at most 1024 rows");
+      // (ROBUST: the law step evaluates z with the diagonal weights, the law is built on the phase kernels, its step stages the window in LDS)
+      if (value != 0 && h->large && !h->large_nominal &&
+          (h->prm.weight_kind == DDMPC_WEIGHT_DENSE || h->kp.r > 1024 || h->prm.n * h->kp.nch > WARM_MAX_NF))
+        return fail(DDMPC_ERR_UNSUPPORTED, "the affine law of ROBUST controllers beyond 271 rows takes scalar / diagonal weights, at most 1024 rows "
+                    "and n*(m+p) <= %d", WARM_MAX_NF);
       h->large_affine = value != 0;
       h->prepared = false;
       h->large_gain_ready = false;

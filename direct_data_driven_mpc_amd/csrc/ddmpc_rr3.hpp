@@ -407,6 +407,7 @@ __device__ __forceinline__ void rr3_small_solve(const double* Sm, int k, const d
 // ---------------------------------------------------------------------------------------------------------------
 // The solve on the kept factor.  grid = batch, RR2_TS threads, dynamic LDS (Rr3Lds + W).  refine != 0: beta and everything the
 // refinement launch needs go to global memory and the outputs are left to rr3_refine_kernel; else the outputs are written here.
+// only (nullptr: every instance): per-instance flags, the instances without one leave at once (the filtered re-solve of the law step).
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void rr3_outputs(const KParams& P, int RPs, const Rr3& S, long long b, const int* perm, const double* tv, const double* bv,
                                             const int* act, int st, int iter, double* red, double* __restrict__ u_opt, double* __restrict__ cost,
@@ -472,9 +473,11 @@ template <bool REFINE_PASS>
 __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_kernel(Rr3 S, KParams P, int RPs, const double* __restrict__ u_past,
                                                            const double* __restrict__ y_past, double* __restrict__ u_opt,
                                                            double* __restrict__ cost, int* __restrict__ status, int* __restrict__ iters,
-                                                           double* __restrict__ beta_ws, signed char* __restrict__ act_ws, int defer_outputs) {
+                                                           double* __restrict__ beta_ws, signed char* __restrict__ act_ws, int defer_outputs,
+                                                           const int* __restrict__ only) {
   extern __shared__ __attribute__((aligned(16))) double r3_lds[];
   const long long b = blockIdx.x;
+  if (only != nullptr && only[b] == 0) return;               // (workgroup-uniform) the law step of ddmpc_rr3_law.hpp finished this instance
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
   const int r = S.r, nA = S.nA, n0 = S.n0, m = P.m, p = P.p;
   const int n = P.npu / m;

@@ -221,7 +221,8 @@ class BatchedDDMPC:
         return self.solve(u_past, y_past, u_opt, cost, status, iters, warm=True)
 
     def gain(self) -> np.ndarray:
-        """The prepared affine law: [batch, n*(m+p)+1, r] with beta = gain[:,0] + gain[:,1:]^T [u_past; y_past]."""
+        """The prepared affine law: [batch, n*(m+p)+1, r] with beta = gain[:,0] + gain[:,1:]^T [u_past; y_past] (component
+        order; a large NOMINAL handle's law gives z = [ubar; ybar] instead of beta)."""
         nf = self.n * (self.m + self.p)
         out = np.empty((self.batch, nf + 1, (self.m + self.p) * (self.L + self.n)))
         L.check(self._lib.ddmpc_get_gain(self._h, C.c_void_p(out.ctypes.data), L.MEM_HOST))
@@ -269,8 +270,11 @@ class BatchedDDMPC:
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_GRAM_LAUNCH, {"matrix_pipe": 0, "staged": 1}[kind]))
 
     def set_large_affine_law(self, on: bool) -> None:
-        """NOMINAL controllers beyond the register-resident kernels: `prepare` also forms the affine law z(past) and `step`
-        evaluates it (DDMPC_OPT_LARGE_AFFINE_LAW; default off: `step` repeats the solve on the kept factors)."""
+        """Controllers beyond the register-resident kernels: `prepare` also forms an affine law of the past window and `step`
+        evaluates it (DDMPC_OPT_LARGE_AFFINE_LAW; default off: `step` repeats the solve on the kept factors).  NOMINAL: the law
+        of z.  ROBUST (phase kernels, up to 1024 rows): the law of beta of the empty active set, in the layout of a small ROBUST
+        handle's `gain()`; under the slack box the instances that leave it are re-solved on the kept factors in the same step.
+        Dense weights, more than 1024 rows or n(m+p) > 256 raise ERR_UNSUPPORTED."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_AFFINE_LAW, 1 if on else 0))
 
     def closed_loop(self, A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step: int = 1):

@@ -120,7 +120,22 @@ extern "C" {
                                          returns it as [batch][n(m+p)+1][(m+p)(L+n)], z = [ubar; ybar] per component = gain[0] +
                                          gain[1:]' [u_past; y_past].  0 (default): ddmpc_step repeats the solve on the kept factors,
                                          bit-equal to ddmpc_solve (controller.py:389-407).  Scalar / diagonal weights, at most 1024
-                                         rows (DDMPC_ERR_UNSUPPORTED otherwise) */
+                                         rows (DDMPC_ERR_UNSUPPORTED otherwise).
+                                         ROBUST controllers beyond the register-resident kernels (phase kernels, 272 .. 1024 rows): 1 =
+                                         ddmpc_prepare also forms the law of beta of the EMPTY active set on the kept factor K0,
+                                         beta(w) = g0 + G'w, w = [u_past; y_past] (the solution of K0 beta = t(w)), refined
+                                         with exact Hankel products under DDMPC_OPT_REFINE (off: plain substitution; auto: the instances
+                                         whose law residual exceeds the threshold; always: every instance; an instance still above the
+                                         threshold after DDMPC_OPT_REFINE_MAX passes has no law and its steps take the re-solve below).
+                                         ddmpc_get_gain returns it as [batch][n(m+p)+1][(m+p)(L+n)], beta per component (rho = k(m+p)+ch)
+                                         = gain[0] + gain[1:]' [u_past; y_past]: the layout and meaning of a ROBUST gain below 272 rows
+                                         (the NOMINAL law above is z, not beta).  ddmpc_step evaluates the law in one HBM-bound launch and
+                                         writes outputs, beta / active-set workspace and the rr3 record (ddmpc_get_solution,
+                                         ddmpc_debug_workspace); with the CONVEX slack box an instance whose boxed slacks all stay within
+                                         c eps_max is optimal as it is (iters 1), the others are re-solved in the same call on the kept
+                                         factors, like ddmpc_solve (same iterations, statuses, solutions to rounding).  Scalar / diagonal
+                                         weights, at most 1024 rows, n(m+p) <= 256 (DDMPC_ERR_UNSUPPORTED otherwise); no effect with
+                                         DDMPC_PIPELINE_ONE_WORKGROUP (ddmpc_get_gain: DDMPC_ERR_NOT_READY) */
 #define DDMPC_OPT_CONVEX_UPDATE 8      /* ROBUST controllers with the CONVEX slack box on the register-resident kernels
                                          (controller.py:631-677): 1 (default) = active-set iterations after the first keep the factor
                                          of the empty active set and treat the <= 4 switched slack components as a diagonal modification
@@ -182,8 +197,8 @@ int ddmpc_device_count(void);
  * profiles/README.md): ROBUST ones on ddmpc_large_solve_kernel (same outputs, status, iterations, ddmpc_get_solution),
  * NOMINAL ones on the rank-revealing route -- phase kernels over the whole batch by default, the one-workgroup kernels on
  * request (DDMPC_OPT_LARGE_PIPELINE) -- with ddmpc_get_solution: ubar / ybar from its z, alpha = H'x from the vector it
- * exports.  By default no affine law is formed at that size (ddmpc_get_gain is DDMPC_ERR_UNSUPPORTED unless a NOMINAL
- * controller asked for it with DDMPC_OPT_LARGE_AFFINE_LAW); the warm path there is
+ * exports.  By default no affine law is formed at that size (ddmpc_get_gain is DDMPC_ERR_UNSUPPORTED unless the
+ * controller asked for it with DDMPC_OPT_LARGE_AFFINE_LAW: NOMINAL z(past), ROBUST beta(past) up to 1024 rows); the warm path there is
  * factor reuse -- ddmpc_prepare forms what depends on the data and the weights alone (NOMINAL: Gram, its rank-revealing
  * factor, the reduced normal matrix and its factor; ROBUST: Gram + lam D, the factor of the columns outside the slack
  * box, the Schur complement of the boxed block), ddmpc_step and the per-step closed loop solve on what it kept, with
@@ -255,7 +270,8 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
  *   active-set iteration cap, as for ddmpc_solve).
  * ddmpc_get_gain: out [batch, nf+1, r] doubles, r = (m+p)(L+n) components in the internal
  *   time-major order rho = k*(m+p) + ch (ch < m: ubar, else ybar+sigma).
- * Beyond 271 rows: see the note on problem sizes at ddmpc_create (the data-dependent factors are kept, no law). */
+ * Beyond 271 rows: see the note on problem sizes at ddmpc_create (the data-dependent factors are kept; a law only with
+ *   DDMPC_OPT_LARGE_AFFINE_LAW: NOMINAL z, ROBUST beta of the empty active set in the layout above, up to 1024 rows). */
 int ddmpc_prepare(ddmpc_handle* h);
 int ddmpc_step(ddmpc_handle* h, const double* u_past, const double* y_past,
                double* u_opt, double* cost, int32_t* status, int32_t* iters, int mem);
