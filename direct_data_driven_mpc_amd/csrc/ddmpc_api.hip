@@ -668,7 +668,7 @@ int ddmpc_create(const ddmpc_params* params, int64_t batch, int device, ddmpc_ha
     // hankel_matrix.py:39-51 takes any N >= L.  A trajectory beyond the LDS is never staged: G = H H' comes from the streaming
     // Gram kernel of the phase pipeline (trajectory in chunks), written into the kernel's tiles (rr2_gram_tiles*_kernel), and the
     // cold kernel runs in its `gpre` mode with no trajectory region at all.  Refinement goes without the whole trajectory on
-    // chip: AUTO's exact-Hankel residual check is streamed by the Hankel kernel of the phase pipeline (long_data_residual_check),
+    // chip: AUTO's exact-Hankel residual check is streamed by the Hankel kernel of the phase pipeline (refine_flagged),
     // and the refining variant passes the trajectory through a window chunk by chunk (ld_window below).
     const int tch = ((RR2_XCAP / k.nch) - k.Ln - 3) & ~3;
     if (k.r > 1024 || tch < 4 || p.weight_kind == DDMPC_WEIGHT_DENSE) {
@@ -821,15 +821,6 @@ static unsigned large_threads(size_t r) {   // workgroup size of the global-work
 
 // Workgroup size of the warm-path kernels (the affine law): a thread per component, 1024 at most.
 static unsigned warm_threads(int r) { return (unsigned)std::min(((r + 63) / 64) * 64, 1024); }
-
-// AUTO refinement: the per-instance flags + one counter word behind them, cleared once when they are first allocated.
-static int ensure_rflag(ddmpc_handle* h) {
-  const size_t bytes = ((size_t)h->batch + 1) * sizeof(int);
-  const bool fresh = h->d_rflag.bytes < bytes;
-  const int rc = h->d_rflag.ensure(bytes);
-  if (!rc && fresh) HIP_TRY(hipMemsetAsync(h->d_rflag.p, 0, bytes, h->stream));
-  return rc;
-}
 
 // Next launch stamp of the AUTO refinement flags (flag[b] == stamp <=> instance b was flagged by THIS launch; the counter word
 // holds the largest stamp that flagged anything).  Stamps only grow, so nothing is cleared between launches -- except
@@ -1123,24 +1114,6 @@ static int launch_rr3_law_step(ddmpc_handle* h, const double* up, const double* 
   return DDMPC_OK;
 }
 
-// Trajectories beyond the LDS (h->long_data), AUTO refinement: the plain kernel flagged what its a-priori bound could not dismiss;
-// H (H' beta) of the whole batch by the streaming Hankel kernel of the phase pipeline, then the residual decides per flagged
-// instance whether the flag stays (the caller launches the refining variant on what is still flagged).
-static int long_data_residual_check(ddmpc_handle* h, const KParams& kq, int* flags, const double* ud, const double* yd, const double* up,
-                                    const double* yp, const double* beta, const signed char* act, int* status, size_t nb) {
-  const int r = kq.r, VL = (r + 63) & ~63;
-  int rc;
-  if ((rc = h->d_rr2zp.ensure((size_t)h->batch * (size_t)RR2_NG * VL * sizeof(double)))) return rc;
-  Rr2Solve H{};
-  H.V = const_cast<double*>(beta); H.vstride = kq.rE; H.VL = VL; H.ZP = (double*)h->d_rr2zp.p; H.fdiv = 1; H.r = r;
-  HankelLaunch hk;
-  if ((rc = pick_hankel_launch(kq, &hk))) return rc;
-  launch_hankel(hk, h->stream, (unsigned)nb, H, kq, ud, yd, 0, 0);
-  hipLaunchKernelGGL(ddmpc_flag_inaccurate_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, kq, 16 * h->kc.NT, kq.epoch, flags, up, yp, beta, act,
-                     (const double*)h->d_rr2zp.p, (int)RR2_NG, VL, status);
-  HIP_TRY(hipGetLastError());
-  return DDMPC_OK;
-}
 
 // ROBUST controllers beyond the register-resident kernels (Route::RobustPhases, Route::RobustOneWg).
 static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const double* up, const double* yp, double* uo,
@@ -1180,72 +1153,128 @@ static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const 
   return DDMPC_OK;
 }
 
+// Pointer arguments of ddmpc_cold_solve_kernel2 (ddmpc_cold2.hpp), in its order.
+struct ColdArgs {
+  const double *ud, *yd, *up, *yp;
+  double *uo, *cost;
+  int32_t *status, *iters = nullptr;
+  double* beta = nullptr; signed char* act = nullptr;     // beta / active-set workspace
+  unsigned long long* stamps = nullptr;
+  double *lfac = nullptr, *lfacT = nullptr;   // factor export (ddmpc_prepare)
+  int *flag = nullptr, *count = nullptr;   // AUTO: per-instance flags of the plain kernel, and the counter word behind them
+  const int* only = nullptr;               // filter: instances with only[b] == 0 are skipped
+  long long nbatch = 0;                    // persistent grid: the instances it strides over
+};
+
+// The launches of the cold kernel.  Plain: fn2, or under the slack box fn2c, which keeps the first factor across active-set
+// iterations (DDMPC_OPT_CONVEX_UPDATE = 0: fn2, which factors again).  Refine: the variant with the refinement loop, which on a
+// trajectory beyond the LDS passes a window of it chunk by chunk.  Filtered: that variant on the instances flagged in d_rflag,
+// a short persistent launch (3 workgroups per CU) that reads one counter word and leaves when nothing was flagged.
+enum class ColdPass { Plain, Refine, Filtered };
+static void enqueue_cold(ddmpc_handle* h, ColdPass pass, KParams k, ColdArgs a, size_t nb) {
+  cold_kernel2_t fn = (k.convex && h->convex_update) ? h->kc.fn2c : h->kc.fn2;
+  size_t lds = h->lds_bytes;
+  if (pass != ColdPass::Plain) {
+    fn = h->kc.fn2r;
+    if (h->long_data) { k.xs_len = h->ld_window; lds = h->ld_lds_bytes; }
+  }
+  unsigned grid = (unsigned)nb;
+  if (pass == ColdPass::Filtered) {
+    k.refine = DDMPC_REFINE_ALWAYS;
+    grid = (unsigned)(nb < 768 ? nb : 768);
+    a.flag = nullptr; a.only = (const int*)h->d_rflag.p; a.nbatch = (long long)nb; a.count = (int*)h->d_rflag.p + h->batch;
+  }
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * h->kc.W), lds, h->stream, k, a.ud, a.yd, a.up, a.yp, a.uo, a.cost, (int*)a.status,
+                     (int*)a.iters, a.beta, a.act, a.stamps, a.lfac, a.lfacT, a.flag, a.only, a.nbatch, a.count);
+}
+
+// What a handle's cold sequence writes besides its outputs, sized before it is enqueued (ddmpc_closed_loop: before a graph
+// capture, inside which nothing may allocate or set an attribute): beta / active set (ws); under AUTO (flags) the flags + counter
+// word, cleared when first allocated, and beyond the LDS the Hankel sums and Hankel kernel LDS of the streamed residual check.
+static int reserve_cold(ddmpc_handle* h, bool ws, bool flags) {
+  const size_t B = (size_t)h->batch, bytes = (B + 1) * sizeof(int);
+  int rc;
+  if (ws && ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE)))) return rc;
+  if (!flags) return DDMPC_OK;
+  const bool fresh = h->d_rflag.bytes < bytes;
+  if ((rc = h->d_rflag.ensure(bytes))) return rc;
+  if (fresh) HIP_TRY(hipMemsetAsync(h->d_rflag.p, 0, bytes, h->stream));
+  if (!h->long_data) return DDMPC_OK;
+  if ((rc = h->d_rr2zp.ensure(B * RR2_NG * (size_t)((h->kp.r + 63) & ~63) * sizeof(double)))) return rc;
+  HankelLaunch hk;
+  return pick_hankel_launch(h->kp, &hk);
+}
+
+// AUTO refinement once the plain launches have flagged the instances their residual check (on a trajectory beyond the LDS: their
+// a-priori bound) could not dismiss.  Beyond the LDS, H (H' beta) of the whole batch by the streaming Hankel kernel of the phase
+// pipeline first; its residual decides per flagged instance whether the flag stays.  Then the filtered refinement pass.
+static int refine_flagged(ddmpc_handle* h, const KParams& kq, const ColdArgs& a) {
+  if (h->long_data) {
+    const int VL = (kq.r + 63) & ~63;
+    Rr2Solve H{};
+    H.V = (double*)h->d_beta.p; H.vstride = kq.rE; H.VL = VL; H.ZP = (double*)h->d_rr2zp.p; H.fdiv = 1; H.r = kq.r;
+    HankelLaunch hk;
+    if (int rc = pick_hankel_launch(kq, &hk)) return rc;
+    launch_hankel(hk, h->stream, (unsigned)h->batch, H, kq, a.ud, a.yd, 0, 0);
+    hipLaunchKernelGGL(ddmpc_flag_inaccurate_kernel, dim3((unsigned)h->batch), dim3(256), 0, h->stream, kq, 16 * h->kc.NT, kq.epoch,
+                       (int*)h->d_rflag.p, a.up, a.yp, (const double*)h->d_beta.p, (const signed char*)h->d_act.p,
+                       (const double*)h->d_rr2zp.p, (int)RR2_NG, VL, (int*)a.status);
+    HIP_TRY(hipGetLastError());
+  }
+  enqueue_cold(h, ColdPass::Filtered, kq, a, (size_t)h->batch);
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
+// What a caller of launch_cold chooses beyond the past window and the outputs: KParams in place of the handle's and the factor
+// export (ddmpc_prepare), whether the beta / active-set workspace is written, a filter (the slack-box warm steps).
+struct ColdSeq {
+  const KParams* kp = nullptr;
+  double *lfac = nullptr, *lfacT = nullptr;
+  bool want_ws = true;
+  const int* only = nullptr;
+};
+
 // The register-resident cold kernels (Route::Cold).  want_ws: also write the beta / active-set workspace (what
 // ddmpc_get_solution, the gain kernel and the slack-box warm step read).  A plain cold solve skips it (1.2 KB of HBM writes per
 // instance) and ddmpc_get_solution re-solves on demand.
-static int launch_cold(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost,
-                       int32_t* status, int32_t* iters, double* lfac = nullptr, const int* only = nullptr,
-                       const KParams* kp_override = nullptr, bool want_ws = true, double* lfacT = nullptr) {
+static int launch_cold(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
+                       int32_t* iters, const ColdSeq& s = ColdSeq()) {
   int rc;
+  const size_t B = (size_t)h->batch;
   h->beta_stale = h->rescue_ran = false;
-  h->ws_stale = !want_ws;
-  if (h->long_data) { want_ws = true; h->ws_stale = false; }       // (the streamed residual check reads beta and the active set)
-  if (want_ws) {
-    if ((rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double)))) return rc;
-    if ((rc = h->d_act.ensure((size_t)h->batch * h->kp.rE))) return rc;
-  }
-  double* bws = want_ws ? (double*)h->d_beta.p : nullptr;
-  signed char* aws = want_ws ? (signed char*)h->d_act.p : nullptr;
-  unsigned long long* stp = h->stamps_on ? (unsigned long long*)h->d_stamps.p : (unsigned long long*)nullptr;
-  dim3 grid((unsigned)h->batch), block(64 * h->kc.W);
+  const bool ws = s.want_ws || h->long_data;       // (the streamed residual check reads beta and the active set)
+  h->ws_stale = !ws;
   // Refinement (DDMPC_OPT_REFINE).  OFF / factor export / nominal scheme (z = t does not depend on beta): plain kernel.
   // ALWAYS: the kernel variant with the refinement loop.  AUTO: plain kernel, which checks every instance's solve with
-  // the exact-Hankel residual and flags the ones above the threshold; those alone are solved again by the refining
-  // variant in a short persistent launch (it reads one counter word and leaves when nothing was flagged).  The decision
-  // is taken per solve: nothing about a data set is remembered, so borrowed device data may change between solves.
-  KParams kq = kp_override ? *kp_override : h->kp;
-  if ((rc = gram_pre_launch(h, kq, h->ud, h->yd, (size_t)h->batch, 0, true))) return rc;
-  const int mode = (lfac != nullptr || kq.lam == 0.0) ? DDMPC_REFINE_OFF : kq.refine;
-  // controllers with the slack box: the plain variant that keeps the first factor across active-set iterations (rank-k update);
-  // DDMPC_OPT_CONVEX_UPDATE = 0 selects the variant that factors again in every iteration (the refining variant always does)
-  const cold_kernel2_t plain = (kq.convex && h->convex_update) ? h->kc.fn2c : h->kc.fn2;
-  // the refining variant on a trajectory beyond the LDS: a window of the trajectory instead of the whole of it (ddmpc_cold2.hpp)
-  KParams kref = kq;
-  size_t ref_lds = h->lds_bytes;
-  if (h->long_data) { kref.xs_len = h->ld_window; ref_lds = h->ld_lds_bytes; }
+  // the exact-Hankel residual and flags the ones above the threshold; those alone are solved again (refine_flagged).  The
+  // decision is taken per solve: nothing about a data set is remembered, so borrowed device data may change between solves.
+  KParams kq = s.kp ? *s.kp : h->kp;
+  const int mode = (s.lfac != nullptr || kq.lam == 0.0) ? DDMPC_REFINE_OFF : kq.refine;
+  // factor export under AUTO: the plain kernel still records which instances AUTO would refine (ddmpc_prepare refines their law)
+  const bool export_flags = s.lfac != nullptr && kq.lam != 0.0 && kq.refine == DDMPC_REFINE_AUTO && s.only == nullptr;
+  if ((rc = gram_pre_launch(h, kq, h->ud, h->yd, B, 0, true))) return rc;
+  if ((rc = reserve_cold(h, ws, mode == DDMPC_REFINE_AUTO || export_flags))) return rc;
+  ColdArgs a{h->ud, h->yd, up, yp, uo, cost, status, iters};
+  if (ws) { a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p; }
+  if (h->stamps_on) a.stamps = (unsigned long long*)h->d_stamps.p;
+  a.lfac = s.lfac; a.lfacT = s.lfacT; a.only = s.only;
   if (mode == DDMPC_REFINE_ALWAYS) {
-    hipLaunchKernelGGL(h->kc.fn2r, grid, block, ref_lds, h->stream, kref, h->ud, h->yd, up, yp, uo, cost, (int*)status,
-                       (int*)iters, bws, aws, stp, lfac, lfacT, (int*)nullptr, only, 0LL, (int*)nullptr);
+    enqueue_cold(h, ColdPass::Refine, kq, a, B);
   } else if (mode == DDMPC_REFINE_AUTO) {
-    // flags [batch] + one counter word behind them (the largest stamp that flagged anything)
-    if ((rc = ensure_rflag(h))) return rc;
-    int* rcount = (int*)h->d_rflag.p + h->batch;
-    if (only) HIP_TRY(hipMemsetAsync(h->d_rflag.p, 0, (size_t)h->batch * sizeof(int), h->stream));   // filtered-out instances: no flag
+    if (s.only) HIP_TRY(hipMemsetAsync(h->d_rflag.p, 0, B * sizeof(int), h->stream));   // filtered-out instances: no flag
     kq.epoch = next_refine_epoch(h);
-    hipLaunchKernelGGL(plain, grid, block, h->lds_bytes, h->stream, kq, h->ud, h->yd, up, yp, uo, cost, (int*)status,
-                       (int*)iters, bws, aws, stp, lfac, lfacT, (int*)h->d_rflag.p, only, 0LL, rcount);
+    a.flag = (int*)h->d_rflag.p; a.count = a.flag + B;
+    enqueue_cold(h, ColdPass::Plain, kq, a, B);
     HIP_TRY(hipGetLastError());
-    // (trajectory beyond the LDS: the exact residual check the plain kernel could not run, streamed; it clears the flags it can)
-    if (h->long_data && (rc = long_data_residual_check(h, kq, (int*)h->d_rflag.p, h->ud, h->yd, up, yp, bws, aws, (int*)status, (size_t)h->batch)))
-      return rc;
-    kref.refine = DDMPC_REFINE_ALWAYS;
-    kref.epoch = kq.epoch;
-    const unsigned pg = (unsigned)(h->batch < 768 ? h->batch : 768);       // persistent grid, 3 workgroups per CU
-    hipLaunchKernelGGL(h->kc.fn2r, dim3(pg), block, ref_lds, h->stream, kref, h->ud, h->yd, up, yp, uo, cost, (int*)status,
-                       (int*)iters, bws, aws, stp, lfac, lfacT, (int*)nullptr, (const int*)h->d_rflag.p, (long long)h->batch, rcount);
+    if ((rc = refine_flagged(h, kq, a))) return rc;
     h->flag_epoch = kq.epoch;                   // the flags now carry this stamp
   } else {
-    // factor export for ddmpc_prepare under AUTO: the plain kernel still records which instances AUTO would refine
-    // (their columns of the affine law are then formed from refining solves, see ddmpc_prepare)
-    int *rf = nullptr, *rcount = nullptr;
-    if (lfac != nullptr && kq.lam != 0.0 && kq.refine == DDMPC_REFINE_AUTO && only == nullptr) {
-      if ((rc = ensure_rflag(h))) return rc;
-      rf = (int*)h->d_rflag.p; rcount = rf + h->batch;
-      kq.epoch = h->prep_epoch = next_refine_epoch(h);
-      h->flag_epoch = kq.epoch;
+    if (export_flags) {
+      a.flag = (int*)h->d_rflag.p; a.count = a.flag + B;
+      kq.epoch = h->prep_epoch = h->flag_epoch = next_refine_epoch(h);
     }
-    hipLaunchKernelGGL(plain, grid, block, h->lds_bytes, h->stream, kq, h->ud, h->yd, up, yp, uo, cost, (int*)status,
-                       (int*)iters, bws, aws, stp, lfac, lfacT, rf, only, 0LL, rcount);
+    enqueue_cold(h, ColdPass::Plain, kq, a, B);
   }
   HIP_TRY(hipGetLastError());
   return DDMPC_OK;
@@ -1276,8 +1305,8 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
     HIP_TRY(hipGetLastError());
     h->beta_stale = false;
     h->ws_stale = false;
-    if (need) return launch_cold(h, up, yp, uo, cost, status, iters, nullptr, need);
-    return DDMPC_OK;
+    ColdSeq s; s.only = need;
+    return need ? launch_cold(h, up, yp, uo, cost, status, iters, s) : DDMPC_OK;
   }
   int* need = nullptr;
   if (h->kp.convex) {
@@ -1294,9 +1323,9 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
   HIP_TRY(hipGetLastError());
   h->beta_stale = !keep;
   h->ws_stale = false;
-  if (need)       // instances with an active slack bound: full active-set solve, same launch geometry, others exit at once
-    return launch_cold(h, up, yp, uo, cost, status, iters, nullptr, need);
-  return DDMPC_OK;
+  // instances with an active slack bound: full active-set solve, same launch geometry, others exit at once
+  ColdSeq s; s.only = need;
+  return need ? launch_cold(h, up, yp, uo, cost, status, iters, s) : DDMPC_OK;
 }
 
 // Nominal scheme: instances whose Gram matrix is singular (exact data) are re-solved by the rank-revealing
@@ -1638,7 +1667,8 @@ static int solve_on_route(ddmpc_handle* h, const double* up, const double* yp, d
   if (route == Route::RobustPhases || route == Route::RobustOneWg)
     return launch_large_robust(h, route, Stage::Solve, up, yp, uo, cost, status, iters);
   int rc = DDMPC_OK;
-  if (route == Route::Cold) rc = launch_cold(h, up, yp, uo, cost, status, iters, nullptr, nullptr, nullptr, /*want_ws=*/false);
+  ColdSeq s; s.want_ws = false;
+  if (route == Route::Cold) rc = launch_cold(h, up, yp, uo, cost, status, iters, s);
   else h->beta_stale = h->rescue_ran = h->ws_stale = false;        // (no cold kernel at this size: the rescue is the solve)
   return rc ? rc : launch_nominal_rescue(h, route, up, yp, uo, cost, status, iters);
 }
@@ -1752,21 +1782,12 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
   hipEvent_t ev[8];
   for (size_t k = 0; k < nchunks; ++k) HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
   // refinement (see launch_cold): ALWAYS -> the refining kernel variant per chunk; AUTO -> the chunks flag the instances
-  // that need it and one filtered launch of the refining variant follows the last chunk
+  // that need it and refine_flagged follows the last chunk.  Trajectories beyond the LDS: the chunks write beta / the active
+  // set for the streamed residual check.
   const bool refinable = h->kp.lam != 0.0;
-  const bool always = refinable && h->kp.refine == DDMPC_REFINE_ALWAYS;
-  int* rflag = nullptr;
-  if (refinable && h->kp.refine == DDMPC_REFINE_AUTO) {
-    if ((rc = ensure_rflag(h))) return rc;
-    rflag = (int*)h->d_rflag.p;
-  }
-  double* lbeta = nullptr;                // trajectories beyond the LDS: the chunks write beta / the active set for the streamed residual check
-  signed char* lact = nullptr;
-  if (h->long_data) {
-    if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
-    lbeta = (double*)h->d_beta.p; lact = (signed char*)h->d_act.p;
-    h->ws_stale = false;
-  }
+  const bool always = refinable && h->kp.refine == DDMPC_REFINE_ALWAYS, autoref = refinable && h->kp.refine == DDMPC_REFINE_AUTO;
+  if ((rc = reserve_cold(h, h->long_data, autoref))) return rc;
+  if (h->long_data) h->ws_stale = false;
   KParams kchunk = h->kp;
   kchunk.epoch = next_refine_epoch(h);
   h->flag_epoch = kchunk.epoch;
@@ -1780,15 +1801,11 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
       break;
     }
     KParams kck = kchunk;
-    if ((rcl = gram_pre_launch(h, kck, (const double*)(dud + b0 * su), (const double*)(dyd + b0 * sy), nb, b0, false))) break;
-    if (always && h->long_data) kck.xs_len = h->ld_window;            // (the refining variant's trajectory window)
-    hipLaunchKernelGGL(always ? h->kc.fn2r : ((h->kp.convex && h->convex_update) ? h->kc.fn2c : h->kc.fn2), dim3((unsigned)nb), dim3(64 * h->kc.W),
-                       (always && h->long_data) ? h->ld_lds_bytes : h->lds_bytes, h->stream, kck,
-                       (const double*)(dud + b0 * su), (const double*)(dyd + b0 * sy), (const double*)(dup + b0 * sup),
-                       (const double*)(dyp + b0 * syp), duo + b0 * suo, dco + b0, (int*)(dst + b0), (int*)(dit + b0),
-                       lbeta ? lbeta + b0 * h->kp.rE : (double*)nullptr, lact ? lact + b0 * h->kp.rE : (signed char*)nullptr,
-                       (unsigned long long*)nullptr, (double*)nullptr,
-                       (double*)nullptr, rflag ? rflag + b0 : (int*)nullptr, (const int*)nullptr, 0LL, rflag ? rflag + B : (int*)nullptr);
+    ColdArgs a{dud + b0 * su, dyd + b0 * sy, dup + b0 * sup, dyp + b0 * syp, duo + b0 * suo, dco + b0, dst + b0, dit + b0};
+    if ((rcl = gram_pre_launch(h, kck, a.ud, a.yd, nb, b0, false))) break;
+    if (h->long_data) { a.beta = (double*)h->d_beta.p + b0 * h->kp.rE; a.act = (signed char*)h->d_act.p + b0 * h->kp.rE; }
+    if (autoref) { a.flag = (int*)h->d_rflag.p + b0; a.count = (int*)h->d_rflag.p + B; }
+    enqueue_cold(h, always ? ColdPass::Refine : ColdPass::Plain, kck, a, nb);
     if (hipGetLastError() != hipSuccess) rcl = fail(DDMPC_ERR_HIP, "ddmpc_solve_from_host: launch of chunk %zu failed", k);
   }
   if (rcl == DDMPC_OK && h->gram_pre) {           // every chunk's Gram tiles are in place: they serve the launches below
@@ -1796,19 +1813,7 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
     h->ud = dud; h->yd = dyd;
     rcl = gram_pre_launch(h, kchunk, dud, dyd, B, 0, true);
   }
-  if (rcl == DDMPC_OK && rflag && h->long_data)
-    rcl = long_data_residual_check(h, kchunk, rflag, dud, dyd, dup, dyp, (const double*)h->d_beta.p, (const signed char*)h->d_act.p,
-                                   (int*)dst, B);
-  if (rcl == DDMPC_OK && rflag) {
-    KParams kq = kchunk;
-    kq.refine = DDMPC_REFINE_ALWAYS;
-    if (h->long_data) kq.xs_len = h->ld_window;
-    hipLaunchKernelGGL(h->kc.fn2r, dim3((unsigned)(B < 768 ? B : 768)), dim3(64 * h->kc.W), h->long_data ? h->ld_lds_bytes : h->lds_bytes, h->stream, kq,
-                       (const double*)dud, (const double*)dyd, (const double*)dup, (const double*)dyp, duo, dco, (int*)dst, (int*)dit,
-                       (double*)nullptr, (signed char*)nullptr, (unsigned long long*)nullptr, (double*)nullptr, (double*)nullptr,
-                       (int*)nullptr, (const int*)rflag, (long long)B, rflag + B);
-    if (hipGetLastError() != hipSuccess) rcl = fail(DDMPC_ERR_HIP, "ddmpc_solve_from_host: launch of the refinement pass failed");
-  }
+  if (rcl == DDMPC_OK && autoref) rcl = refine_flagged(h, kchunk, ColdArgs{dud, dyd, dup, dyp, duo, dco, dst, dit});
   if (rcl == DDMPC_OK) {            // NOMINAL on exact data: same rank-revealing rescue as ddmpc_solve (all chunks are uploaded
     h->ud = dud; h->yd = dyd;       // and solved by now in stream order)
     rcl = launch_nominal_rescue(h, Route::Cold, dup, dyp, duo, dco, dst, dit);
@@ -1877,8 +1882,8 @@ int ddmpc_prepare(ddmpc_handle* h) {
   // one cold factorisation with the factor exported (its solution for a zero past window is discarded)
   KParams k0 = h->kp;                              // slack box: factor of the EMPTY active set (one iteration)
   k0.convex = 0;
-  if ((rc = launch_cold(h, z, z + B * p.n * p.m, (double*)h->d_uopt.p, (double*)h->d_cost.p,
-                        (int32_t*)h->d_prep_status.p, nullptr, (double*)h->d_lfac.p, nullptr, &k0, true, (double*)h->d_lfacT.p)))
+  ColdSeq s0; s0.kp = &k0; s0.lfac = (double*)h->d_lfac.p; s0.lfacT = (double*)h->d_lfacT.p;
+  if ((rc = launch_cold(h, z, z + B * p.n * p.m, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p, nullptr, s0)))
     return rc;
   if (k.lam != 0.0 && k.refine == DDMPC_REFINE_AUTO) {
     // AUTO decides from the exact-Hankel residual of a solve, which depends on the right-hand side -- and the factor-export
@@ -1895,17 +1900,15 @@ int ddmpc_prepare(ddmpc_handle* h) {
     KParams kprobe = k0;
     kprobe.epoch = h->prep_epoch;
     if ((rc = gram_pre_launch(h, kprobe, h->ud, h->yd, B, 0, true))) return rc;
-    hipLaunchKernelGGL(h->kc.fn2, dim3((unsigned)B), dim3(64 * h->kc.W), h->lds_bytes, h->stream, kprobe, h->ud, h->yd,
-                       (const double*)pu, (const double*)py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int*)h->d_status.p,
-                       (int*)nullptr, (double*)nullptr, (signed char*)nullptr, (unsigned long long*)nullptr, (double*)nullptr,
-                       (double*)nullptr, (int*)h->d_need.p, (const int*)nullptr, 0LL, (int*)h->d_need.p + B);
+    ColdArgs a{h->ud, h->yd, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p};
+    a.flag = (int*)h->d_need.p; a.count = a.flag + B;
+    enqueue_cold(h, ColdPass::Plain, kprobe, a, B);       // (k0: no slack box, so the plain kernel fn2)
     hipLaunchKernelGGL(ddmpc_or_flags_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, (long long)B,
                        h->prep_epoch, (const int*)h->d_need.p, (int*)h->d_rflag.p);
     HIP_TRY(hipGetLastError());
   }
   const size_t ntiles = B * (size_t)(NT * (NT + 1) / 2);
   if (ntiles > 0x7fffffffULL) return fail(DDMPC_ERR_INVALID, "batch too large for ddmpc_prepare");
-  if ((rc = h->d_beta.ensure(B * k.rE * sizeof(double)))) return rc;     // beta of the cold launch above
   // DDMPC_OPT_CONVEX_WARM_LAW: the boxed components and M = K0^-1 E_box, nbox more right-hand sides of the gain kernel
   const bool cwl = convex_warm_on(h);
   int nbox = 0;
@@ -1954,25 +1957,21 @@ int ddmpc_prepare(ddmpc_handle* h) {
     double* py = pu + B * (size_t)npu;               // the handle's staging buffers may hold a caller's window)
     KParams kr = k0;
     kr.refine = DDMPC_REFINE_ALWAYS;
+    ColdSeq sr; sr.kp = &kr;
+    ColdArgs a{h->ud, h->yd, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p};
+    a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p;
     const unsigned gp = (unsigned)((B * (size_t)(npu + npy) + 255) / 256), gg = (unsigned)((B * (size_t)k.r + 255) / 256);
     for (int j = 0; j < nrhs; ++j) {
       hipLaunchKernelGGL(ddmpc_unit_past_kernel, dim3(gp), dim3(256), 0, h->stream, (long long)B, npu, npy, j - 1,
                          pu, py);
       if (!flagged_only) {
-        if ((rc = launch_cold(h, (const double*)pu, (const double*)py, (double*)h->d_uopt.p, (double*)h->d_cost.p,
-                              (int32_t*)h->d_prep_status.p, nullptr, nullptr, nullptr, &kr, true)))
+        if ((rc = launch_cold(h, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p, nullptr, sr)))
           return rc;
       } else {
-        if ((rc = h->d_act.ensure(B * k.rE))) return rc;
+        // (trajectory beyond the LDS: the flags are those of the a-priori bound alone, no streamed check)
         kr.epoch = h->prep_epoch;
         if ((rc = gram_pre_launch(h, kr, h->ud, h->yd, B, 0, true))) return rc;
-        if (h->long_data) kr.xs_len = h->ld_window;       // (trajectory beyond the LDS: the refining variant's window; there the
-                                                          //  flags are those of the a-priori bound alone, no streamed check)
-        hipLaunchKernelGGL(h->kc.fn2r, dim3((unsigned)(B < 768 ? B : 768)), dim3(64 * h->kc.W), h->long_data ? h->ld_lds_bytes : h->lds_bytes, h->stream, kr, h->ud,
-                           h->yd, (const double*)pu, (const double*)py, (double*)h->d_uopt.p, (double*)h->d_cost.p,
-                           (int*)h->d_prep_status.p, (int*)nullptr, (double*)h->d_beta.p, (signed char*)h->d_act.p,
-                           (unsigned long long*)nullptr, (double*)nullptr, (double*)nullptr, (int*)nullptr,
-                           (const int*)h->d_rflag.p, (long long)B, (int*)h->d_rflag.p + B);
+        enqueue_cold(h, ColdPass::Filtered, kr, a, B);
       }
       hipLaunchKernelGGL(ddmpc_gain_column_kernel, dim3(gg), dim3(256), 0, h->stream, (long long)B, k.r, k.rE, nrhs, j,
                          (const double*)h->d_beta.p, (double*)h->d_gain.p,
@@ -2386,8 +2385,8 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   if (!warm) {
     if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
     if (warm_box && (rc = h->d_need.ensure(B * sizeof(int)))) return rc;
-    // AUTO refinement flags of launch_cold: sized (and cleared once) before a capture starts
-    if (select_route(h) == Route::Cold && (rc = ensure_rflag(h))) return rc;
+    // what launch_cold allocates or sets: sized before a capture starts
+    if (select_route(h) == Route::Cold && (rc = reserve_cold(h, true, true))) return rc;
   }
   if (use_graph && hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
     (void)hipGetLastError();                          // e.g. a caller-provided legacy stream: launch the steps directly

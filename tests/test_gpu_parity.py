@@ -1035,16 +1035,19 @@ def test_noise_free_data(gpu):
 
 def test_closed_loop_graph_replay_matches_direct_launches(gpu):
     # the per-step paths (slack box: warm + filtered cold + plant; forced cold: cold + plant) are recorded into a
-    # HIP graph and replayed; results must be identical to launching the same kernels one by one
+    # HIP graph and replayed; results must be identical to launching the same kernels one by one.  The last case is a
+    # trajectory beyond the LDS (slack box, AUTO refinement, as in test_trajectories_beyond_the_lds): the streamed residual
+    # check of its filtered cold launches needs its buffers and the Hankel kernel's LDS limit before the capture starts
     B, n_steps = 32, 45
-    d = generate_batch(range(200, 200 + B))
     w = 0.002 * np.random.default_rng(4).uniform(-1.0, 1.0, (B, n_steps, 2))
-    up = d["u_d"][:, -4:, :].reshape(B, -1); yp = d["y_d"][:, -4:, :].reshape(B, -1)
     P = orc.FOUR_TANK
-    for kw, path in ((dict(slack_var_constraint_type=1), "auto"), (dict(), "cold")):
+    for kw, path, N in ((dict(slack_var_constraint_type=1), "auto", 400), (dict(), "cold", 400),
+                        (dict(slack_var_constraint_type=1), "auto", 6000)):
+        d = generate_batch(range(200, 200 + B), N=N)
+        up = d["u_d"][:, -4:, :].reshape(B, -1); yp = d["y_d"][:, -4:, :].reshape(B, -1)
         spec = orc.spec_from_params(**kw)
         out = {}
-        with _engine(spec, 400, B) as eng:
+        with _engine(spec, N, B) as eng:
             eng.set_data(d["u_d"], d["y_d"])
             eng.set_closed_loop_path(path)
             for graph in (True, False):
