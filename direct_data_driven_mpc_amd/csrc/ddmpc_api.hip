@@ -160,6 +160,38 @@ enum class Route {
 // solve on the factors ddmpc_prepare kept (ddmpc_step).  The values are the template argument of the one-workgroup kernels.
 enum class Stage { Solve = 0, Factors = 1, OnFactors = 2 };
 
+// What ddmpc_get_solution may read: the record of the last call that wrote solve outputs (ddmpc_solve, ddmpc_solve_from_host,
+// ddmpc_step, ddmpc_closed_loop).  Each of them sets it whole (begin_solve ... end_solve); ddmpc_get_solution makes it current.
+enum class BetaState {
+  Written,          // beta / active set of the last solve are in the workspace
+  ReSolveCold,      // a cold solve skipped them: solve once more at the same past window
+  ReEvalLaw,        // a warm step skipped them: evaluate the affine law once more
+};
+enum class XState {
+  Written,          // x = L^-T w of the NOMINAL rescue is in the workspace (or not needed)
+  FromW,            // ... is still to be formed from the final w the phase solve kept
+  ReSolveOnFactors, // a step on the NOMINAL affine law kept no w: solve once more on the route's factors
+};
+struct LastSolve {
+  bool valid = false;
+  Route route = Route::Cold;               // the route that served it (Cold until the first solve)
+  const double *up = nullptr, *yp = nullptr;   // the past window of the reconstruction and of any re-solve
+  BetaState beta = BetaState::Written;
+  bool rescue = false;                     // z / x / flags of the NOMINAL rescue kernel are current
+  XState x = XState::Written;
+};
+
+// What ddmpc_prepare kept; it serves the route it was formed on only (prep_valid).
+struct Prep {
+  bool valid = false;
+  Route route = Route::Cold;
+  bool law = false;                        // beyond 271 rows: the affine law was formed (DDMPC_OPT_LARGE_AFFINE_LAW)
+  int r3_nolaw = 0;                        // ... ROBUST: instances whose law missed the refinement threshold (their steps take the filtered re-solve)
+  int cwl_nbox = 0;                        // DDMPC_OPT_CONVEX_WARM_LAW: boxed components
+  int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch)
+  int epoch = 0;                           // stamp of the flags recorded by the factor-export launch (AUTO)
+};
+
 struct ddmpc_handle {
   ddmpc_params prm{};
   std::vector<double> Qh, Rh, us_h, ys_h;
@@ -171,7 +203,9 @@ struct ddmpc_handle {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   hipStream_t copy_stream = nullptr;      // uploads of ddmpc_solve_from_host, overlapped with the solves on `stream`
-  bool have_data = false, solved = false;
+  bool have_data = false;
+  LastSolve last;
+  Prep prep;
   // parameter tables on device
   DevBuf d_tabd, d_tabi, d_dmat;
   // data (owned copies when the caller passed host memory)
@@ -191,9 +225,6 @@ struct ddmpc_handle {
   DevBuf d_rr2v, d_rr2zp, d_rr2sc, d_wz;   // ... vectors, Hankel partial sums and scalars of the solve (ddmpc_rr2_solve.hpp); weights / targets
   DevBuf d_gz, d_gres, d_zvirt;            // ... the affine law z(past) and the residuals of the dependent fixed rows (DDMPC_OPT_LARGE_AFFINE_LAW)
   int large_affine = 0;                    // DDMPC_OPT_LARGE_AFFINE_LAW
-  bool large_gain_ready = false;           // ... the law of the current data set has been formed (ddmpc_prepare)
-  bool gain_step_last = false;             // ... the last solve was a step on the law (no w to form alpha from)
-  bool rr2_x_pending = false;              // ... x = L^-T w of the last solve has not been formed yet (ddmpc_get_solution does it on demand)
   DevBuf d_rr2mt;                          // ... Minv of every 64 x 64 diagonal block of the two factors (ddmpc_rr2.hpp)
   DevBuf d_rr3w, d_rr3k, d_rr_fb, d_rrmeta_fb;   // ROBUST beyond 271 rows on the phase kernels (ddmpc_rr3.hpp): W + the k x k factor, the per-instance
                                           // ints; workspace / record of the fall-back (ddmpc_large_solve_kernel on instances marked 5)
@@ -201,7 +232,6 @@ struct ddmpc_handle {
   DevBuf d_r3y, d_r3res, d_r3zp, d_r3flag; // ... DDMPC_OPT_LARGE_AFFINE_LAW (ddmpc_rr3_law.hpp; the law itself in d_gz): substitution
                                           //   vectors, residuals and Hankel sums of a chunk of instances; [no law | re-solve | refine] flags,
                                           //   then the re-solve flags again as Rr2Solve::si (2 ints per instance)
-  int r3_nolaw = 0;                       // ... instances whose law missed the refinement threshold (their steps take the filtered re-solve)
   DevBuf d_gpre;                          // Gram tiles of ddmpc_gram_tiles_kernel (structured Gram, m + p != 4), see gram_pre_launch
   bool gram_pre = false, gpre_valid = false;
   int gram_launch = 0;                     // DDMPC_OPT_GRAM_LAUNCH: 0 streaming matrix-pipe kernel (rr2_gram_tiles*_kernel), 1 ddmpc_gram_tiles_kernel
@@ -220,28 +250,17 @@ struct ddmpc_handle {
   int convex_update = 1;                        // DDMPC_OPT_CONVEX_UPDATE: active-set iterations keep the first factor (rank-k update)
   int convex_warm = 0;                     // DDMPC_OPT_CONVEX_WARM_LAW: warm steps under the slack box run the active-set iteration on the law
   DevBuf d_mcol, d_cwl_tab, d_cwl_sg, d_cwl_ref;   // ... M = K0^-1 E_box [batch][nbox][r]; [box_rho | box_of]; k x k scratch; refined-law flags (+ count)
-  int cwl_nbox = 0;                        // ... boxed components
-  int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch)
-  bool rescue_ran = false;
   int epoch = 0;                           // cold launches so far (KParams::epoch)
-  int prep_epoch = 0;                      // stamp of the flags recorded by ddmpc_prepare's factor-export launch (AUTO)
   int flag_epoch = 0;                      // latest stamp written into d_rflag
-  bool ws_stale = false;                   // the last solve was a cold solve that skipped the beta / active-set workspace                 // the last solve launched the rescue kernel (its flags are current)
   HostBuf h_io;
   HostBuf h_flag;                          // one pinned word: the "factor again" count of the rank decision (launch_rr2_factors)
   hipEvent_t ev_flag = nullptr;            // ... and the event behind its copy
-  bool prepared = false;
-  Route prep_route = Route::Cold;          // the route ddmpc_prepare formed what it kept on (it serves no other)
-  Route solve_route = Route::Cold;         // the route of the last solve or step (Cold until the first one)
   int closed_loop_path = DDMPC_PATH_AUTO;
   bool closed_loop_graph = false;
   bool large = false;                      // r beyond the register-resident cold kernels: global-workspace kernels only
   bool large_nominal = false;              // ... NOMINAL (the rank-revealing kernels); else ROBUST
   int n_free = 0;                          // weighted (free) components, nominal scheme: rows of the reduced normal matrix
   bool stamps_on = false;                  // ddmpc_debug_stamps (the phase kernels carry no stamps)
-  bool beta_stale = false;                 // the last solve was a warm step that skipped the beta / active-set workspace
-  const double* last_up = nullptr;
-  const double* last_yp = nullptr;
 };
 
 // The one decision of which implementation serves a handle.  Beyond the register-resident kernels the phase kernels take
@@ -257,7 +276,14 @@ static Route select_route(const ddmpc_handle* h) {
 static bool nominal_route(Route r) { return r == Route::NominalPhases || r == Route::NominalOneWg; }
 
 // What ddmpc_prepare kept is the input of the route it was formed on only (the routes keep different things next to the factors).
-static bool prep_valid(const ddmpc_handle* h) { return h->prepared && h->prep_route == select_route(h); }
+static bool prep_valid(const ddmpc_handle* h) { return h->prep.valid && h->prep.route == select_route(h); }
+
+// Forget what ddmpc_prepare kept (the data, the weights or an option it was formed with changed).
+static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; }
+
+// A call that writes solve outputs starts the record afresh (nothing of an earlier call survives) and makes it readable at its end.
+static Route begin_solve(ddmpc_handle* h, Route route) { h->last = LastSolve{}; h->last.route = route; return route; }
+static void end_solve(ddmpc_handle* h, const double* up, const double* yp) { h->last.up = up; h->last.yp = yp; h->last.valid = true; }
 
 extern "C" {
 
@@ -808,9 +834,8 @@ int ddmpc_set_data(ddmpc_handle* h, const double* u_d, const double* y_d, int me
     return fail(DDMPC_ERR_INVALID, "mem must be DDMPC_MEM_HOST or DDMPC_MEM_DEVICE");
   }
   h->have_data = true;
-  h->solved = false;
-  h->prepared = false;
-  h->large_gain_ready = false;
+  h->last.valid = false;
+  forget_prep(h);
   h->gpre_valid = false;
   return DDMPC_OK;
 }
@@ -1088,9 +1113,9 @@ static int launch_rr3_law_build(ddmpc_handle* h) {
   std::vector<int> nl(B);
   HIP_TRY(hipMemcpyAsync(nl.data(), nolaw, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  h->r3_nolaw = 0;
-  for (size_t i = 0; i < B; ++i) h->r3_nolaw += nl[i] != 0;
-  h->large_gain_ready = true;
+  h->prep.r3_nolaw = 0;
+  for (size_t i = 0; i < B; ++i) h->prep.r3_nolaw += nl[i] != 0;
+  h->prep.law = true;
   return DDMPC_OK;
 }
 
@@ -1110,7 +1135,7 @@ static int launch_rr3_law_step(ddmpc_handle* h, const double* up, const double* 
                      (const double*)h->d_gz.p, nolaw, up, yp, uo, cost, (int*)status, (int*)iters, (double*)h->d_beta.p,
                      (signed char*)h->d_act.p, need, si);
   HIP_TRY(hipGetLastError());
-  if (k.convex || h->r3_nolaw > 0) return launch_rr3_solve(h, k, up, yp, uo, cost, status, iters, need, si);
+  if (k.convex || h->prep.r3_nolaw > 0) return launch_rr3_solve(h, k, up, yp, uo, cost, status, iters, need, si);
   return DDMPC_OK;
 }
 
@@ -1119,12 +1144,11 @@ static int launch_rr3_law_step(ddmpc_handle* h, const double* up, const double* 
 static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const double* up, const double* yp, double* uo,
                                double* cost, int32_t* status, int32_t* iters) {
   int rc;
-  h->beta_stale = h->rescue_ran = h->ws_stale = false;
   if (route == Route::RobustPhases) {
     // lock-step factorisation of the whole batch, then one workgroup per instance that streams the factor twice and runs the
     // active-set iterations on its trailing block
     if (stage != Stage::OnFactors && (rc = launch_rr3_factors(h))) return rc;
-    if (stage == Stage::OnFactors && h->large_affine && h->large_gain_ready) return launch_rr3_law_step(h, up, yp, uo, cost, status, iters);
+    if (stage == Stage::OnFactors && h->large_affine && h->prep.law) return launch_rr3_law_step(h, up, yp, uo, cost, status, iters);
     if (stage != Stage::Factors && (rc = launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters))) return rc;
     return DDMPC_OK;
   }
@@ -1242,9 +1266,7 @@ static int launch_cold(ddmpc_handle* h, const double* up, const double* yp, doub
                        int32_t* iters, const ColdSeq& s = ColdSeq()) {
   int rc;
   const size_t B = (size_t)h->batch;
-  h->beta_stale = h->rescue_ran = false;
   const bool ws = s.want_ws || h->long_data;       // (the streamed residual check reads beta and the active set)
-  h->ws_stale = !ws;
   // Refinement (DDMPC_OPT_REFINE).  OFF / factor export / nominal scheme (z = t does not depend on beta): plain kernel.
   // ALWAYS: the kernel variant with the refinement loop.  AUTO: plain kernel, which checks every instance's solve with
   // the exact-Hankel residual and flags the ones above the threshold; those alone are solved again (refine_flagged).  The
@@ -1272,7 +1294,7 @@ static int launch_cold(ddmpc_handle* h, const double* up, const double* yp, doub
   } else {
     if (export_flags) {
       a.flag = (int*)h->d_rflag.p; a.count = a.flag + B;
-      kq.epoch = h->prep_epoch = h->flag_epoch = next_refine_epoch(h);
+      kq.epoch = h->prep.epoch = h->flag_epoch = next_refine_epoch(h);
     }
     enqueue_cold(h, ColdPass::Plain, kq, a, B);
   }
@@ -1293,18 +1315,16 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
     // DDMPC_OPT_CONVEX_WARM_LAW: the whole active-set iteration on the law and M; only instances whose law came from refining
     // solves and leaves the box go to the filtered cold launch (none unless ddmpc_prepare refined some)
     int* need = nullptr;
-    if (h->cwl_nref > 0) {
+    if (h->prep.cwl_nref > 0) {
       if ((rc = h->d_need.ensure((size_t)h->batch * sizeof(int)))) return rc;
       need = (int*)h->d_need.p;
     }
     hipLaunchKernelGGL(ddmpc_warm_convex_step_kernel, dim3((unsigned)h->batch), dim3(threads), 0, h->stream, h->kp,
                        16 * h->kc.NT, nf, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo, cost,
-                       (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->cwl_nbox,
+                       (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox,
                        (const int*)h->d_cwl_tab.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
                        need ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, need);
     HIP_TRY(hipGetLastError());
-    h->beta_stale = false;
-    h->ws_stale = false;
     ColdSeq s; s.only = need;
     return need ? launch_cold(h, up, yp, uo, cost, status, iters, s) : DDMPC_OK;
   }
@@ -1321,8 +1341,7 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
                      (int*)status, (int*)iters, keep ? (double*)h->d_beta.p : (double*)nullptr,
                      keep ? (signed char*)h->d_act.p : (signed char*)nullptr, need);
   HIP_TRY(hipGetLastError());
-  h->beta_stale = !keep;
-  h->ws_stale = false;
+  if (!keep) h->last.beta = BetaState::ReEvalLaw;
   // instances with an active slack bound: full active-set solve, same launch geometry, others exit at once
   ColdSeq s; s.only = need;
   return need ? launch_cold(h, up, yp, uo, cost, status, iters, s) : DDMPC_OK;
@@ -1367,7 +1386,7 @@ static int launch_nominal_rescue(ddmpc_handle* h, Route route, const double* up,
     if (rcz) return rcz;
     // (a factors-only launch writes neither z_ws, x_ws nor the flags: what the previous solve left there stays readable by
     //  ddmpc_get_solution, so the flags must not be cleared -- ddmpc_solve -> ddmpc_prepare -> ddmpc_get_solution)
-    if (stage != Stage::Factors || !h->rescue_ran)
+    if (stage != Stage::Factors || !h->last.rescue)
       HIP_TRY(hipMemsetAsync(h->d_resc.p, 0, (size_t)h->batch * sizeof(int), h->stream));
   }
   // rank tolerance 1e-8 (relative to the largest diagonal entry of the Gram): with the fixed-first ordering the
@@ -1398,14 +1417,16 @@ static int launch_nominal_rescue(ddmpc_handle* h, Route route, const double* up,
     if (stage != Stage::OnFactors) rcl = phases ? launch_rr2_factors(h, scratch, (long long)ndbl, 1e-8)
                                                 : (wide ? launch(ddmpc_nominal_rr_wide_kernel<1>) : launch(ddmpc_nominal_rr_kernel<1>));
     if (!rcl && stage != Stage::Factors) {
-      h->rr2_x_pending = false;
       rcl = phases ? launch_rr2_solve(h, scratch, (long long)ndbl, up, yp, uo, cost, status, iters, 1e-7)
                    : (wide ? launch(ddmpc_nominal_rr_wide_kernel<2>) : launch(ddmpc_nominal_rr_kernel<2>));
       if (!rcl && phases && h->kp.refine_max > 1 && !wdense) rcl = launch(ddmpc_nominal_rr_kernel<2>);      // the instances the phase solve marked 4 (more passes)
     }
   }
   if (rcl) return rcl;
-  if (stage != Stage::Factors) h->rescue_ran = true;
+  if (stage != Stage::Factors) {          // (the phase solve keeps w: x = L^-T w is formed on demand)
+    h->last.rescue = true;
+    h->last.x = scratch && route == Route::NominalPhases ? XState::FromW : XState::Written;
+  }
   return DDMPC_OK;
 }
 
@@ -1590,10 +1611,7 @@ static int launch_rr2_solve(ddmpc_handle* h, double* scratch, long long ndbl, co
   Rr2Solve S;
   int rc = rr2_solve_desc(h, scratch, ndbl, &S);
   if (rc) return rc;
-  if ((rc = rr2_solve_sequence(h, S, (unsigned)h->batch, up, yp, uo, cost, status, iters, (double*)h->d_zws.p, (int*)h->d_resc.p, feas_tol)))
-    return rc;
-  h->rr2_x_pending = true;
-  return DDMPC_OK;
+  return rr2_solve_sequence(h, S, (unsigned)h->batch, up, yp, uo, cost, status, iters, (double*)h->d_zws.p, (int*)h->d_resc.p, feas_tol);
 }
 
 // DDMPC_OPT_LARGE_AFFINE_LAW: the affine law z(past) of every instance (ddmpc_rr2_solve.hpp), formed by ddmpc_prepare from solves at
@@ -1609,7 +1627,7 @@ static int launch_rr2_gain_build(ddmpc_handle* h, double* scratch, long long ndb
   if ((rc = h->d_gz.ensure(B * (size_t)nrhs * k.r * sizeof(double))) || (rc = h->d_gres.ensure(B * (size_t)nrhs * nFp * sizeof(double))) ||
       (rc = h->d_zvirt.ensure(Bv * (size_t)k.rE * sizeof(double))))
     return rc;
-  if (h->rr2_x_pending) {
+  if (h->last.x == XState::FromW) {
     // the virtual-batch solves below reuse (and re-size) the vectors the last solve kept for the on-demand x = L^-T w of
     // ddmpc_get_solution(ALPHA): form x now (ddmpc_solve -> ddmpc_prepare -> ddmpc_get_solution)
     Rr2Solve S0;
@@ -1617,7 +1635,7 @@ static int launch_rr2_gain_build(ddmpc_handle* h, double* scratch, long long ndb
     if ((rc = h->d_xws.ensure(B * (size_t)k.rE * sizeof(double)))) return rc;
     hipLaunchKernelGGL(rr2_xws_kernel, dim3((unsigned)B), dim3(RR2_TS), 0, h->stream, S0, k, (double*)h->d_xws.p);
     HIP_TRY(hipGetLastError());
-    h->rr2_x_pending = false;
+    h->last.x = XState::Written;
   }
   Rr2Solve S;
   if ((rc = rr2_solve_desc(h, scratch, ndbl, &S, Bv))) return rc;
@@ -1633,15 +1651,14 @@ static int launch_rr2_gain_build(ddmpc_handle* h, double* scratch, long long ndb
   hipLaunchKernelGGL(rr2_gain_finish_kernel, dim3((unsigned)((tz + 255) / 256)), dim3(256), 0, h->stream, (long long)B, nrhs, k.r, (double*)h->d_gz.p);
   hipLaunchKernelGGL(rr2_gain_finish_kernel, dim3((unsigned)((tr + 255) / 256)), dim3(256), 0, h->stream, (long long)B, nrhs, nFp, (double*)h->d_gres.p);
   HIP_TRY(hipGetLastError());
-  h->large_gain_ready = true;
+  h->prep.law = true;
   return DDMPC_OK;
 }
 
 // NOMINAL controller beyond the register-resident kernels, warm: a solve on the factors ddmpc_prepare left in the workspace
 static int launch_large_nominal_warm(ddmpc_handle* h, Route route, const double* up, const double* yp, double* uo, double* cost,
                                      int32_t* status, int32_t* iters) {
-  h->beta_stale = h->ws_stale = h->gain_step_last = false;
-  if (h->large_gain_ready && h->large_affine) {                        // the affine law of ddmpc_prepare: one HBM-bound launch
+  if (h->prep.law && h->large_affine) {                                // the affine law of ddmpc_prepare: one HBM-bound launch
     const KParams& k = h->kp;
     const int nf = h->prm.n * k.nch, nFp = (h->nF + 63) & ~63;
     int rcz = h->d_zws.ensure((size_t)h->batch * k.rE * sizeof(double));
@@ -1651,9 +1668,8 @@ static int launch_large_nominal_warm(ddmpc_handle* h, Route route, const double*
                        (const double*)h->d_gz.p, (const double*)h->d_gres.p, up, yp, uo, cost, (int*)status, (int*)iters,
                        (double*)h->d_zws.p, (int*)h->d_resc.p, 1e-7);
     HIP_TRY(hipGetLastError());
-    h->rescue_ran = true;
-    h->rr2_x_pending = false;
-    h->gain_step_last = true;
+    h->last.rescue = true;
+    h->last.x = XState::ReSolveOnFactors;
     return DDMPC_OK;
   }
   return launch_nominal_rescue(h, route, up, yp, uo, cost, status, iters, Stage::OnFactors);
@@ -1662,21 +1678,23 @@ static int launch_large_nominal_warm(ddmpc_handle* h, Route route, const double*
 // A cold solve of the whole batch on the handle's route (ddmpc_solve, the cold closed loop).
 static int solve_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                           int32_t* iters) {
-  const Route route = h->solve_route = select_route(h);
-  if (route != h->prep_route) h->prepared = false;              // (its workspace is the one ddmpc_prepare kept things in)
+  const Route route = begin_solve(h, select_route(h));
+  if (route != h->prep.route) forget_prep(h);                   // (its workspace is the one ddmpc_prepare kept things in)
   if (route == Route::RobustPhases || route == Route::RobustOneWg)
     return launch_large_robust(h, route, Stage::Solve, up, yp, uo, cost, status, iters);
   int rc = DDMPC_OK;
-  ColdSeq s; s.want_ws = false;
-  if (route == Route::Cold) rc = launch_cold(h, up, yp, uo, cost, status, iters, s);
-  else h->beta_stale = h->rescue_ran = h->ws_stale = false;        // (no cold kernel at this size: the rescue is the solve)
+  if (route == Route::Cold) {           // (beyond 271 rows no cold kernel: the rescue is the solve)
+    ColdSeq s; s.want_ws = false;
+    rc = launch_cold(h, up, yp, uo, cost, status, iters, s);
+    if (!h->long_data) h->last.beta = BetaState::ReSolveCold;   // (beyond the LDS the streamed residual check wrote them)
+  }
   return rc ? rc : launch_nominal_rescue(h, route, up, yp, uo, cost, status, iters);
 }
 
 // A control step on what ddmpc_prepare kept (ddmpc_step, the per-step closed loop): the callers have prepared on this route.
 static int step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                          int32_t* iters) {
-  const Route route = h->solve_route = select_route(h);
+  const Route route = begin_solve(h, select_route(h));
   if (route == Route::RobustPhases || route == Route::RobustOneWg)
     return launch_large_robust(h, route, Stage::OnFactors, up, yp, uo, cost, status, iters);
   if (route != Route::Cold) return launch_large_nominal_warm(h, route, up, yp, uo, cost, status, iters);
@@ -1700,9 +1718,7 @@ static int solve_impl(ddmpc_handle* h, const double* u_past, const double* y_pas
   int rc;
   if (mem == DDMPC_MEM_DEVICE) {
     if ((rc = launch(h, u_past, y_past, u_opt, cost, status, iters))) return rc;
-    h->last_up = u_past;
-    h->last_yp = y_past;
-    h->solved = true;
+    end_solve(h, u_past, y_past);
     return DDMPC_OK;
   }
   if (mem != DDMPC_MEM_HOST) return fail(DDMPC_ERR_INVALID, "mem must be DDMPC_MEM_HOST or DDMPC_MEM_DEVICE");
@@ -1727,9 +1743,7 @@ static int solve_impl(ddmpc_handle* h, const double* u_past, const double* y_pas
   memcpy(cost, hb + o_cost, B * sizeof(double));
   memcpy(status, hb + o_st, B * sizeof(int32_t));
   if (iters) memcpy(iters, hb + o_it, B * sizeof(int32_t));
-  h->last_up = (const double*)(db + o_up);
-  h->last_yp = (const double*)(db + o_yp);
-  h->solved = true;
+  end_solve(h, (const double*)(db + o_up), (const double*)(db + o_yp));
   return DDMPC_OK;
 }
 
@@ -1772,9 +1786,7 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
     (void)hipEventDestroy(ev0);
     if (e0 != hipSuccess) return fail(DDMPC_ERR_HIP, "ddmpc_solve_from_host: %s", hipGetErrorString(e0));
   }
-  h->beta_stale = false;
-  h->rescue_ran = false;
-  h->ws_stale = true;
+  begin_solve(h, Route::Cold);
   HIP_TRY(hipMemcpyAsync(dup, u_past, B * sup * sizeof(double), hipMemcpyHostToDevice, h->copy_stream));
   HIP_TRY(hipMemcpyAsync(dyp, y_past, B * syp * sizeof(double), hipMemcpyHostToDevice, h->copy_stream));
   // chunks of instances: upload chunk k+1 on the copy stream while chunk k is being solved on the compute stream
@@ -1787,7 +1799,7 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
   const bool refinable = h->kp.lam != 0.0;
   const bool always = refinable && h->kp.refine == DDMPC_REFINE_ALWAYS, autoref = refinable && h->kp.refine == DDMPC_REFINE_AUTO;
   if ((rc = reserve_cold(h, h->long_data, autoref))) return rc;
-  if (h->long_data) h->ws_stale = false;
+  if (!h->long_data) h->last.beta = BetaState::ReSolveCold;
   KParams kchunk = h->kp;
   kchunk.epoch = next_refine_epoch(h);
   h->flag_epoch = kchunk.epoch;
@@ -1813,7 +1825,12 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
     h->ud = dud; h->yd = dyd;
     rcl = gram_pre_launch(h, kchunk, dud, dyd, B, 0, true);
   }
-  if (rcl == DDMPC_OK && autoref) rcl = refine_flagged(h, kchunk, ColdArgs{dud, dyd, dup, dyp, duo, dco, dst, dit});
+  if (rcl == DDMPC_OK && autoref) {
+    ColdArgs a{dud, dyd, dup, dyp, duo, dco, dst, dit};
+    // the chunks wrote beta / active set: the refining pass corrects those of the instances it refines (as in launch_cold)
+    if (h->last.beta == BetaState::Written) { a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p; }
+    rcl = refine_flagged(h, kchunk, a);
+  }
   if (rcl == DDMPC_OK) {            // NOMINAL on exact data: same rank-revealing rescue as ddmpc_solve (all chunks are uploaded
     h->ud = dud; h->yd = dyd;       // and solved by now in stream order)
     rcl = launch_nominal_rescue(h, Route::Cold, dup, dyp, duo, dco, dst, dit);
@@ -1831,9 +1848,8 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
   if (rcl != DDMPC_OK) return rcl;
   h->ud = dud; h->yd = dyd;
   h->have_data = true;
-  h->prepared = false;
-  h->last_up = dup; h->last_yp = dyp;
-  h->solved = true;
+  forget_prep(h);
+  end_solve(h, dup, dyp);
   return DDMPC_OK;
 }
 
@@ -1844,26 +1860,24 @@ int ddmpc_prepare(ddmpc_handle* h) {
   if (prep_valid(h)) return DDMPC_OK;
   h->gpre_valid = false;
   const Route route = select_route(h);
-  h->prepared = false;                    // (until the route's preparation below has been queued in full)
-  h->prep_route = route;
+  forget_prep(h);                         // (until the route's preparation below has been queued in full)
+  h->prep.route = route;
   HIP_TRY(hipSetDevice(h->device));
   if (nominal_route(route)) {
     // no affine law at this size, but everything that depends on the data alone -- Gram, its rank-revealing factor, the
     // reduced normal matrix and its factor, 70 % of a solve -- is formed once and kept in the workspace; ddmpc_step and
     // the per-step closed loop then only redo the substitutions and the refinement passes
     int rc = h->d_prep_status.ensure((size_t)h->batch * sizeof(int32_t));
-    h->large_gain_ready = false;
     if (!rc) rc = launch_nominal_rescue(h, route, h->ud, h->yd, nullptr, nullptr, (int32_t*)h->d_prep_status.p, nullptr, Stage::Factors);
     if (!rc && h->large_affine && route == Route::NominalPhases && h->d_rr.p) rc = launch_rr2_gain_build(h, (double*)h->d_rr.p, rr2_ndbl(h));
-    h->prepared = rc == DDMPC_OK;
+    h->prep.valid = rc == DDMPC_OK;
     return rc;
   }
   if (route != Route::Cold) {             // ROBUST at this size: Gram + lam D, the factor of the columns outside the slack box and
                                           // the Schur complement of the boxed block are formed once and kept
-    h->large_gain_ready = false;
     int rc = launch_large_robust(h, route, Stage::Factors, h->ud, h->yd, nullptr, nullptr, nullptr, nullptr);
     if (!rc && h->large_affine && route == Route::RobustPhases) rc = launch_rr3_law_build(h);   // ... and the affine law on that factor
-    h->prepared = rc == DDMPC_OK;
+    h->prep.valid = rc == DDMPC_OK;
     return rc;
   }
   const ddmpc_params& p = h->prm;
@@ -1872,6 +1886,7 @@ int ddmpc_prepare(ddmpc_handle* h) {
   if (nf > WARM_MAX_NF) return fail(DDMPC_ERR_UNSUPPORTED, "warm path supports n*(m+p) <= %d", WARM_MAX_NF);
   const size_t B = (size_t)h->batch;
   const size_t lf_bytes = B * (size_t)(NT * (NT + 1) / 2) * 256 * sizeof(double);
+  h->last.valid = false;                           // (the launches below overwrite the outputs and the workspace of the last solve)
   int rc;
   if ((rc = h->d_lfac.ensure(lf_bytes)) || (rc = h->d_lfacT.ensure(lf_bytes)) || (rc = h->d_gain.ensure(B * nrhs * k.r * sizeof(double))) ||
       (rc = h->d_prep_status.ensure(B * sizeof(int32_t))) || (rc = h->d_zero.ensure(B * nf * sizeof(double))) ||
@@ -1898,13 +1913,13 @@ int ddmpc_prepare(ddmpc_handle* h) {
                        (long long)B, p.N, p.m, p.p, p.n, h->ud, h->yd, pu, py);
     HIP_TRY(hipMemsetAsync(h->d_need.p, 0, (B + 1) * sizeof(int), h->stream));
     KParams kprobe = k0;
-    kprobe.epoch = h->prep_epoch;
+    kprobe.epoch = h->prep.epoch;
     if ((rc = gram_pre_launch(h, kprobe, h->ud, h->yd, B, 0, true))) return rc;
     ColdArgs a{h->ud, h->yd, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p};
     a.flag = (int*)h->d_need.p; a.count = a.flag + B;
     enqueue_cold(h, ColdPass::Plain, kprobe, a, B);       // (k0: no slack box, so the plain kernel fn2)
     hipLaunchKernelGGL(ddmpc_or_flags_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, (long long)B,
-                       h->prep_epoch, (const int*)h->d_need.p, (int*)h->d_rflag.p);
+                       h->prep.epoch, (const int*)h->d_need.p, (int*)h->d_rflag.p);
     HIP_TRY(hipGetLastError());
   }
   const size_t ntiles = B * (size_t)(NT * (NT + 1) / 2);
@@ -1929,7 +1944,7 @@ int ddmpc_prepare(ddmpc_handle* h) {
     HIP_TRY(hipMemcpy(h->d_cwl_tab.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(h->d_cwl_ref.p, 0, (B + 1) * sizeof(int), h->stream));
   }
-  h->cwl_nbox = nbox;
+  h->prep.cwl_nbox = nbox;
   bool launched = false;
 #define DDMPC_INSTANCE(NT_, W_)                                                                              \
   if (!launched && NT == NT_) {                                                                               \
@@ -1969,13 +1984,13 @@ int ddmpc_prepare(ddmpc_handle* h) {
           return rc;
       } else {
         // (trajectory beyond the LDS: the flags are those of the a-priori bound alone, no streamed check)
-        kr.epoch = h->prep_epoch;
+        kr.epoch = h->prep.epoch;
         if ((rc = gram_pre_launch(h, kr, h->ud, h->yd, B, 0, true))) return rc;
         enqueue_cold(h, ColdPass::Filtered, kr, a, B);
       }
       hipLaunchKernelGGL(ddmpc_gain_column_kernel, dim3(gg), dim3(256), 0, h->stream, (long long)B, k.r, k.rE, nrhs, j,
                          (const double*)h->d_beta.p, (double*)h->d_gain.p,
-                         flagged_only ? (const int*)h->d_rflag.p : (const int*)nullptr, h->prep_epoch);
+                         flagged_only ? (const int*)h->d_rflag.p : (const int*)nullptr, h->prep.epoch);
     }
     HIP_TRY(hipGetLastError());
   }
@@ -1984,16 +1999,15 @@ int ddmpc_prepare(ddmpc_handle* h) {
     // (ddmpc_step), and their presence sends ddmpc_closed_loop to the per-step path
     const int mode = (k.lam != 0.0) ? k.refine : DDMPC_REFINE_OFF;
     hipLaunchKernelGGL(ddmpc_cwl_mark_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, (long long)B, mode,
-                       h->prep_epoch, (const int*)h->d_rflag.p, (int*)h->d_cwl_ref.p);
+                       h->prep.epoch, (const int*)h->d_rflag.p, (int*)h->d_cwl_ref.p);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
-  h->cwl_nref = 0;
-  if (cwl) HIP_TRY(hipMemcpy(&h->cwl_nref, (const int*)h->d_cwl_ref.p + B, sizeof(int), hipMemcpyDeviceToHost));
+  h->prep.cwl_nref = 0;
+  if (cwl) HIP_TRY(hipMemcpy(&h->prep.cwl_nref, (const int*)h->d_cwl_ref.p + B, sizeof(int), hipMemcpyDeviceToHost));
   h->d_lfac.release();                           // the factor is only needed to form the gain
   h->d_lfacT.release();
-  h->prepared = true;
-  h->solved = false;
+  h->prep.valid = true;
   return DDMPC_OK;
 }
 
@@ -2012,7 +2026,7 @@ int ddmpc_get_gain(ddmpc_handle* h, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
   if (h->large && !h->large_affine)
     return fail(DDMPC_ERR_UNSUPPORTED, "no affine law at this problem size without DDMPC_OPT_LARGE_AFFINE_LAW");
-  if (!prep_valid(h) || (h->large && !h->large_gain_ready)) return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare must be called before ddmpc_get_gain");
+  if (!prep_valid(h) || (h->large && !h->prep.law)) return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare must be called before ddmpc_get_gain");
   HIP_TRY(hipSetDevice(h->device));
   // (beyond the register-resident kernels, NOMINAL: z = [ubar; ybar] (component order) = gain[:,0] + gain[:,1:]' [u_past; y_past];
   //  ROBUST: beta of the empty active set (component order) = gain[:,0] + gain[:,1:]' [u_past; y_past], as below 272 rows)
@@ -2038,18 +2052,18 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value != DDMPC_REFINE_OFF && value != DDMPC_REFINE_AUTO && value != DDMPC_REFINE_ALWAYS)
         return fail(DDMPC_ERR_INVALID, "refinement mode must be DDMPC_REFINE_OFF, _AUTO or _ALWAYS");
       h->kp.refine = value;
-      h->prepared = false;              // the affine law is formed from a refined solve of the offset column
+      forget_prep(h);                   // the affine law is formed from a refined solve of the offset column
       return DDMPC_OK;
     case DDMPC_OPT_REFINE_MAX:
       if (value < 1 || value > 10) return fail(DDMPC_ERR_INVALID, "refinement passes must be within [1, 10]");
       h->kp.refine_max = value;
-      if (h->large_affine) h->prepared = false;   // the ROBUST law beyond 271 rows marks "no law" after refine_max passes
+      if (h->large_affine) forget_prep(h);        // the ROBUST law beyond 271 rows marks "no law" after refine_max passes
       return DDMPC_OK;
     case DDMPC_OPT_REFINE_RES_LOG10:
       if (value < 0 || value > 3000)
         return fail(DDMPC_ERR_INVALID, "refinement threshold (tenths of a decade below 1) must be within [0, 3000]");
       h->kp.refine_res = std::pow(10.0, -0.1 * (double)value);
-      h->prepared = false;
+      forget_prep(h);
       return DDMPC_OK;
     case DDMPC_OPT_LARGE_AFFINE_LAW:
       // (the law's step kernel evaluates the cost with the diagonal weights, and the law is built by the phase kernels: 1024 rows)
@@ -2061,8 +2075,7 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
         return fail(DDMPC_ERR_UNSUPPORTED, "the affine law of ROBUST controllers beyond 271 rows takes scalar / diagonal weights, at most 1024 rows "
                     "and n*(m+p) <= %d", WARM_MAX_NF);
       h->large_affine = value != 0;
-      h->prepared = false;
-      h->large_gain_ready = false;
+      forget_prep(h);
       return DDMPC_OK;
     case DDMPC_OPT_CONVEX_UPDATE:
       h->convex_update = value != 0;
@@ -2087,7 +2100,7 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
             return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_CONVEX_WARM_LAW: a boxed output component has no weight (Q entry 0)");
       }
       h->convex_warm = value;
-      h->prepared = false;
+      forget_prep(h);
       return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
@@ -2095,7 +2108,7 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value == 0 && !h->gram_stream_ok) return fail(DDMPC_ERR_UNSUPPORTED, "the streaming Gram launch does not hold this shape");
       h->gram_launch = value;
       h->gpre_valid = false;
-      h->prepared = false;
+      forget_prep(h);
       return DDMPC_OK;
     case DDMPC_OPT_LARGE_PIPELINE:
       if (value != DDMPC_PIPELINE_ONE_WORKGROUP && value != DDMPC_PIPELINE_PHASES)
@@ -2115,45 +2128,17 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s) {
   h->ys_h.assign(y_s, y_s + h->prm.p);
   h->prm.u_s = h->us_h.data();
   h->prm.y_s = h->ys_h.data();
-  h->solved = false;
-  h->prepared = false;
-  h->large_gain_ready = false;
+  h->last.valid = false;
+  forget_prep(h);
   HIP_TRY(hipStreamSynchronize(h->stream));
   return upload_params(h);
 }
 
 int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
-  if (!h->solved) return fail(DDMPC_ERR_NOT_READY, "no solve to read a solution from");
-  HIP_TRY(hipSetDevice(h->device));
+  LastSolve& l = h->last;
+  if (!l.valid) return fail(DDMPC_ERR_NOT_READY, "no solve to read a solution from");
   const KParams& k = h->kp;
-  if (h->ws_stale) {
-    // last solve = a cold solve that skipped the workspace: solve once more at the same past window, keeping beta / active set
-    const size_t B = (size_t)h->batch;
-    int rc;
-    if ((rc = h->d_uopt.ensure(B * h->prm.L * k.m * sizeof(double))) || (rc = h->d_cost.ensure(B * sizeof(double))) ||
-        (rc = h->d_status.ensure(B * sizeof(int32_t))) || (rc = h->d_iters.ensure(B * sizeof(int32_t))))
-      return rc;
-    const bool resc0 = h->rescue_ran;
-    if ((rc = launch_cold(h, h->last_up, h->last_yp, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p,
-                          (int32_t*)h->d_iters.p)))
-      return rc;
-    h->rescue_ran = resc0;         // the rescue kernel's z / flags of the real solve stay valid
-  }
-  if (h->beta_stale) {             // last solve = warm step without the workspace: evaluate the affine law once more, keeping beta
-    const size_t B = (size_t)h->batch;
-    int rc;
-    if ((rc = h->d_uopt.ensure(B * h->prm.L * k.m * sizeof(double))) || (rc = h->d_cost.ensure(B * sizeof(double))) ||
-        (rc = h->d_status.ensure(B * sizeof(int32_t))) || (rc = h->d_iters.ensure(B * sizeof(int32_t))) ||
-        (rc = h->d_beta.ensure(B * k.rE * sizeof(double))) || (rc = h->d_act.ensure(B * k.rE)))
-      return rc;
-    hipLaunchKernelGGL(ddmpc_warm_step_kernel, dim3((unsigned)h->batch), dim3(warm_threads(k.r)), 0, h->stream, k, 16 * h->kc.NT,
-                       h->prm.n * k.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, h->last_up, h->last_yp,
-                       (double*)h->d_uopt.p, (double*)h->d_cost.p, (int*)h->d_status.p, (int*)h->d_iters.p,
-                       (double*)h->d_beta.p, (signed char*)h->d_act.p, (int*)nullptr);
-    HIP_TRY(hipGetLastError());
-    h->beta_stale = false;
-  }
   size_t per = 0;
   switch (what) {
     case DDMPC_SOL_ALPHA: per = k.c; break;
@@ -2165,40 +2150,53 @@ int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
       break;
     default: return fail(DDMPC_ERR_INVALID, "unknown solution selector %d", what);
   }
-  const size_t bytes = per * h->batch * sizeof(double);
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t B = (size_t)h->batch;
+  const bool resolve_x = what == DDMPC_SOL_ALPHA && l.x == XState::ReSolveOnFactors;
+  int rc;
+  // make the record current: beta first, then (alpha only) x; a re-solve writes its outputs into the handle's own buffers
+  if ((l.beta != BetaState::Written || resolve_x) &&
+      ((rc = h->d_uopt.ensure(B * h->prm.L * k.m * sizeof(double))) || (rc = h->d_cost.ensure(B * sizeof(double))) ||
+       (rc = h->d_status.ensure(B * sizeof(int32_t))) || (rc = h->d_iters.ensure(B * sizeof(int32_t)))))
+    return rc;
+  double *uo = (double*)h->d_uopt.p, *co = (double*)h->d_cost.p;
+  int32_t *st = (int32_t*)h->d_status.p, *it = (int32_t*)h->d_iters.p;
+  switch (l.beta) {
+    case BetaState::Written: break;
+    case BetaState::ReSolveCold:     // solve once more at the same past window, keeping beta / active set (and the rescue's output)
+      if ((rc = launch_cold(h, l.up, l.yp, uo, co, st, it))) return rc;
+      break;
+    case BetaState::ReEvalLaw:       // evaluate the affine law once more, keeping beta / active set
+      if ((rc = h->d_beta.ensure(B * k.rE * sizeof(double))) || (rc = h->d_act.ensure(B * k.rE))) return rc;
+      hipLaunchKernelGGL(ddmpc_warm_step_kernel, dim3((unsigned)B), dim3(warm_threads(k.r)), 0, h->stream, k, 16 * h->kc.NT,
+                         h->prm.n * k.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, l.up, l.yp, uo, co, (int*)st,
+                         (int*)it, (double*)h->d_beta.p, (signed char*)h->d_act.p, (int*)nullptr);
+      HIP_TRY(hipGetLastError());
+      break;
+  }
+  l.beta = BetaState::Written;
+  const size_t bytes = per * B * sizeof(double);
   double* dst = out;
   if (mem == DDMPC_MEM_HOST) {
-    int rc = h->d_out.ensure(bytes);
-    if (rc) return rc;
+    if ((rc = h->d_out.ensure(bytes))) return rc;
     dst = (double*)h->d_out.p;
   }
   // instances solved by the NOMINAL rescue kernel have no beta: ubar / ybar come from the z it exported, alpha = H' x from
   // the vector x it exported
-  if (h->large_nominal && h->gain_step_last && what == DDMPC_SOL_ALPHA) {
-    // the last solve was a step on the affine law, which keeps no w: solve once more on its route's factors at the same past window
-    const size_t B = (size_t)h->batch;
-    int rc;
-    if ((rc = h->d_uopt.ensure(B * h->prm.L * k.m * sizeof(double))) || (rc = h->d_cost.ensure(B * sizeof(double))) ||
-        (rc = h->d_status.ensure(B * sizeof(int32_t))) || (rc = h->d_iters.ensure(B * sizeof(int32_t))))
-      return rc;
-    if ((rc = launch_nominal_rescue(h, h->solve_route, h->last_up, h->last_yp, (double*)h->d_uopt.p, (double*)h->d_cost.p,
-                                    (int32_t*)h->d_status.p, (int32_t*)h->d_iters.p, Stage::OnFactors)))
-      return rc;
-    h->gain_step_last = false;
-  }
-  const bool resc = h->rescue_ran && h->d_resc.p && h->d_zws.p;
+  if (resolve_x &&                   // solve once more on the route's factors at the same past window (on the phase route: x from w)
+      (rc = launch_nominal_rescue(h, l.route, l.up, l.yp, uo, co, st, it, Stage::OnFactors)))
+    return rc;
+  const bool resc = l.rescue && h->d_resc.p && h->d_zws.p;
   if (h->large_nominal && !resc) return fail(DDMPC_ERR_NOT_READY, "no solve to read a solution from");
-  if (h->large_nominal && h->rr2_x_pending && what == DDMPC_SOL_ALPHA) {
-    // phase-kernel solve: x = L_I^-T w (alpha = H' x) is formed here, on demand, from the final w the solve kept
+  if (what == DDMPC_SOL_ALPHA && l.x == XState::FromW) {    // x = L_I^-T w (alpha = H' x) from the final w the phase solve kept
     Rr2Solve S;
-    int rcx = rr2_solve_desc(h, (double*)h->d_rr.p, rr2_ndbl(h), &S);
-    if (rcx) return rcx;
-    hipLaunchKernelGGL(rr2_xws_kernel, dim3((unsigned)h->batch), dim3(RR2_TS), 0, h->stream, S, k, (double*)h->d_xws.p);
+    if ((rc = rr2_solve_desc(h, (double*)h->d_rr.p, rr2_ndbl(h), &S))) return rc;
+    hipLaunchKernelGGL(rr2_xws_kernel, dim3((unsigned)B), dim3(RR2_TS), 0, h->stream, S, k, (double*)h->d_xws.p);
     HIP_TRY(hipGetLastError());
-    h->rr2_x_pending = false;
+    l.x = XState::Written;
   }
   hipLaunchKernelGGL(ddmpc_reconstruct_kernel, dim3((unsigned)h->batch), dim3(256), 0, h->stream, k, 16 * h->kc.NT, what, h->ud,
-                     h->yd, h->last_up, h->last_yp, (const double*)h->d_beta.p, (const signed char*)h->d_act.p, dst,
+                     h->yd, l.up, l.yp, (const double*)h->d_beta.p, (const signed char*)h->d_act.p, dst,
                      resc ? (const double*)h->d_zws.p : (const double*)nullptr, resc ? (const int*)h->d_resc.p : (const int*)nullptr,
                      resc ? (const double*)h->d_xws.p : (const double*)nullptr);
   HIP_TRY(hipGetLastError());
@@ -2351,25 +2349,24 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
     // affine control law: the whole loop of an instance runs inside one workgroup
     if ((rc = ddmpc_prepare(h))) return rc;
     if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
+    begin_solve(h, Route::Cold);
     hipLaunchKernelGGL(ddmpc_closed_loop_warm_kernel, dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
                        16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
                        (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
                        (double*)h->d_beta.p, (signed char*)h->d_act.p);
     HIP_TRY(hipGetLastError());
-    h->ws_stale = false;
   }
-  if (warm_box && convex_warm_on(h) && h->cwl_nref == 0) {
+  if (warm_box && convex_warm_on(h) && h->prep.cwl_nref == 0) {
     // DDMPC_OPT_CONVEX_WARM_LAW: the whole loop of an instance in one workgroup, active-set iterations included
     if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
+    begin_solve(h, Route::Cold);
     hipLaunchKernelGGL(ddmpc_closed_loop_convex_warm_kernel, dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
                        16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
                        (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
-                       (double*)h->d_beta.p, (signed char*)h->d_act.p, h->cwl_nbox, (const int*)h->d_cwl_tab.p,
+                       (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,
                        (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p);
     HIP_TRY(hipGetLastError());
-    h->ws_stale = false;
-    h->beta_stale = false;
-    warm = true;                                    // (no per-step launches below)
+    warm = true;                                   // (no per-step launches below)
   }
   const unsigned pblocks = (unsigned)((B + 127) / 128);
   // The per-step paths are loops of two or three small launches per control step.  Optionally
@@ -2423,9 +2420,7 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(DDMPC_ERR_HIP, "closed-loop graph: %s", hipGetErrorString(e));
   }
-  h->last_up = dup;
-  h->last_yp = dyp;
-  h->solved = true;
+  end_solve(h, dup, dyp);          // (the final window: the per-step cold path re-solves there, the fused paths wrote beta before it)
   if (mem == DDMPC_MEM_HOST) {
     HIP_TRY(hipMemcpyAsync(x, dx, nx, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(u_past, dup, nup, hipMemcpyDeviceToHost, h->stream));
@@ -2486,7 +2481,7 @@ int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws
                           int64_t* ws_avail, int64_t* meta_avail) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
   // what the last solve left, read on the route that served it
-  if (h->solve_route == Route::RobustPhases && h->d_rr3k.p) {
+  if (h->last.route == Route::RobustPhases && h->d_rr3k.p) {
     // ROBUST on the phase kernels (ddmpc_rr3.hpp): the per-instance record of the last solve --
     // [k, state, iterations, k, switched positions (RR3_KMAX), active set (rv), start tick, ticks] -- into meta_out
     const int rv = (h->kp.r + 1) & ~1;
@@ -2500,7 +2495,7 @@ int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws
       HIP_TRY(hipMemcpy(meta_out, (const int*)h->d_rr3k.p + b * kstride, (size_t)(meta_count < kstride ? meta_count : kstride) * sizeof(int), hipMemcpyDeviceToHost));
     return DDMPC_OK;
   }
-  if (!nominal_route(h->solve_route) || !h->d_rr.p || !h->d_rrmeta.p) return fail(DDMPC_ERR_NOT_READY, "no global workspace to read");
+  if (!nominal_route(h->last.route) || !h->d_rr.p || !h->d_rrmeta.p) return fail(DDMPC_ERR_NOT_READY, "no global workspace to read");
   if (ws_count < 0 && h->d_rr2cand.p) {
     // diagnostics: the pivot candidates of G's factorisation (phase kernels), n16 doubles, relative to nothing (dmax is meta's business)
     const int n16 = (h->kp.r + 15) & ~15;

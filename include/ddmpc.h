@@ -283,8 +283,10 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value);
 /* set_input_output_setpoints (controller.py:945-982); takes effect at the next solve. */
 int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
 
-/* Values of the optimisation variables after the last ddmpc_solve
- * (controller.py:434-445 `.value`); `out` sized as listed at DDMPC_SOL_*.  Instances of a NOMINAL controller that
+/* Values of the optimisation variables of the last ddmpc_solve, ddmpc_solve_from_host, ddmpc_step or ddmpc_closed_loop
+ * (controller.py:434-445 `.value`); `out` sized as listed at DDMPC_SOL_*.  DDMPC_ERR_NOT_READY before any of them and after
+ * ddmpc_set_data, ddmpc_set_setpoints or a ddmpc_prepare on the register-resident kernels ((m+p)(L+n) <= 271); a
+ * ddmpc_prepare beyond 271 rows keeps the solution readable.  Instances of a NOMINAL controller that
  * were solved by the rank-revealing rescue kernel (exact, rank-deficient data) report ubar / ybar from that kernel's
  * own solution and NaN for alpha (any alpha with H alpha = [ubar; ybar] is optimal there; none is formed). */
 int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem);

@@ -705,6 +705,20 @@ def test_closed_loop_warm_and_cold_paths_agree(gpu, kw, n_mpc_step):
     for a, b in zip(out["warm"], out["auto"]):
         assert np.array_equal(a, b)                            # AUTO picks the warm path here
     assert np.all(out["warm"][2] == 0)
+    # what ddmpc_get_solution reads after the fused loop is the loop's own, whatever a ddmpc_step before it left
+    convex = kw.get("slack_var_constraint_type") == 1
+    sol = []
+    for step_first in (False, True):
+        with _engine(spec, 400, B) as eng:
+            if convex:
+                eng.set_convex_warm_law(True)                  # (the fused loop under the slack box)
+            eng.set_data(d["u_d"], d["y_d"])
+            eng.set_closed_loop_path("warm")
+            if step_first:
+                eng.step(up, yp)
+            eng.closed_loop(P["A"], P["B"], P["C"], P["D"], d["x_end"], up, yp, w, n_mpc_step=n_mpc_step)
+            sol.append([eng.get_solution(k) for k in ("alpha", "ubar", "ybar")])
+    assert all(np.array_equal(a, b) for a, b in zip(*sol))
 
 
 # ----------------------------------------------------- device persistent-excitation guard
