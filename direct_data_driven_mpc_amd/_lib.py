@@ -39,6 +39,7 @@ EXPORTS = (
     "ddmpc_get_solution", "ddmpc_hankel", "ddmpc_cost_model", "ddmpc_kernel_name", "ddmpc_debug_stamps",
     "ddmpc_closed_loop", "ddmpc_prepare", "ddmpc_step", "ddmpc_get_gain", "ddmpc_set_option",
     "ddmpc_pe_guard", "ddmpc_solve_from_host", "ddmpc_debug_workspace", "ddmpc_debug_poison_allocations",
+    "ddmpc_closed_loop_kernel_name",
 )
 
 c_double_p = C.POINTER(C.c_double)
@@ -99,6 +100,8 @@ def load() -> C.CDLL:
     lib.ddmpc_cost_model.argtypes = [vp, c_double_p, c_double_p]
     lib.ddmpc_kernel_name.argtypes = [vp]
     lib.ddmpc_kernel_name.restype = C.c_char_p
+    lib.ddmpc_closed_loop_kernel_name.argtypes = [vp]
+    lib.ddmpc_closed_loop_kernel_name.restype = C.c_char_p
     lib.ddmpc_debug_stamps.argtypes = [vp, C.c_int, vp]
     lib.ddmpc_debug_stamps.restype = C.c_int
     lib.ddmpc_closed_loop.argtypes = [vp, C.POINTER(Plant), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int]

@@ -215,6 +215,7 @@ struct ddmpc_handle {
   // staging for host-memory solves + workspace for get_solution
   DevBuf d_up, d_yp, d_uopt, d_cost, d_status, d_iters, d_beta, d_act, d_out, d_stamps;
   DevBuf d_pl, d_x, d_w, d_usys, d_ysys, d_stacc;
+  DevBuf d_lwup, d_lwyp;                   // ddmpc_closed_loop: the past window of the loop's last solve (what ddmpc_get_solution reads)
   // warm path: per-instance affine law (ddmpc_prepare)
   DevBuf d_lfac, d_lfacT, d_gain, d_prep_status, d_zero, d_need;
   // host-pointer solves: one packed device buffer and its pinned host mirror (two copies per solve instead of six)
@@ -256,6 +257,7 @@ struct ddmpc_handle {
   HostBuf h_flag;                          // one pinned word: the "factor again" count of the rank decision (launch_rr2_factors)
   hipEvent_t ev_flag = nullptr;            // ... and the event behind its copy
   int closed_loop_path = DDMPC_PATH_AUTO;
+  const char* loop_kernel = "";           // the kernel that stepped the plant in the last ddmpc_closed_loop (ddmpc_closed_loop_kernel_name)
   bool closed_loop_graph = false;
   bool large = false;                      // r beyond the register-resident cold kernels: global-workspace kernels only
   bool large_nominal = false;              // ... NOMINAL (the rank-revealing kernels); else ROBUST
@@ -2330,8 +2332,14 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
     dx = (double*)h->d_x.p; dup = (double*)h->d_up.p; dyp = (double*)h->d_yp.p; dw = (const double*)h->d_w.p;
     dus = (double*)h->d_usys.p; dys = (double*)h->d_ysys.p;
   }
+  // the fused loops keep the window and the inputs in use in LDS arrays of WARM_MAX_NF doubles: shapes beyond them take the
+  // per-step path (ddmpc_plant_kernel sizes nothing by m, p, n or n_mpc_step)
   const bool warm_ok = h->closed_loop_path != DDMPC_PATH_COLD &&
                        (size_t)n_mpc_step * m <= (size_t)WARM_MAX_NF && n * h->kp.nch <= WARM_MAX_NF;
+  // the record of the loop is its last solve, at the window that solve saw (the `.value`s the reference holds after its loop):
+  // the plant steps that follow it move u_past / y_past on, so that window is kept apart
+  if ((rc = h->d_lwup.ensure(nup)) || (rc = h->d_lwyp.ensure(nyp))) return rc;
+  double *lwup = (double*)h->d_lwup.p, *lwyp = (double*)h->d_lwyp.p;
   const bool warm_large = h->large && h->closed_loop_path != DDMPC_PATH_COLD;           // per step, on what ddmpc_prepare kept
   bool warm = warm_ok && !h->kp.convex && !h->large;   // no inequality: fused loop, one launch
   const bool warm_box = warm_ok && h->kp.convex && !h->large;     // slack box: per step, affine iterate + cold re-solve where a bound is active
@@ -2345,15 +2353,17 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
     for (size_t i = 0; i < B; ++i)
       if (ps[i] != 0) { warm = false; break; }
   }
+  h->loop_kernel = "ddmpc_plant_kernel";
   if (warm) {
     // affine control law: the whole loop of an instance runs inside one workgroup
     if ((rc = ddmpc_prepare(h))) return rc;
+    h->loop_kernel = "ddmpc_closed_loop_warm_kernel";
     if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
     begin_solve(h, Route::Cold);
     hipLaunchKernelGGL(ddmpc_closed_loop_warm_kernel, dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
                        16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
                        (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
-                       (double*)h->d_beta.p, (signed char*)h->d_act.p);
+                       (double*)h->d_beta.p, (signed char*)h->d_act.p, lwup, lwyp);
     HIP_TRY(hipGetLastError());
   }
   if (warm_box && convex_warm_on(h) && h->prep.cwl_nref == 0) {
@@ -2364,8 +2374,9 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
                        16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
                        (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
                        (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,
-                       (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p);
+                       (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p, lwup, lwyp);
     HIP_TRY(hipGetLastError());
+    h->loop_kernel = "ddmpc_closed_loop_convex_warm_kernel";
     warm = true;                                   // (no per-step launches below)
   }
   const unsigned pblocks = (unsigned)((B + 127) / 128);
@@ -2391,6 +2402,10 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   }
   auto enqueue_steps = [&]() -> int {
     for (int t = 0; !warm && t < n_steps; t += n_mpc_step) {
+      if (t + n_mpc_step >= n_steps) {                // the last solve: keep its window
+        HIP_TRY(hipMemcpyAsync(lwup, dup, nup, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(lwyp, dyp, nyp, hipMemcpyDeviceToDevice, h->stream));
+      }
       int rcs = (warm_box || warm_large ? step_on_route : solve_on_route)(h, dup, dyp, (double*)h->d_uopt.p, (double*)h->d_cost.p,
                                                                           (int32_t*)h->d_status.p, nullptr);
       if (rcs) return rcs;
@@ -2420,7 +2435,7 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(DDMPC_ERR_HIP, "closed-loop graph: %s", hipGetErrorString(e));
   }
-  end_solve(h, dup, dyp);          // (the final window: the per-step cold path re-solves there, the fused paths wrote beta before it)
+  end_solve(h, lwup, lwyp);        // (the last solve's window: the per-step cold path re-solves there, the other paths wrote its beta)
   if (mem == DDMPC_MEM_HOST) {
     HIP_TRY(hipMemcpyAsync(x, dx, nx, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(u_past, dup, nup, hipMemcpyDeviceToHost, h->stream));
@@ -2452,6 +2467,8 @@ int ddmpc_cost_model(ddmpc_handle* h, double* flops_per_solve, double* bytes_per
 }
 
 const char* ddmpc_kernel_name(ddmpc_handle* h) { return h ? h->kc.name2 : ""; }
+
+const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h) { return h ? h->loop_kernel : ""; }
 
 int ddmpc_debug_stamps(ddmpc_handle* h, int enable, uint64_t* out) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");

@@ -103,6 +103,7 @@ __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const dou
 // --------------------------------------------------------------------------
 // Closed-loop glue: apply up to `nsub` inputs of the last solve to the plant, record the
 // trajectories, push (u,y) into the past windows.  One thread per instance (tiny matvecs).
+// The only fixed-size array is xn[16] (ns <= 16, checked by ddmpc_closed_loop); nsub <= n_mpc_step <= L keeps u_opt in range.
 //   pl: [A (ns*ns) | B (ns*m) | C (p*ns) | D (p*m)] row-major.
 // utilities/controller/controller_operation.py:278-305, utilities/model_simulation.py:93-98,
 // direct_data_driven_mpc_controller.py:893-895.
@@ -638,13 +639,20 @@ __global__ void ddmpc_warm_step_kernel(KParams P, int RPs, int nf, const double*
 // Whole closed loop of one instance in one workgroup (warm path): per solve the affine law gives
 // optimal_u, then the plant/FIFO steps of ddmpc_plant_kernel.  Same loop order as
 // utilities/controller/controller_operation.py:263-305.
+// Fixed-size arrays and the checks of ddmpc_closed_loop that cover them (the same hold for the convex loop below):
+//   pv [WARM_MAX_NF]  nf = n (m + p) <= WARM_MAX_NF (`warm_ok`, and again in ddmpc_prepare)
+//   uo [WARM_MAX_NF]  n_mpc_step * m <= WARM_MAX_NF (`warm_ok`)
+//   xs / xn [16]      plant->ns <= 16
+//   bsh [WARM_MAX_R]  r <= 271: beyond that the handle is `large` and never launched here
+// m and p are bounded by these only; nothing is sized by p (the outputs of a step go straight to y_sys).
 __global__ void ddmpc_closed_loop_warm_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                               const int* __restrict__ prep_status, int ns, const double* __restrict__ pl,
                                               int n_steps, int n_mpc_step, double* __restrict__ x,
                                               double* __restrict__ u_past, double* __restrict__ y_past,
                                               const double* __restrict__ w, double* __restrict__ u_sys,
                                               double* __restrict__ y_sys, int* __restrict__ status_out,
-                                              double* __restrict__ beta_ws, signed char* __restrict__ act_ws) {
+                                              double* __restrict__ beta_ws, signed char* __restrict__ act_ws,
+                                              double* __restrict__ lw_up, double* __restrict__ lw_yp) {
   __shared__ double pv[WARM_MAX_NF];
   __shared__ double uo[WARM_MAX_NF];      // the first n_mpc_step*m entries of optimal_u
   __shared__ double xs[16];
@@ -668,6 +676,10 @@ __global__ void ddmpc_closed_loop_warm_kernel(KParams P, int RPs, int nf, const 
   for (int t0 = 0; t0 < n_steps; t0 += n_mpc_step) {
     __syncthreads();
     const bool last = (t0 + n_mpc_step >= n_steps);
+    if (last)                                         // the window of the last solve, for ddmpc_get_solution
+      for (int f = tid; f < nf; f += blockDim.x) {
+        if (f < P.npu) lw_up[b * P.npu + f] = pv[f]; else lw_yp[b * nyp + (f - P.npu)] = pv[f];
+      }
     const bool all_rows = last || P.dense_w;          // dense weights: z needs the whole beta vector
     for (int rho = tid; rho < r; rho += blockDim.x) {
       const int oidx = P.tabi[2 * RPs + rho];
@@ -701,12 +713,11 @@ __global__ void ddmpc_closed_loop_warm_kernel(KParams P, int RPs, int nf, const 
         }
         const double* uk = uo + j * m;
         const double* wk = w + (b * n_steps + k) * p;
-        double yv[16], xn[16];
+        double xn[16];                             // (ns <= 16: checked by ddmpc_closed_loop)
         for (int i = 0; i < p; ++i) {              // y = C x + D u + w with the state BEFORE the update
           double s = wk[i];
           for (int q = 0; q < ns; ++q) s += C[i * ns + q] * xs[q];
           for (int q = 0; q < m; ++q) s += Dm[i * m + q] * uk[q];
-          yv[i] = s;
           ys[i] = s;
         }
         for (int i = 0; i < ns; ++i) {
@@ -720,7 +731,7 @@ __global__ void ddmpc_closed_loop_warm_kernel(KParams P, int RPs, int nf, const 
         for (int i = 0; i < (n - 1) * m; ++i) up[i] = up[i + m];       // FIFO shift
         for (int i = 0; i < m; ++i) up[(n - 1) * m + i] = uk[i];
         for (int i = 0; i < (n - 1) * p; ++i) yp[i] = yp[i + p];
-        for (int i = 0; i < p; ++i) yp[(n - 1) * p + i] = yv[i];
+        for (int i = 0; i < p; ++i) yp[(n - 1) * p + i] = ys[i];      // (p is not bounded: no private copy of y)
       }
     }
   }
@@ -1003,10 +1014,11 @@ __global__ void ddmpc_closed_loop_convex_warm_kernel(KParams P, int RPs, int nf,
                                                      double* __restrict__ y_sys, int* __restrict__ status_out,
                                                      double* __restrict__ beta_ws, signed char* __restrict__ act_ws, int nbox,
                                                      const int* __restrict__ tab, const double* __restrict__ Mcol,
-                                                     double* __restrict__ sg) {
+                                                     double* __restrict__ sg, double* __restrict__ lw_up,
+                                                     double* __restrict__ lw_yp) {
   __shared__ double pv[WARM_MAX_NF];
   __shared__ double uo[WARM_MAX_NF];      // the first n_mpc_step*m entries of optimal_u
-  __shared__ double xs[16], yv[16], xn[16];   // (the plant's vectors in LDS: no scratch)
+  __shared__ double xs[16], xn[16];       // (the plant's state in LDS: no scratch; ns <= 16 is checked by ddmpc_closed_loop)
   __shared__ double bsh[WARM_MAX_R];
   __shared__ CwlLds s;
   const long long b = blockIdx.x;
@@ -1032,6 +1044,10 @@ __global__ void ddmpc_closed_loop_convex_warm_kernel(KParams P, int RPs, int nf,
   for (int t0 = 0; t0 < n_steps; t0 += n_mpc_step) {
     __syncthreads();
     const bool last = (t0 + n_mpc_step >= n_steps);
+    if (last)                                         // the window of the last solve, for ddmpc_get_solution
+      for (int f = tid; f < nf; f += blockDim.x) {
+        if (f < P.npu) lw_up[b * P.npu + f] = pv[f]; else lw_yp[b * nyp + (f - P.npu)] = pv[f];
+      }
     int viol = 0;
     for (int rho = tid; rho < r; rho += blockDim.x) {
       const int oidx = P.tabi[2 * RPs + rho];
@@ -1086,7 +1102,6 @@ __global__ void ddmpc_closed_loop_convex_warm_kernel(KParams P, int RPs, int nf,
           double sum = wk[i];
           for (int q = 0; q < ns; ++q) sum += C[i * ns + q] * xs[q];
           for (int q = 0; q < m; ++q) sum += Dm[i * m + q] * uk[q];
-          yv[i] = sum;
           ys[i] = sum;
         }
         for (int i = 0; i < ns; ++i) {
@@ -1100,7 +1115,7 @@ __global__ void ddmpc_closed_loop_convex_warm_kernel(KParams P, int RPs, int nf,
         for (int i = 0; i < (n - 1) * m; ++i) up[i] = up[i + m];       // FIFO shift
         for (int i = 0; i < m; ++i) up[(n - 1) * m + i] = uk[i];
         for (int i = 0; i < (n - 1) * p; ++i) yp[i] = yp[i + p];
-        for (int i = 0; i < p; ++i) yp[(n - 1) * p + i] = yv[i];
+        for (int i = 0; i < p; ++i) yp[(n - 1) * p + i] = ys[i];      // (p is not bounded: no private copy of y)
       }
     }
   }

@@ -370,6 +370,11 @@ class BatchedDDMPC:
     def kernel_name(self) -> str:
         return self._lib.ddmpc_kernel_name(self._h).decode()
 
+    def closed_loop_kernel_name(self) -> str:
+        """The kernel that stepped the plant in the last `closed_loop`: one of the two fused loops, or 'ddmpc_plant_kernel'
+        when the loop ran per step."""
+        return self._lib.ddmpc_closed_loop_kernel_name(self._h).decode()
+
 
 def hankel_matrix_batched(X: np.ndarray, L_: int, device: int = 0) -> np.ndarray:
     """Batched hankel_matrix on the GPU: X [B,N,nch] -> [B, L*nch, N-L+1]."""

@@ -333,7 +333,17 @@ typedef struct ddmpc_plant {
  * w [batch,n_steps,p] is the measurement noise; u_sys [batch,n_steps,m], y_sys [batch,n_steps,p]
  * receive the closed-loop trajectories; status [batch] the worst solve status seen (an instance whose
  * solve is not optimal stops evolving -- the reference raises at that point, controller.py:808 --
- * and the rest of its trajectory is NaN).  All buffers follow `mem`. */
+ * and the rest of its trajectory is NaN).  All buffers follow `mem`.
+ * A stopped instance: the rows of u_sys / y_sys from the first step of the failed solve on are NaN, the rows before
+ * it are those of a loop that did not stop, and x, u_past, y_past come back as they stood when that solve was
+ * made (the state after, and the window of, the last step applied; the caller's own values when the first solve
+ * fails).  The other instances of the batch are not affected.
+ * Bounds the call enforces: 1 <= plant->ns <= 16 and 1 <= n_mpc_step <= L (DDMPC_ERR_INVALID otherwise); m and p
+ * are bounded by the controller only.  The fused one-workgroup loops also need n (m + p) <= 256 and
+ * n_mpc_step * m <= 256: beyond either the call runs the per-step path whatever DDMPC_OPT_CLOSED_LOOP_PATH says.
+ * ddmpc_get_solution after the call reads the loop's last solve, at the past window that solve saw (the reference's
+ * `.value`s after its loop): the last n rows of [u_past on entry; u_sys[0 .. t)] and of [y_past on entry; y_sys[0 .. t)],
+ * t = n_mpc_step * ((n_steps - 1) / n_mpc_step) being the step of that solve. */
 int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps, int32_t n_mpc_step,
                       double* x, double* u_past, double* y_past, const double* w,
                       double* u_sys, double* y_sys, int32_t* status, int mem);
@@ -344,6 +354,12 @@ int ddmpc_cost_model(ddmpc_handle* h, double* flops_per_solve, double* bytes_per
 
 /* Name of the dominant kernel as it appears in rocprofv3 traces. */
 const char* ddmpc_kernel_name(ddmpc_handle* h);
+
+/* Name of the kernel that stepped the plant in the last ddmpc_closed_loop: "ddmpc_closed_loop_warm_kernel" or
+ * "ddmpc_closed_loop_convex_warm_kernel" when the whole loop ran fused in one launch, "ddmpc_plant_kernel" when it ran
+ * per step (DDMPC_PATH_COLD, shapes beyond the fused loops' bounds, NOMINAL instances without a law, laws taken from
+ * refining solves under DDMPC_OPT_CONVEX_WARM_LAW, handles beyond 271 rows); "" before the first loop.  Read-only. */
+const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h);
 
 /* Diagnostics only: in-kernel phase stamps (shader-clock ticks) of the next solves.
  * `enable` != 0 turns stamping on (zeroing the buffer); `out` (host, [batch,16] uint64,

@@ -147,3 +147,36 @@ def test_example_plot_helper(tmp_path):
     out = tmp_path / "p.png"
     plot_closed_loops(str(out), {"a": (u, y), "b": (u * 2, ydiv)}, [1.0, 1.0], [0.65, 0.77], t0=4, title="t")
     assert out.stat().st_size > 10000
+
+
+def test_harness_plant_simulation_matches_oracle_on_a_non_square_plant_with_feedthrough():
+    # simulate_batch / generate_batch against oracle.Plant.simulate / generate_instance where nothing coincides: m != p,
+    # ns != n (the data run knows ns only) and D != 0 -- the four-tank has m = p and D = 0
+    from direct_data_driven_mpc_amd.harness import simulate_batch
+    from oracle import ddmpc_oracle as orc
+    rng = np.random.default_rng(5)
+    ns, m, p, N = 5, 3, 2, 90
+    A = rng.normal(size=(ns, ns))
+    A *= 0.8 / max(abs(np.linalg.eigvals(A)))
+    plant = dict(A=A, B=rng.normal(size=(ns, m)), C=rng.normal(size=(p, ns)), D=0.3 * rng.normal(size=(p, m)), eps_max=0.002)
+    seeds = [3, 11, 12]
+    d = generate_batch(seeds, N=N, plant=plant)
+    assert d["u_d"].shape == (3, N, m) and d["y_d"].shape == (3, N, p) and d["x_end"].shape == (3, ns)
+    for b, s in enumerate(seeds):
+        ref = orc.generate_instance(s, N=N, plant_params=plant)
+        assert np.array_equal(d["u_d"][b], ref["u_d"])
+        assert np.max(np.abs(d["x_0"][b] - ref["x_0"])) < 1e-12
+        assert np.max(np.abs(d["y_d"][b] - ref["y_d"])) < 1e-12
+        assert np.max(np.abs(d["x_end"][b] - ref["plant"].x)) < 1e-12
+    U = rng.uniform(-1.0, 1.0, (3, 17, m))
+    W = 0.002 * rng.uniform(-1.0, 1.0, (3, 17, p))
+    x0 = rng.normal(size=(3, ns))
+    Y, x_end = simulate_batch(plant["A"], plant["B"], plant["C"], plant["D"], x0, U, W)
+    for b in range(3):
+        pl = orc.Plant(plant["A"], plant["B"], plant["C"], plant["D"])
+        pl.x = x0[b].copy()
+        assert np.max(np.abs(Y[b] - pl.simulate(U[b], W[b]))) < 1e-12
+        assert np.max(np.abs(x_end[b] - pl.x)) < 1e-12
+    # the feedthrough is really in there: y[0] depends on u[0]
+    Y2, _ = simulate_batch(plant["A"], plant["B"], plant["C"], plant["D"], x0, U + 1.0, W)
+    assert np.max(np.abs(Y2[:, 0] - Y[:, 0] - np.ones(m) @ plant["D"].T)) < 1e-12

@@ -301,3 +301,30 @@ def test_model_based_nominal_oracle_with_dense_weighting_matrices():
     a = solve_nominal_model_based(mk(Qd, Rd), plant, up, yp)
     b = solve_nominal_model_based(mk(Qd + 1e-300, Rd), plant, up, yp)       # (not diagonal to the letter: the dense path)
     assert np.max(np.abs(a["optimal_u"] - b["optimal_u"])) < 1e-12 and abs(a["cost"] - b["cost"]) < 1e-12 * max(1.0, abs(a["cost"]))
+
+
+def test_premises_of_the_closed_loop_plant_tests():
+    """tests/test_gpu_closed_loop_plants.py rests on figures of the oracle alone: every loop of its table stays optimal
+    (orc.closed_loop raises otherwise), the recorded active-set iteration counts of the convex rows and of the 300-row case,
+    two or more iterations somewhere in at least two convex rows with m != p (so the active-set code of the fused convex
+    kernel runs there), and the stop indices of the capped loops.  Kept here so that they cannot drift unseen."""
+    import test_gpu_closed_loop_plants as T
+    several = 0
+    for name in T.CASES:
+        case, nms = T._table_case(name)
+        if case["spec"].slack != "convex":
+            for b in range(case["B"]):
+                T.oracle_loop(case, b, nms)
+            continue
+        its = T.oracle_iterations(case, nms)
+        assert its == T.ORACLE_ITERS[name], (name, its)
+        several += case["spec"].m != case["spec"].p and max(max(i) for i in its) >= 2
+    assert several >= 2
+    case = T._large_case()
+    assert T.oracle_iterations(case, T.LARGE["nms"]) == T.LARGE["oracle_iters"]
+    g = T.STOP
+    spec, d, x0, up, yp, w = T._stop_case()
+    stops = [T.oracle_capped_loop(spec, d["u_d"][b], d["y_d"][b], x0[b], up[b], yp[b], w[b], 1, g["max_iter"])[2]
+             for b in range(g["B"])]
+    assert stops == g["stop_at"]
+    assert any(s is not None and s >= 1 for s in stops) and any(s is None for s in stops)
