@@ -599,6 +599,12 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_kernel(Rr3 S, KParams P, 
           if (iter == 1) RR3_STAMP();   // 4: W
           rr3_w_gram(Wg, nT, k, Sm);                                      // Sm = -W'W (big: the tile exchange is done with)
           w_times(yv);                                                    // hv = W'y
+          // lam (D0 - D1) = lam / lamb_sigma for a weighted boxed output and for every output of the terminal window.  An
+          // unweighted one (Q entry 0) has D0 = 1e25 + 1 / lamb_sigma == D1 = 1e25 in fp64, but it cannot be on the list: its
+          // multiplier is ~1e-25 (K_ii = lam 1e25), so |sig_scale * beta| never reaches the bound and the box test above leaves
+          // act = 0 (tests/test_gpu_large_weights.py::test_robust_unweighted_boxed_outputs_never_switch).  Should one get here
+          // all the same, `dok` sends the instance to ddmpc_large_solve_kernel (st = 5) before anything is read from the
+          // system the division below would spoil.
           bool dok = true;
           if (tid < k) {
             const int rho = perm[list[tid]];

@@ -75,6 +75,7 @@ class BatchedDDMPC:
             r = _expand_weight(wk_r, r, self.m * self.L, target)
             wk_q = wk_r = target
         self._q, self._r = q, r
+        self.weight_kind = int(wk_q)                     # DDMPC_WEIGHT_* handed to ddmpc_create
         self._us = np.ascontiguousarray(np.asarray(u_s, dtype=np.float64).reshape(-1))
         self._ys = np.ascontiguousarray(np.asarray(y_s, dtype=np.float64).reshape(-1))
         if self._us.size != self.m or self._ys.size != self.p:

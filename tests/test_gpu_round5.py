@@ -610,6 +610,15 @@ def test_dense_weighting_matrices_of_nominal_controllers_beyond_the_register_res
     assert np.array_equal(res["diag"][2], res["dense"][2])
     assert np.max(np.abs(res["diag"][0] - res["dense"][0])) <= 1e-9 * np.max(np.abs(res["diag"][0]))
     assert np.max(np.abs(res["diag"][1] - res["dense"][1]) / np.abs(res["diag"][1])) <= 1e-9
+    # ... and the diagonal path against the model-based solution of the QP with these weights (two implementations that agree
+    # with each other are not yet right)
+    sp = orc.QPSpec(**{**spec.__dict__, "Q": np.diag(qd), "R": np.diag(rd)})
+    assert np.all(res["diag"][2] == 0), res["diag"][2]
+    for b in range(B):
+        mod = solve_nominal_model_based(sp, plant, up[b], yp[b])
+        assert mod["feas_residual"] < 1e-10
+        assert np.max(np.abs(res["diag"][0][b] - mod["optimal_u"])) / np.max(np.abs(mod["optimal_u"])) < TOL_U, b
+        assert abs(res["diag"][1][b] - mod["cost"]) <= TOL_COST * abs(mod["cost"]), b
 
 
 # ------------------------------------------------------------------ more than 1024 rows (ROBUST)

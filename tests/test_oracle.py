@@ -328,3 +328,68 @@ def test_premises_of_the_closed_loop_plant_tests():
              for b in range(g["B"])]
     assert stops == g["stop_at"]
     assert any(s is not None and s >= 1 for s in stops) and any(s is None for s in stops)
+
+
+# (scheme, shape, slack) of every case of tests/test_gpu_large_weights.py; test_large_weight_premises_cover_every_case keeps
+# the list in step with that file without importing it (and the GPU test modules it builds on) when this file is collected
+LARGE_WEIGHT_CASES = [("robust", "296", "none"), ("robust", "296", "convex"), ("robust", "296-crowded", "convex"),
+                      ("robust", "300", "none"), ("robust", "300", "convex"), ("robust", "608", "none"), ("robust", "608", "convex"),
+                      ("robust", "1100", "convex"), ("nominal", "5ch-315rows", "none"), ("nominal", "4ch-296rows", "none"),
+                      ("nominal", "9ch-405rows", "none"), ("nominal", "cfg5", "none"), ("nominal", "3ch-1029rows", "none")]
+
+
+def test_large_weight_premises_cover_every_case():
+    import test_gpu_large_weights as T
+    assert LARGE_WEIGHT_CASES == [("robust", s, k) for s, k in T.ROBUST_USED] + [("nominal", s, "none") for s in T.NOMINAL_USED]
+
+
+@pytest.mark.parametrize("scheme,shape,slack", LARGE_WEIGHT_CASES)
+def test_premises_of_the_large_weight_tests(scheme, shape, slack):
+    """tests/test_gpu_large_weights.py compares the device with the oracle under the ramp weight profile at 1e-8 (optimal_u) and
+    1e-9 (cost).  That notices an indexing mistake of a reader of the weight tables only if the mistake moves the solution: for
+    every (shape, scheme, slack) used there, each of the five mistakes of T.MUTATIONS, applied to Q and R of the oracle's own
+    problem (instance 0, the data tail as the window), must move optimal_u by at least 1e-5 or the cost by at least 1e-6
+    relative -- 1000 bars.  Also kept here: the crowded case does crowd the oracle's active set, the
+    NOMINAL zeros profile leaves the reduced least-squares matrix with full column rank (smallest singular value at least
+    1e-6 of the largest), and the closed loop of the ramp profile stays optimal."""
+    import test_gpu_large_weights as T
+    from oracle.nominal_exact import solve_nominal_model_based
+    if scheme == "robust":
+        B = 6 if shape == "296-crowded" else 1
+        spec0, N, u_d, y_d, up, yp = T.robust_case(shape, slack, B)
+
+        def solve(spec, b=0):
+            sol = orc.solve_fullspace(spec, u_d[b], y_d[b], up[b], yp[b])
+            assert sol.status == "optimal"
+            return sol.optimal_u, sol.cost, sol
+    else:
+        spec0, plant, N, u_d, y_d, up, yp = T.nominal_case(shape, 1)
+
+        def solve(spec, b=0):
+            mod = solve_nominal_model_based(spec, plant, up[b], yp[b])
+            assert mod["feas_residual"] < 1e-10
+            return mod["optimal_u"], mod["cost"], mod
+    q, r = T.ramp(spec0)
+    assert np.all(np.diff(q, axis=0) > 0) and np.all(np.diff(r, axis=0) > 0)    # no two steps of a channel share a value,
+    assert np.all(np.diff(q, axis=1) > 0) and np.all(np.diff(r, axis=1) > 0)    # no two channels of a step
+    u0, c0, _ = solve(T.with_weights(spec0, q, r))
+    for name, mut in T.MUTATIONS.items():
+        qm, rm = mut(q, spec0.n), mut(r, spec0.n)
+        assert not (np.array_equal(qm, q) and np.array_equal(rm, r)), name     # the mistake does change the tables of this shape
+        u1, c1, _ = solve(T.with_weights(spec0, qm, rm))
+        du, dc = np.max(np.abs(u1 - u0)) / np.max(np.abs(u0)), abs(c1 - c0) / abs(c0)
+        print("%s %s %s | %-36s | u %.1e (%.0e bars)  cost %.1e (%.0e bars)" % (scheme, shape, slack, name, du, du / 1e-8, dc, dc / 1e-9))
+        assert du >= 1e-5 or dc >= 1e-6, (name, du, dc)
+    if shape == "296-crowded":
+        spec = T.weighted(spec0, "ramp")
+        assert max(np.count_nonzero(solve(spec, b)[2].active) for b in range(B)) > 64
+    if scheme == "nominal" and shape in ("5ch-315rows", "4ch-296rows", "9ch-405rows"):
+        spec = T.weighted(spec0, "zeros")
+        assert np.count_nonzero(np.diag(spec.Q) == 0.0) >= spec.L // 3 and np.all(np.diag(spec.R) > 0.0)
+        sv = np.linalg.svd(T.nominal_reduced_matrix(spec, plant, up[0], yp[0]), compute_uv=False)
+        print("nominal %s zeros: %d x rank %d, sigma_min / sigma_max = %.1e" % (shape, sv.size, np.sum(sv > 1e-6 * sv[0]), sv[-1] / sv[0]))
+        assert sv[-1] >= 1e-6 * sv[0]
+    if (shape, slack) == ("300", "convex"):
+        case = T.closed_loop_case()
+        for b in range(case["B"]):
+            T.CLP.oracle_loop(case, b, T.CLP.LARGE["nms"])                     # (raises unless every solve is optimal)
