@@ -314,6 +314,12 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
     const int NS = rE >> 2, IR = rE >> 4, rr = rE & 15;
     const int lane = tid & 63;
     const int l15 = lane & 15, l4 = lane >> 4, l3 = lane & 3, lo = l15 >> 2;
+    // The in-tile factorisation's three lane-dependent LDS offsets (own panel row, operand store, next panel columns), formed
+    // ONCE per pass and opaque: otherwise they are rematerialised from the lane id in every sub-step, a dozen integer
+    // instructions in the panel wave's stream each time.
+    // (the row index is scaled after the fence, so that the 32-byte alignment of a panel row stays visible)
+    int ix_x = lane & 31, ix_lt = l4 * LRS + l15, ix_pw = l4 * 4 + l3;
+    if constexpr (WAVE == 0) asm volatile("" : "+v"(ix_x), "+v"(ix_lt), "+v"(ix_pw));
     static_for<NE>([&](auto e) __attribute__((always_inline)) {
       const int rho = tid + e * NTHR;
       if (rho < RP) {
@@ -360,17 +366,25 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
     // `pend(h)`, h = 0..11: hooks at which the caller slips independent MFMAs (trailing updates of later diagonal tiles)
     // into the dependency chain of the sub-step; pinned with sched_barrier so that they run beside the chain's VALU
     // work and LDS waits instead of in front of it.
-    auto substep = [&](d4& Ad, d4& Et, auto QQ, int nq, auto&& pend) __attribute__((always_inline)) {
+    // (Mt: where the last sub-step leaves the tile M = L_JJ^-1 in accumulator layout, see below)
+    auto substep = [&](d4& Ad, d4& Et, d4& Mt, auto QQ, auto&& pend) __attribute__((always_inline)) {
       constexpr int q = QQ;
       constexpr int c0 = 4 * q;
 #define DDMPC_HOOK(h) do { pend(std::integral_constant<int, h>{}); } while (0)
-      const int x = lane & 31;                                      // lanes 32..63 mirror lanes 0..31
+      const double* Pr = PT2 + 4 * ix_x;                             // own row (lanes 32..63 mirror lanes 0..31)
       const double* Pd = PT2 + c0 * 4;                              // rows c0..c0+3 of the tile, 4 panel entries each
       const double p00 = -Pd[0];
       const double p10 = -Pd[4], p11 = -Pd[5];
       const double p20 = -Pd[8], p21 = -Pd[9], p22 = -Pd[10];
       const double p30 = -Pd[12], p31 = -Pd[13], p32 = -Pd[14], p33 = -Pd[15];
-      const double r0 = PT2[x * 4 + 0], r1 = PT2[x * 4 + 1], r2 = PT2[x * 4 + 2], r3 = PT2[x * 4 + 3];
+      const double r0 = Pr[0], r1 = Pr[1], r2 = Pr[2], r3 = Pr[3];
+      double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+      if constexpr (q == 3) {                                       // rows 0..11 of M, stored by the sub-steps before (Ad, Et are dead: registers to spare)
+        // (each lane reloads exactly what IT stored as opE in sub-steps 0..2 -- LT[ix_lt + 4q LRS + 16] -- so this is a spill and
+        //  reload through LDS with no cross-lane hand-off: it needs no fence, and differs from keeping the four opE in registers
+        //  only in that those registers are free during the sub-steps where Ad and Et are live)
+        m0 = LT[ix_lt + 16]; m1 = LT[ix_lt + 4 * LRS + 16]; m2 = LT[ix_lt + 8 * LRS + 16];
+      }
       DDMPC_HOOK(0);
       const double i0 = rsq_n2(p00);
       DDMPC_HOOK(1);
@@ -389,10 +403,6 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
       const double x2 = -(r2 + x0 * l20 + x1 * l21) * i2;
       const double x3 = -(r3 + x0 * l30 + x1 * l31 + x2 * l32) * i3;
       DDMPC_HOOK(6);
-      if (lane < 32) {                                              // kept for M / L_JJ / y; not on the chain
-        LT[(c0 + 0) * LRS + x] = x0; LT[(c0 + 1) * LRS + x] = x1;
-        LT[(c0 + 2) * LRS + x] = x2; LT[(c0 + 3) * LRS + x] = x3;
-      }
       // MFMA operands without an LDS round trip.  Lane rows hold [tile rows, identity rows, tile rows, identity rows]
       // (x = lane & 31); v_permlane16_swap exchanges the odd rows of its first operand with the even rows of its second:
       //   swap(x0, x1) -> [x0.A x1.A x0.A x1.A], [x0.E x1.E x0.E x1.E];  swap(x2, x3) likewise,
@@ -401,18 +411,30 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
       const bool lowhalf = lane < 32;
       const double opA = lowhalf ? s01a[0] : s23a[0];
       const double opE = lowhalf ? s01a[1] : s23a[1];
+      // The operands ARE the rows kept for L_JJ / M / y: lane (l4, l15) holds x_l4 of tile row l15 (opA) and of identity row
+      // l15 (opE).  One store each by the whole wave (LT keeps its k-major layout, bit for bit: the mirror lanes compute
+      // the same values), and opE is register q of M in accumulator layout (M[l4 + 4q][l15]): the last sub-step of a full
+      // tile leaves M in the diagonal tile's registers -- its own rows from the operand, the rows of the sub-steps before
+      // read back from LT at its start, under the pivot chain -- instead of a read-back behind the chain in factor_end.
+      LT[ix_lt + c0 * LRS] = opA;
+      LT[ix_lt + c0 * LRS + 16] = opE;
+      if constexpr (q == 3) Mt = d4{m0, m1, m2, opE};
       DDMPC_HOOK(7);
-      Ad = __builtin_amdgcn_mfma_f64_16x16x4f64(opA, opA, Ad, 0, 0, 0);
-      Et = __builtin_amdgcn_mfma_f64_16x16x4f64(opE, opA, Et, 0, 0, 0);
+      if constexpr (q < 3) {                                        // (nothing reads the two accumulators after the last sub-step)
+        Ad = __builtin_amdgcn_mfma_f64_16x16x4f64(opA, opA, Ad, 0, 0, 0);
+        Et = __builtin_amdgcn_mfma_f64_16x16x4f64(opE, opA, Et, 0, 0, 0);
+      }
       DDMPC_HOOK(8);
       DDMPC_HOOK(9);
       DDMPC_HOOK(10);
       DDMPC_HOOK(11);
       if constexpr (q < 3) {
-        if (q + 1 < nq && lo == q + 1) {
+        // (the next panel columns go out whether or not a sub-step follows: after the last pivot group of a padded tile
+        //  nobody reads PT2 before factor_begin rewrites all of it, and the test would be in every sub-step's stream)
+        if (lo == q + 1) {
           static_for<4>([&](auto j) __attribute__((always_inline)) {
-            PT2[(l4 + 4 * j) * 4 + l3] = Ad[j()];
-            PT2[(16 + l4 + 4 * j) * 4 + l3] = Et[j()];
+            PT2[ix_pw + 16 * j] = Ad[j()];
+            PT2[ix_pw + 16 * j + 64] = Et[j()];
           });
         }
       }
@@ -428,8 +450,8 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
       static_for<4>([&](auto j) __attribute__((always_inline)) { Et[j()] = ((lz >> 4) + 4 * j() == (lz & 15)) ? -1.0 : 0.0; });
       if (lo == 0) {
         static_for<4>([&](auto j) __attribute__((always_inline)) {
-          PT2[(l4 + 4 * j) * 4 + l3] = Ad[j()];
-          PT2[(16 + l4 + 4 * j) * 4 + l3] = Et[j()];
+          PT2[ix_pw + 16 * j] = Ad[j()];
+          PT2[ix_pw + 16 * j + 64] = Et[j()];
         });
       }
       // In-wave hand-off through LDS: lanes read what OTHER lanes of the wave just wrote.  Without a fence the compiler
@@ -442,11 +464,14 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
       constexpr int Jt = JT;
       constexpr int SD = TM::slot(Jt, Jt);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");       // LT was written by other lanes of this wave
-      static_for<4>([&](auto j) __attribute__((always_inline)) {
-        const int k = l4 + 4 * j();
-        const double mv = LT[k * LRS + 16 + l15];
-        acc[SD][j()] = (k < 4 * nq) ? mv : 0.0;                     // register j of lane (l4, l15) = M[l4 + 4j][l15]
-      });
+      // nq == 4 <=> the caller ran sub-step q = 3 (its `q < nq` guard), the only one that writes Mt = acc[SD]: keep the two in step
+      if (nq < 4) {                                                 // padded last tile (a full tile got M from its last sub-step)
+        static_for<4>([&](auto j) __attribute__((always_inline)) {
+          const int k = l4 + 4 * j();
+          const double mv = LT[k * LRS + 16 + l15];
+          acc[SD][j()] = (k < 4 * nq) ? mv : 0.0;                   // register j of lane (l4, l15) = M[l4 + 4j][l15]
+        });
+      }
       if (Jt == IR) {                                               // y of the last tile column = the substituted rhs row
         if (lane < 4 * nq) tvec[16 * Jt + lane] = LT[lane * LRS + rr];
       }
@@ -672,7 +697,7 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
           d4 Ad = fix_tile(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, acc[S0]);
           d4 Et;
           factor_begin(Ad, Et);
-          static_for<4>([&](auto q) __attribute__((always_inline)) { substep(Ad, Et, q, 4, no_pend); });
+          static_for<4>([&](auto q) __attribute__((always_inline)) { substep(Ad, Et, acc[S0], q, no_pend); });
           factor_end(std::integral_constant<int, 0>{}, 4);
           f0_done = true;
         }
@@ -713,7 +738,7 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
           d4 Ad = acc[TM::slot(0, 0)];
           d4 Et;
           factor_begin(Ad, Et);
-          static_for<4>([&](auto q) __attribute__((always_inline)) { if (q() < nq0) substep(Ad, Et, q, nq0, no_pend); });
+          static_for<4>([&](auto q) __attribute__((always_inline)) { if (q() < nq0) substep(Ad, Et, acc[TM::slot(0, 0)], q, no_pend); });
           factor_end(std::integral_constant<int, 0>{}, nq0);
         }
       }
@@ -772,7 +797,7 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
             });
             tphU += now() - tu0;
             factor_begin(Ad, Et);
-            substep(Ad, Et, std::integral_constant<int, 0>{}, nqn, no_pend);
+            substep(Ad, Et, acc[S], std::integral_constant<int, 0>{}, no_pend);
           }
         }
         // (T2) the other tiles of tile row Jb
@@ -805,7 +830,7 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
                 }
               });
             };
-            if (q < nqn) substep(Ad, Et, std::integral_constant<int, q>{}, nqn, pend);
+            if (q < nqn) substep(Ad, Et, acc[TM::slot(Jb + 1, Jb + 1)], std::integral_constant<int, q>{}, pend);
           });
           if (nqn > 0) factor_end(std::integral_constant<int, Jb + 1>{}, nqn);
         }
