@@ -1,8 +1,9 @@
-// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp).
+// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp).
 // Host-side responsibilities: parameter validation with the reference's error
 // conditions (direct_data_driven_mpc_controller.py:165-168,211-222,298-343,664-670),
 // device buffer ownership, kernel-instance selection, launch.
 #include "ddmpc_rr3_law.hpp"
+#include "ddmpc_box_law.hpp"
 #include "../../include/ddmpc.h"
 
 #include <cmath>
@@ -154,6 +155,8 @@ enum class Route {
   RobustOneWg,      // ... the one-workgroup kernel (ddmpc_large_solve_kernel)
   NominalPhases,    // NOMINAL beyond the register-resident kernels: the phase kernels (ddmpc_rr2*.hpp)
   NominalOneWg,     // ... the one-workgroup kernel (ddmpc_nominal_rr_kernel)
+  BoxLaw,           // ROBUST with input bounds (ddmpc_set_input_bounds), register-resident sizes: the active-set iteration on the
+                    // law and M = K0^-1 E_box (ddmpc_box_law.hpp); the cold kernels serve its preparation only
 };
 
 // What a launch of the global-workspace routes does: the whole solve, the data-dependent factors alone (ddmpc_prepare), or a
@@ -187,8 +190,9 @@ struct Prep {
   Route route = Route::Cold;
   bool law = false;                        // beyond 271 rows: the affine law was formed (DDMPC_OPT_LARGE_AFFINE_LAW)
   int r3_nolaw = 0;                        // ... ROBUST: instances whose law missed the refinement threshold (their steps take the filtered re-solve)
-  int cwl_nbox = 0;                        // DDMPC_OPT_CONVEX_WARM_LAW: boxed components
-  int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch)
+  int cwl_nbox = 0;                        // DDMPC_OPT_CONVEX_WARM_LAW, Route::BoxLaw: boxed components
+  int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch;
+                                           //     BoxLaw: they iterate like the others and report optimal_inaccurate with a non-empty active set)
   int epoch = 0;                           // stamp of the flags recorded by the factor-export launch (AUTO)
 };
 
@@ -251,6 +255,11 @@ struct ddmpc_handle {
   int convex_update = 1;                        // DDMPC_OPT_CONVEX_UPDATE: active-set iterations keep the first factor (rank-k update)
   int convex_warm = 0;                     // DDMPC_OPT_CONVEX_WARM_LAW: warm steps under the slack box run the active-set iteration on the law
   DevBuf d_mcol, d_cwl_tab, d_cwl_sg, d_cwl_ref;   // ... M = K0^-1 E_box [batch][nbox][r]; [box_rho | box_of]; k x k scratch; refined-law flags (+ count)
+  // input bounds (ddmpc_set_input_bounds): per channel, +-infinity = none; `bounded` = some bound is finite (Route::BoxLaw)
+  std::vector<double> umin_h, umax_h;
+  bool bounded = false;
+  DevBuf d_box_bd, d_ubnd;                 // ... [a | c | lo | hi | 1/d] of the box list (ddmpc_box_law.hpp); [u_min | u_max] for the reconstruction
+  DevBuf s_gain, s_prep_status, s_mcol, s_cwl_ref;   // ... the preparation of ddmpc_solve's own (solve_box): a kept ddmpc_prepare survives the solve
   int epoch = 0;                           // cold launches so far (KParams::epoch)
   int flag_epoch = 0;                      // latest stamp written into d_rflag
   HostBuf h_io;
@@ -269,7 +278,7 @@ struct ddmpc_handle {
 // batches up to 65535 (grid rows), up to 1024 rows (64-bit masks over 16-column chunks) and no diagnostic stamps
 // (DDMPC_OPT_LARGE_PIPELINE selects them by default); the one-workgroup kernels serve everything else at that size.
 static Route select_route(const ddmpc_handle* h) {
-  if (!h->large) return Route::Cold;
+  if (!h->large) return h->bounded ? Route::BoxLaw : Route::Cold;
   const bool phases = h->large_pipeline == DDMPC_PIPELINE_PHASES && h->batch <= 65535 && !h->stamps_on && h->kp.r <= 1024;
   if (h->large_nominal) return phases ? Route::NominalPhases : Route::NominalOneWg;
   return phases ? Route::RobustPhases : Route::RobustOneWg;
@@ -774,7 +783,9 @@ int ddmpc_destroy(ddmpc_handle* h) {
   DevBuf* bufs[] = {&h->d_tabd, &h->d_tabi, &h->d_ud, &h->d_yd, &h->d_up, &h->d_yp, &h->d_uopt,
                     &h->d_cost, &h->d_status, &h->d_iters, &h->d_beta, &h->d_act, &h->d_out, &h->d_stamps,
                     &h->d_pl, &h->d_x, &h->d_w, &h->d_usys, &h->d_ysys, &h->d_stacc,
-                    &h->d_lfac, &h->d_lfacT, &h->d_gain, &h->d_prep_status, &h->d_zero, &h->d_dmat, &h->d_need, &h->d_io, &h->d_rr, &h->d_alpha, &h->d_zws, &h->d_resc, &h->d_xws, &h->d_rflag, &h->d_rrmeta, &h->d_gpre, &h->d_perm, &h->d_rr2d, &h->d_rr2res, &h->d_rr2mt, &h->d_rr2v, &h->d_rr2zp, &h->d_rr2sc, &h->d_wz, &h->d_gz, &h->d_gres, &h->d_zvirt, &h->d_rr3w, &h->d_rr3k, &h->d_rr_fb, &h->d_rrmeta_fb, &h->d_rr2cand, &h->d_rr2tol, &h->d_rr2rank, &h->d_wd, &h->d_rr2y};
+                    &h->d_lfac, &h->d_lfacT, &h->d_gain, &h->d_prep_status, &h->d_zero, &h->d_dmat, &h->d_need, &h->d_io, &h->d_rr, &h->d_alpha, &h->d_zws, &h->d_resc, &h->d_xws, &h->d_rflag, &h->d_rrmeta, &h->d_gpre, &h->d_perm, &h->d_rr2d, &h->d_rr2res, &h->d_rr2mt, &h->d_rr2v, &h->d_rr2zp, &h->d_rr2sc, &h->d_wz, &h->d_gz, &h->d_gres, &h->d_zvirt, &h->d_rr3w, &h->d_rr3k, &h->d_rr_fb, &h->d_rrmeta_fb, &h->d_rr2cand, &h->d_rr2tol, &h->d_rr2rank, &h->d_wd, &h->d_rr2y,
+                    &h->d_mcol, &h->d_cwl_tab, &h->d_cwl_sg, &h->d_cwl_ref, &h->d_r3y, &h->d_r3res, &h->d_r3zp, &h->d_r3flag,
+                    &h->d_box_bd, &h->d_ubnd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp};
   for (DevBuf* b : bufs) b->release();
   h->h_io.release();
   h->h_flag.release();
@@ -1349,6 +1360,43 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
   return need ? launch_cold(h, up, yp, uo, cost, status, iters, s) : DDMPC_OK;
 }
 
+// Route::BoxLaw (input bounds): a control step on what ddmpc_prepare kept -- the law, M for the whole box list and the table.
+static int launch_box_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
+                           int32_t* iters) {
+  int rc;
+  if ((rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure((size_t)h->batch * h->kp.rE)))
+    return rc;
+  hipLaunchKernelGGL(ddmpc_box_step_kernel, dim3((unsigned)h->batch), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
+                     16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo,
+                     cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox,
+                     (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                     h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr);
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
+// ... and a cold solve: the trajectories are read anew and nothing derived from them is kept.  What ddmpc_prepare runs goes
+// into a preparation of the solve's own (buffers apart from the kept one's, which a ddmpc_prepare before the call keeps valid,
+// as on Route::Cold), the step kernel runs at the caller's window, and that preparation is dropped.
+static int solve_box(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
+                     int32_t* iters) {
+  auto swap_bufs = [&]() {
+    std::swap(h->d_gain, h->s_gain); std::swap(h->d_prep_status, h->s_prep_status);
+    std::swap(h->d_mcol, h->s_mcol); std::swap(h->d_cwl_ref, h->s_cwl_ref);
+  };
+  const Prep kept = h->prep;
+  swap_bufs();
+  h->prep = Prep{};
+  int rc = ddmpc_prepare(h);
+  if (!rc) {
+    begin_solve(h, Route::BoxLaw);
+    rc = launch_box_step(h, up, yp, uo, cost, status, iters);
+  }
+  swap_bufs();
+  h->prep = kept;
+  return rc;
+}
+
 // Nominal scheme: instances whose Gram matrix is singular (exact data) are re-solved by the rank-revealing
 // kernel; it only touches instances the fast path marked SOLVER_ERROR.  Beyond the register-resident kernels (the NOMINAL
 // routes) every instance is marked and this is the whole solve.
@@ -1680,6 +1728,7 @@ static int launch_large_nominal_warm(ddmpc_handle* h, Route route, const double*
 // A cold solve of the whole batch on the handle's route (ddmpc_solve, the cold closed loop).
 static int solve_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                           int32_t* iters) {
+  if (select_route(h) == Route::BoxLaw) return solve_box(h, up, yp, uo, cost, status, iters);
   const Route route = begin_solve(h, select_route(h));
   if (route != h->prep.route) forget_prep(h);                   // (its workspace is the one ddmpc_prepare kept things in)
   if (route == Route::RobustPhases || route == Route::RobustOneWg)
@@ -1697,6 +1746,7 @@ static int solve_on_route(ddmpc_handle* h, const double* up, const double* yp, d
 static int step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                          int32_t* iters) {
   const Route route = begin_solve(h, select_route(h));
+  if (route == Route::BoxLaw) return launch_box_step(h, up, yp, uo, cost, status, iters);
   if (route == Route::RobustPhases || route == Route::RobustOneWg)
     return launch_large_robust(h, route, Stage::OnFactors, up, yp, uo, cost, status, iters);
   if (route != Route::Cold) return launch_large_nominal_warm(h, route, up, yp, uo, cost, status, iters);
@@ -1760,6 +1810,9 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
   if (!h || !u_d || !y_d || !u_past || !y_past || !u_opt || !cost || !status)
     return fail(DDMPC_ERR_INVALID, "null argument");
   if (h->batch > 0x7fffffffLL) return fail(DDMPC_ERR_INVALID, "batch too large for one launch");
+  if (h->bounded)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_solve_from_host does not serve a handle with input bounds (ddmpc_set_input_bounds): "
+                "use ddmpc_set_data + ddmpc_solve");
   h->gpre_valid = false;
   if (select_route(h) != Route::Cold) {   // no chunked cold launches beyond the register-resident kernels: plain upload + solve
     int rcs = ddmpc_set_data(h, u_d, y_d, DDMPC_MEM_HOST);
@@ -1875,7 +1928,8 @@ int ddmpc_prepare(ddmpc_handle* h) {
     h->prep.valid = rc == DDMPC_OK;
     return rc;
   }
-  if (route != Route::Cold) {             // ROBUST at this size: Gram + lam D, the factor of the columns outside the slack box and
+  const bool box = route == Route::BoxLaw;
+  if (route != Route::Cold && !box) {     // ROBUST at this size: Gram + lam D, the factor of the columns outside the slack box and
                                           // the Schur complement of the boxed block are formed once and kept
     int rc = launch_large_robust(h, route, Stage::Factors, h->ud, h->yd, nullptr, nullptr, nullptr, nullptr);
     if (!rc && h->large_affine && route == Route::RobustPhases) rc = launch_rr3_law_build(h);   // ... and the affine law on that factor
@@ -1927,17 +1981,41 @@ int ddmpc_prepare(ddmpc_handle* h) {
   const size_t ntiles = B * (size_t)(NT * (NT + 1) / 2);
   if (ntiles > 0x7fffffffULL) return fail(DDMPC_ERR_INVALID, "batch too large for ddmpc_prepare");
   // DDMPC_OPT_CONVEX_WARM_LAW: the boxed components and M = K0^-1 E_box, nbox more right-hand sides of the gain kernel
-  const bool cwl = convex_warm_on(h);
+  // Route::BoxLaw: the same for its whole box list, the slack components (CONVEX) and the free input rows of the channels with a
+  // finite bound in ascending row order, with the table of ddmpc_box_law.hpp
+  const bool cwl = convex_warm_on(h) || box;
   int nbox = 0;
   if (cwl) {
     const int RP = 16 * NT;
     std::vector<int> ti(3 * (size_t)RP);
+    if (box) HIP_TRY(hipStreamSynchronize(h->stream));     // (a step in flight may still read the tables written below)
     HIP_TRY(hipMemcpy(ti.data(), h->d_tabi.p, ti.size() * sizeof(int), hipMemcpyDeviceToHost));
     std::vector<int> tab;
     std::vector<int> box_of((size_t)k.r, -1);
+    auto bounded_row = [&](int rho) {
+      const int ch = rho % k.nch;
+      return box && ti[rho] == K_UFREE && (std::isfinite(h->umin_h[ch]) || std::isfinite(h->umax_h[ch]));
+    };
     for (int rho = 0; rho < k.r; ++rho)
-      if (ti[rho] == K_WPRED || ti[rho] == K_WTERM) { box_of[rho] = (int)tab.size(); tab.push_back(rho); }
+      if ((k.convex && (ti[rho] == K_WPRED || ti[rho] == K_WTERM)) || bounded_row(rho)) { box_of[rho] = (int)tab.size(); tab.push_back(rho); }
     nbox = (int)tab.size();
+    if (box) {
+      std::vector<double> td(4 * (size_t)RP);
+      HIP_TRY(hipMemcpy(td.data(), h->d_tabd.p, td.size() * sizeof(double), hipMemcpyDeviceToHost));
+      std::vector<double> bd(5 * (size_t)nbox);
+      for (int s = 0; s < nbox; ++s) {
+        const int rho = tab[s], ch = rho % k.nch;
+        const double D0 = td[rho], D1 = td[RP + rho];
+        const bool inp = ti[rho] == K_UFREE;
+        bd[0 * nbox + s] = inp ? td[2 * RP + rho] : 0.0;
+        bd[1 * nbox + s] = inp ? -k.lam * D0 : k.sig_scale;
+        bd[2 * nbox + s] = inp ? h->umin_h[ch] : -k.bound;
+        bd[3 * nbox + s] = inp ? h->umax_h[ch] : k.bound;
+        bd[4 * nbox + s] = 1.0 / (k.lam * (inp ? D0 : D0 - D1));
+      }
+      if ((rc = h->d_box_bd.ensure(bd.size() * sizeof(double)))) return rc;
+      HIP_TRY(hipMemcpy(h->d_box_bd.p, bd.data(), bd.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
     tab.insert(tab.end(), box_of.begin(), box_of.end());
     if ((rc = h->d_cwl_tab.ensure(tab.size() * sizeof(int))) || (rc = h->d_mcol.ensure(B * (size_t)nbox * k.r * sizeof(double))) ||
         (rc = h->d_cwl_ref.ensure((B + 1) * sizeof(int))))
@@ -2053,6 +2131,8 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
     case DDMPC_OPT_REFINE:
       if (value != DDMPC_REFINE_OFF && value != DDMPC_REFINE_AUTO && value != DDMPC_REFINE_ALWAYS)
         return fail(DDMPC_ERR_INVALID, "refinement mode must be DDMPC_REFINE_OFF, _AUTO or _ALWAYS");
+      if (value == DDMPC_REFINE_ALWAYS && h->bounded)       // (M comes from the unrefined factor: no refined iteration on it)
+        return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_REFINE_ALWAYS is not available on a handle with input bounds (ddmpc_set_input_bounds)");
       h->kp.refine = value;
       forget_prep(h);                   // the affine law is formed from a refined solve of the offset column
       return DDMPC_OK;
@@ -2123,8 +2203,73 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
   }
 }
 
+// With the terminal constraint the last n predicted inputs are fixed to u_s: outside the input bounds the QP is infeasible.
+static const char* setpoint_outside_bounds(const ddmpc_handle* h, const double* u_s, const double* u_min, const double* u_max) {
+  if (!h->prm.use_terminal_constraint) return nullptr;
+  for (int ch = 0; ch < h->prm.m; ++ch)
+    if (u_s[ch] < u_min[ch] || u_s[ch] > u_max[ch]) return "u_s lies outside [u_min, u_max] and the terminal constraint fixes the last n inputs to it";
+  return nullptr;
+}
+
+int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max) {
+  if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
+  if ((u_min == nullptr) != (u_max == nullptr))
+    return fail(DDMPC_ERR_INVALID, "%s is null: pass both u_min and u_max, or neither to remove the bounds", u_min ? "u_max" : "u_min");
+  const ddmpc_params& p = h->prm;
+  bool any = false;
+  if (u_min) {
+    for (int ch = 0; ch < p.m; ++ch) {
+      if (u_min[ch] != u_min[ch]) return fail(DDMPC_ERR_INVALID, "u_min[%d] is NaN", ch);
+      if (u_max[ch] != u_max[ch]) return fail(DDMPC_ERR_INVALID, "u_max[%d] is NaN", ch);
+      if (u_min[ch] >= u_max[ch]) return fail(DDMPC_ERR_INVALID, "u_min[%d] >= u_max[%d]: the box is empty or a point", ch, ch);
+      any = any || std::isfinite(u_min[ch]) || std::isfinite(u_max[ch]);
+    }
+  }
+  if (any) {
+    if (const char* msg = setpoint_outside_bounds(h, h->us_h.data(), u_min, u_max)) return fail(DDMPC_ERR_INVALID, "u_min / u_max: %s", msg);
+    if (p.controller_type != DDMPC_ROBUST)
+      return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: ROBUST controllers only (a NOMINAL one has no regularised reduced system to iterate on)");
+    if (h->large)
+      return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels)", h->kp.r);
+    if (p.weight_kind == DDMPC_WEIGHT_DENSE)
+      return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)");
+    if (p.n * h->kp.nch > WARM_MAX_NF)
+      return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: n*(m+p) = %d, the affine law of ddmpc_prepare holds %d", p.n * h->kp.nch, WARM_MAX_NF);
+    if (h->kp.refine == DDMPC_REFINE_ALWAYS)
+      return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: not with DDMPC_REFINE_ALWAYS (DDMPC_OPT_REFINE must be OFF or AUTO)");
+    const int nfree = p.use_terminal_constraint ? p.L - p.n : p.L;
+    const bool diag = p.weight_kind == DDMPC_WEIGHT_DIAG;
+    for (int ch = 0; ch < p.m; ++ch) {
+      if (!std::isfinite(u_min[ch]) && !std::isfinite(u_max[ch])) continue;
+      for (int kp = 0; kp < nfree; ++kp)
+        if (!((diag ? h->Rh[(size_t)kp * p.m + ch] : h->Rh[0]) > 0.0))
+          return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: channel %d is bounded and has an R entry of 0 on a free prediction step (limit: R > 0 there)", ch);
+    }
+    if (h->kp.convex)        // (the slack components join the box list: each must change its diagonal entry at the bound)
+      for (int i = 0; i < (diag ? nfree * p.p : 1); ++i)
+        if (!(h->Qh[(size_t)i] > 0.0))
+          return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: with the CONVEX slack box every Q entry of a free prediction step must be positive (limit: Q > 0 there)");
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->last.valid = false;
+  forget_prep(h);
+  h->bounded = any;
+  if (!any) { h->umin_h.clear(); h->umax_h.clear(); return DDMPC_OK; }
+  h->umin_h.assign(u_min, u_min + p.m);
+  h->umax_h.assign(u_max, u_max + p.m);
+  std::vector<double> ub(h->umin_h);
+  ub.insert(ub.end(), h->umax_h.begin(), h->umax_h.end());
+  int rc;
+  if ((rc = h->d_ubnd.ensure(ub.size() * sizeof(double)))) { h->bounded = false; return rc; }
+  HIP_TRY(hipMemcpy(h->d_ubnd.p, ub.data(), ub.size() * sizeof(double), hipMemcpyHostToDevice));
+  return DDMPC_OK;
+}
+
 int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s) {
   if (!h || !u_s || !y_s) return fail(DDMPC_ERR_INVALID, "null argument");
+  if (h->bounded)
+    if (const char* msg = setpoint_outside_bounds(h, u_s, h->umin_h.data(), h->umax_h.data())) return fail(DDMPC_ERR_INVALID, "%s", msg);
   HIP_TRY(hipSetDevice(h->device));
   h->us_h.assign(u_s, u_s + h->prm.m);
   h->ys_h.assign(y_s, y_s + h->prm.p);
@@ -2200,7 +2345,8 @@ int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
   hipLaunchKernelGGL(ddmpc_reconstruct_kernel, dim3((unsigned)h->batch), dim3(256), 0, h->stream, k, 16 * h->kc.NT, what, h->ud,
                      h->yd, l.up, l.yp, (const double*)h->d_beta.p, (const signed char*)h->d_act.p, dst,
                      resc ? (const double*)h->d_zws.p : (const double*)nullptr, resc ? (const int*)h->d_resc.p : (const int*)nullptr,
-                     resc ? (const double*)h->d_xws.p : (const double*)nullptr);
+                     resc ? (const double*)h->d_xws.p : (const double*)nullptr,
+                     h->bounded ? (const double*)h->d_ubnd.p : (const double*)nullptr);
   HIP_TRY(hipGetLastError());
   if (mem == DDMPC_MEM_HOST) {
     HIP_TRY(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -2341,8 +2487,9 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   if ((rc = h->d_lwup.ensure(nup)) || (rc = h->d_lwyp.ensure(nyp))) return rc;
   double *lwup = (double*)h->d_lwup.p, *lwyp = (double*)h->d_lwyp.p;
   const bool warm_large = h->large && h->closed_loop_path != DDMPC_PATH_COLD;           // per step, on what ddmpc_prepare kept
-  bool warm = warm_ok && !h->kp.convex && !h->large;   // no inequality: fused loop, one launch
-  const bool warm_box = warm_ok && h->kp.convex && !h->large;     // slack box: per step, affine iterate + cold re-solve where a bound is active
+  const bool ubox = select_route(h) == Route::BoxLaw;  // input bounds: the fused loop of ddmpc_box_law.hpp, or per step ddmpc_solve's sequence
+  bool warm = warm_ok && !h->kp.convex && !h->large && !ubox;   // no inequality: fused loop, one launch
+  const bool warm_box = warm_ok && h->kp.convex && !h->large && !ubox;     // slack box: per step, affine iterate + cold re-solve where a bound is active
   if ((warm_large || warm_box) && (rc = ddmpc_prepare(h))) return rc;
   if (warm && p.controller_type == DDMPC_NOMINAL) {
     // nominal scheme: an instance with a singular Gram matrix (exact data) has no affine law; if there is one,
@@ -2379,6 +2526,20 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
     h->loop_kernel = "ddmpc_closed_loop_convex_warm_kernel";
     warm = true;                                   // (no per-step launches below)
   }
+  if (ubox && warm_ok) {
+    if ((rc = ddmpc_prepare(h))) return rc;
+    if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
+    begin_solve(h, Route::BoxLaw);
+    hipLaunchKernelGGL(ddmpc_closed_loop_box_kernel, dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
+                       16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
+                       (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
+                       (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,
+                       (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                       h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, lwup, lwyp);
+    HIP_TRY(hipGetLastError());
+    h->loop_kernel = "ddmpc_closed_loop_box_kernel";
+    warm = true;                                   // (no per-step launches below)
+  }
   const unsigned pblocks = (unsigned)((B + 127) / 128);
   // The per-step paths are loops of two or three small launches per control step.  Optionally
   // (DDMPC_OPT_CLOSED_LOOP_GRAPH) they are recorded into a HIP graph and replayed with a single launch; all
@@ -2388,7 +2549,7 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   // replayed many times, which a closed loop with new data is not.
   const int n_solves = (n_steps + n_mpc_step - 1) / n_mpc_step;
   bool use_graph = !warm && h->closed_loop_graph && n_solves >= 4 &&
-                   !h->large && p.controller_type != DDMPC_NOMINAL;   // those paths size workspaces / set attributes per launch
+                   !h->large && p.controller_type != DDMPC_NOMINAL && !ubox;   // those paths size workspaces / set attributes per launch
   hipGraph_t graph = nullptr;
   if (!warm) {
     if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;

@@ -30,14 +30,15 @@ __global__ void ddmpc_hankel_kernel(const double* __restrict__ X, double* __rest
 // Variable reconstruction for ddmpc_get_solution (the `.value` stand-ins of
 // controller.py:434-445) from the beta / active-set workspace of the last solve.
 // what: 0 alpha, 1 ubar, 2 ybar, 3 sigma.  One workgroup per instance.
-// `RPs` is the row stride of the component tables.
+// `RPs` is the row stride of the component tables.  `ubnd` (null without input bounds): [u_min (m) | u_max (m)] of
+// ddmpc_set_input_bounds; a free input row in the active set is held at its bound (t = bound, D = 0).
 // --------------------------------------------------------------------------
 __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const double* __restrict__ u_d,
                                          const double* __restrict__ y_d, const double* __restrict__ u_past,
                                          const double* __restrict__ y_past, const double* __restrict__ beta_ws,
                                          const signed char* __restrict__ act_ws, double* __restrict__ out,
                                          const double* __restrict__ z_ws, const int* __restrict__ rescued,
-                                         const double* __restrict__ x_ws) {
+                                         const double* __restrict__ x_ws, const double* __restrict__ ubnd) {
   const long long b = blockIdx.x;
   const int n = P.npu / P.m;
   const bool resc = rescued != nullptr && rescued[b] != 0;
@@ -87,6 +88,7 @@ __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const dou
       for (int j = 0; j < P.r; ++j) sdb += dr[j] * bw[j];
       z = t - P.lam * (D * bb + sdb);
     }
+    if (ubnd != nullptr && kind == K_UFREE && s_act != 0) z = ubnd[(s_act > 0 ? P.m : 0) + ch];
     if (ch < P.m) {
       if (what == 1) out[b * (long long)(P.Ln * P.m) + k * P.m + ch] = z;
       continue;

@@ -1,0 +1,384 @@
+// ddmpc_box_law.hpp -- input bounds u_min <= ubar <= u_max for ROBUST controllers on the register-resident sizes
+// (ddmpc_set_input_bounds, (m+p)(L+n) <= 271): the primal-dual active-set iteration of the warm CONVEX path
+// (ddmpc_aux_kernels.hpp, CwlLds / cwl_iterate) with a per-component description of the box instead of the slack box's
+// symmetric +-bound.  Included by the API translation unit only.
+//
+// A free input row of the reduced system is z_i = t_i - lam D0_i beta_i, D0_i = 1 / w_i.  Holding it at a
+// bound makes the row hard -- D1_i = 0, t_i = bound --, the same diagonal rank-k change of K0 the slack box makes:
+//     K(A) = K0 - E_A diag(d_A) E_A',  d_s = lam (D0_s - D1_s)        t(A) = t0 + E_A shift_A
+//     beta(A) = beta0 + M_A ev,   ev = shift_A + (diag(1/d_A) - M[A,A])^-1 (beta0[A] + M[A,A] shift_A)
+// Boxed components s = 0 .. nbox-1 in ascending row order (the slack components of a CONVEX controller and the free input
+// rows of the channels with a finite bound), shared by the batch and tabulated on the host:
+//     tab = [box_rho (nbox) | box_of (r): s, or -1]
+//     bd  = [a | c | lo | hi | 1/d], nbox doubles each:  hat_s = a_s + c_s beta_rho is the value the component takes when it
+//           is released (for an active one beta_rho is the multiplier: mu_s = 2 w_s (hat_s - bound_s)).  From the empty set: an
+//           inactive component becomes +1 if hat_s > hi_s, -1 if hat_s < lo_s; one at +1 stays while hat_s > hi_s, one at -1
+//           while hat_s < lo_s, and is released otherwise (BoxTab::test);  shift_s = (hi_s or lo_s) - a_s.
+//       slack:  a = 0,  c = -lam / lamb_sigma, lo / hi = -+ c_param eps_max, d = lam (D0 - D1)
+//       input:  a = tb (= u_s), c = -lam D0,   lo / hi = u_min / u_max of the channel (either may be infinite), d = lam D0
+// The k x k system lives in LDS up to CWL_KLDS components and in the instance's slice of `sg` beyond; M = K0^-1 E_box is
+// nbox * r doubles per instance (122 KB at L = 30, n = 4, m = p = 2, CONVEX, both channels bounded: 0.5 GB at 4096 instances).
+#pragma once
+#include "ddmpc_aux_kernels.hpp"
+
+namespace ddmpc {
+
+struct BoxTab {
+  int nbox;
+  const int *rho, *of;
+  const double *a, *c, *lo, *hi, *invd;
+  __device__ __forceinline__ BoxTab(int nbox_, const int* __restrict__ tab, const double* __restrict__ bd)
+      : nbox(nbox_), rho(tab), of(tab + nbox_), a(bd), c(bd + nbox_), lo(bd + 2 * nbox_), hi(bd + 3 * nbox_), invd(bd + 4 * nbox_) {}
+  // the side component j belongs on, given the beta of its row and the side it is on now: an inactive one goes to the bound
+  // it violates; an active one stays while its multiplier has the right sign (hat beyond ITS bound) and is released otherwise
+  // -- never moved to the other bound in one step, the rule of the full-space reference formulation (with a two-sided box
+  // whose width is small against the unconstrained moves, jumping from bound to bound makes the iteration cycle)
+  __device__ __forceinline__ int test(int j, double beta, int cur) const {
+    const double hat = fma(c[j], beta, a[j]);
+    const int up = hat > hi[j], dn = hat < lo[j];
+    return cur > 0 ? up : (cur < 0 ? -dn : up - dn);
+  }
+  __device__ __forceinline__ double bound(int j, int act) const { return act > 0 ? hi[j] : lo[j]; }
+  __device__ __forceinline__ double shift(int j, int act) const { return bound(j, act) - a[j]; }
+};
+
+// The active-set iteration of one instance by the whole workgroup: cwl_iterate with the table (same control flow, same
+// count of solves, status 4 at the cap or on a non-positive pivot of the k x k system; blockDim.x >= r > nbox).
+__device__ int box_iterate(const KParams& P, const BoxTab& T, const double* __restrict__ Mb, double* __restrict__ Sg,
+                           const double* b0, CwlLds& s, int* iters) {
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, r = P.r, nbox = T.nbox;
+  for (int j = tid; j < nbox; j += nthr) { s.bc[j] = b0[T.rho[j]]; s.act[j] = 0; s.slot[j] = -1; }
+  if (tid == 0) { s.kfin = 0; s.fail = 0; s.nslots = 0; }
+  int iter = 1, st = 0;
+  for (;;) {
+    if (tid == 0) s.changed = 0;
+    __syncthreads();
+    for (int j = tid; j < nbox; j += nthr) {
+      const int ns = T.test(j, s.bc[j], s.act[j]);
+      if (ns != s.act[j]) { s.act[j] = (signed char)ns; s.changed = 1; }
+    }
+    __syncthreads();
+    if (!s.changed) break;
+    if (iter >= P.max_iter) { st = 4; break; }
+    ++iter;
+    // the active set in ascending order: one ballot per wave (nbox < blockDim.x: thread s looks at component s)
+    const bool a = tid < nbox && s.act[tid] != 0;
+    const unsigned long long mk = __ballot(a);
+    if (lane == 0) s.wcnt[wave] = __popcll(mk);
+    __syncthreads();
+    int off = 0, k = 0;
+    for (int w = 0; w < (nthr >> 6); ++w) { off += (w < wave) ? s.wcnt[w] : 0; k += s.wcnt[w]; }
+    if (a) s.al[off + __popcll(mk & ((1ull << lane) - 1ull))] = tid;
+    const int n0 = s.nslots;                                          // (read by all before thread 0 changes it)
+    __syncthreads();
+    if (tid == 0) {                                                   // LDS slots for columns that enter A for the first time
+      int ns_ = n0;
+      for (int i = 0; i < k && ns_ < CWL_CC; ++i) {
+        const int j = s.al[i];
+        if (s.slot[j] < 0) { s.slot[j] = ns_; s.slotj[ns_] = j; ++ns_; }
+      }
+      s.nslots = ns_;
+    }
+    __syncthreads();
+    const int n1 = s.nslots;
+    for (int e = tid; e < (n1 - n0) * r; e += nthr) {                 // coalesced r-vectors
+      const int sl = n0 + e / r, rho = e - (e / r) * r;
+      s.Mc[sl][rho] = Mb[(long long)s.slotj[sl] * r + rho];
+    }
+    __syncthreads();
+    // S = diag(1/d_A) - M[A,A] (lower triangle) and the right-hand side beta0[A] + M[A,A] shift_A
+    double* Sp = (k <= CWL_KLDS) ? s.S : Sg;
+    for (int e = tid; e < k * k; e += nthr) {
+      const int i = e / k, l = e - i * k;
+      if (l <= i) {
+        const int ri = T.rho[s.al[i]];
+        double v = -s.m(Mb, r, s.al[l], ri);
+        if (l == i) v += T.invd[s.al[i]];
+        Sp[i * (i + 1) / 2 + l] = v;
+      }
+    }
+    for (int i = tid; i < k; i += nthr) {
+      const int ri = T.rho[s.al[i]];
+      double g = b0[ri];
+      for (int l = 0; l < k; ++l) g += s.m(Mb, r, s.al[l], ri) * T.shift(s.al[l], s.act[s.al[l]]);
+      s.ev[i] = g;
+    }
+    __syncthreads();
+    // Cholesky, right-looking, one column per step
+    for (int c = 0; c < k; ++c) {
+      if (tid == 0) {
+        const double pv = Sp[c * (c + 1) / 2 + c];
+        if (!(pv > 0.0)) s.fail = 1; else Sp[c * (c + 1) / 2 + c] = sqrt(pv);
+      }
+      __syncthreads();
+      if (s.fail) break;
+      const double dc = Sp[c * (c + 1) / 2 + c];
+      for (int i = c + 1 + tid; i < k; i += nthr) Sp[i * (i + 1) / 2 + c] /= dc;
+      __syncthreads();
+      const int nt = k - c - 1;
+      for (int e = tid; e < nt * nt; e += nthr) {
+        const int ii = e / nt, jj = e - ii * nt;
+        if (jj <= ii) {
+          const int i = c + 1 + ii, j = c + 1 + jj;
+          Sp[i * (i + 1) / 2 + j] -= Sp[i * (i + 1) / 2 + c] * Sp[j * (j + 1) / 2 + c];
+        }
+      }
+      __syncthreads();
+    }
+    if (s.fail) { if (tid == 0) s.kfin = 0; st = 4; __syncthreads(); break; }
+    if (tid == 0) {                                                   // L y = g, L' x = y, ev = shift + x
+      for (int i = 0; i < k; ++i) {
+        double v = s.ev[i];
+        for (int l = 0; l < i; ++l) v -= Sp[i * (i + 1) / 2 + l] * s.ev[l];
+        s.ev[i] = v / Sp[i * (i + 1) / 2 + i];
+      }
+      for (int i = k - 1; i >= 0; --i) {
+        double v = s.ev[i];
+        for (int l = i + 1; l < k; ++l) v -= Sp[l * (l + 1) / 2 + i] * s.ev[l];
+        s.ev[i] = v / Sp[i * (i + 1) / 2 + i];
+      }
+      for (int i = 0; i < k; ++i) s.ev[i] += T.shift(s.al[i], s.act[s.al[i]]);
+      s.kfin = k;
+    }
+    __syncthreads();
+    for (int j = tid; j < nbox; j += nthr) s.bc[j] = s.beta(Mb, r, b0[T.rho[j]], T.rho[j]);
+  }
+  *iters = iter;
+  return st;
+}
+
+// Output stage of one component with its active flag (j: its place in the box list, or -1): cwl_component, and an input row
+// held at a bound is that bound exactly (t = bound, D1 = 0); its cost term is the K_UFREE one.
+__device__ __forceinline__ double box_component(const KParams& P, int RPs, const BoxTab& T, int rho, int j, double beta, int sa,
+                                                const double* pv, double* z_out) {
+  const int kind = P.tabi[0 * RPs + rho];
+  const int pidx = P.tabi[1 * RPs + rho];
+  const double D = sa ? P.tabd[1 * RPs + rho] : P.tabd[0 * RPs + rho];
+  const double tb = P.tabd[2 * RPs + rho];
+  const double wq = P.tabd[3 * RPs + rho];
+  const double tp = (pidx >= 0) ? pv[pidx] : tb;
+  double z = tp + sa * P.bound - P.lam * D * beta;
+  if (kind == K_UFREE && sa != 0) z = T.bound(j, sa);
+  double contrib = P.lam * beta * z;
+  if (kind == K_UFREE || kind == K_YFREE) { const double dlt = z - tb; contrib += wq * dlt * dlt; }
+  else if (kind == K_WINT) { const double sg = z - tp; contrib += P.lamb_sigma * sg * sg; }
+  else if (kind == K_WTERM) { const double sg = z - tb; contrib += P.lamb_sigma * sg * sg; }
+  else if (kind == K_WPRED) {
+    const double sg = (sa != 0) ? sa * P.bound : -P.lam * beta / P.lamb_sigma;
+    const double dlt = z - sg - tb;
+    contrib += wq * dlt * dlt + P.lamb_sigma * sg * sg;
+  }
+  *z_out = z;
+  return contrib;
+}
+
+// One control step of a bounded handle for the batch: grid = batch, block = r rounded up to 64 (the geometry of
+// ddmpc_warm_step_kernel): law, violation test with the table, iteration, M_A ev correction, outputs.  Mcol [batch][nbox][r],
+// sg [batch][nbox (nbox + 1) / 2] (used for k > CWL_KLDS only).  No cold hand-over: no cold kernel serves these handles.
+// `refined` (may be null): instances whose law came from refining solves (ddmpc_prepare, AUTO); their M is the unrefined
+// factor's, so a solve of theirs that ends with a non-empty active set is reported optimal_inaccurate.
+__global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
+                                      const int* __restrict__ prep_status, const double* __restrict__ u_past,
+                                      const double* __restrict__ y_past, double* __restrict__ u_opt, double* __restrict__ cost,
+                                      int* __restrict__ status, int* __restrict__ iters, double* __restrict__ beta_ws,
+                                      signed char* __restrict__ act_ws, int nbox, const int* __restrict__ tab,
+                                      const double* __restrict__ bd, const double* __restrict__ Mcol, double* __restrict__ sg,
+                                      const int* __restrict__ refined) {
+  __shared__ double pv[WARM_MAX_NF];
+  __shared__ double red[32];
+  __shared__ double bsh[WARM_MAX_R];
+  __shared__ CwlLds s;
+  const BoxTab T(nbox, tab, bd);
+  const long long b = blockIdx.x;
+  const int tid = threadIdx.x, r = P.r, nrhs = nf + 1;
+  const int nyp = nf - P.npu;
+  for (int f = tid; f < nf; f += blockDim.x)
+    pv[f] = (f < P.npu) ? u_past[b * P.npu + f] : y_past[b * nyp + (f - P.npu)];
+  __syncthreads();
+  const double* g = gain + b * (long long)nrhs * r;
+  int viol = 0;
+  for (int rho = tid; rho < r; rho += blockDim.x) {
+    // all loads of a chunk of 8 columns are issued before they are consumed (HBM-bound: keep bytes in flight)
+    double beta = g[rho];
+    const double* gc = g + r + rho;
+    int f = 0;
+    for (; f + 8 <= nf; f += 8) {
+      double v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = gc[(long long)(f + q) * r];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) beta += pv[f + q] * v[q];
+    }
+    for (; f < nf; ++f) beta += pv[f] * gc[(long long)f * r];
+    bsh[rho] = beta;
+    const int j = T.of[rho];
+    if (j >= 0 && T.test(j, beta, 0) != 0) viol = 1;
+  }
+  viol = __syncthreads_or(viol);
+  int st = prep_status[b], it = 1;
+  const double* Mb = Mcol + b * (long long)nbox * r;
+  const bool iterate = viol && st <= 1;               // (a failed factorisation: nothing to iterate on)
+  if (iterate) {
+    const int dst = box_iterate(P, T, Mb, sg + b * (long long)(nbox * (nbox + 1) / 2), bsh, s, &it);
+    if (dst) st = dst;
+    else if (st == 0 && refined != nullptr && refined[b] != 0 && s.kfin > 0) st = 1;
+  }
+  double part = 0.0;
+  bool finite = true;
+  for (int rho = tid; rho < r; rho += blockDim.x) {
+    double beta = bsh[rho], z;
+    int sa = 0;
+    if (!iterate) {
+      part += warm_component(P, RPs, rho, beta, pv, bsh, &z);
+    } else {
+      const int j = T.of[rho];
+      sa = (j >= 0) ? s.act[j] : 0;
+      beta = s.beta(Mb, r, beta, rho);
+      part += box_component(P, RPs, T, rho, j, beta, sa, pv, &z);
+    }
+    finite = finite && (fabs(beta) < 1e300);
+    const int oidx = P.tabi[2 * RPs + rho];
+    if (oidx >= 0) u_opt[b * (long long)((P.Ln - P.npu / P.m) * P.m) + oidx] = z;
+    beta_ws[b * (long long)P.rE + rho] = beta;
+    act_ws[b * (long long)P.rE + rho] = (signed char)sa;
+  }
+  part = wave_sum(part);
+  const unsigned long long okmask = __ballot(finite);
+  if ((tid & 63) == 0) { red[tid >> 6] = part; red[16 + (tid >> 6)] = (okmask == ~0ull) ? 0.0 : 1.0; }
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0, bad = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { tot += red[w]; bad += red[16 + w]; }
+    if (bad != 0.0 || !(fabs(tot) < 1e300)) st = 4;
+    cost[b] = tot;
+    status[b] = st;
+    if (iters) iters[b] = it;
+  }
+}
+
+// Whole closed loop of one instance of a bounded handle in one workgroup: the twin of ddmpc_closed_loop_convex_warm_kernel
+// (same fixed-size arrays and the same checks of ddmpc_closed_loop behind them).  Per solve the law on the boxed rows and the
+// n_mpc_step * m input rows in use, the iteration of ddmpc_box_step_kernel, the M_A ev correction of those rows, then the
+// plant / FIFO steps of ddmpc_plant_kernel; everything on the last solve.
+__global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
+                                             const int* __restrict__ prep_status, int ns, const double* __restrict__ pl,
+                                             int n_steps, int n_mpc_step, double* __restrict__ x, double* __restrict__ u_past,
+                                             double* __restrict__ y_past, const double* __restrict__ w, double* __restrict__ u_sys,
+                                             double* __restrict__ y_sys, int* __restrict__ status_out, double* __restrict__ beta_ws,
+                                             signed char* __restrict__ act_ws, int nbox, const int* __restrict__ tab,
+                                             const double* __restrict__ bd, const double* __restrict__ Mcol, double* __restrict__ sg,
+                                             const int* __restrict__ refined, double* __restrict__ lw_up, double* __restrict__ lw_yp) {
+  __shared__ double pv[WARM_MAX_NF];
+  __shared__ double uo[WARM_MAX_NF];      // the first n_mpc_step*m entries of optimal_u
+  __shared__ double xs[16], xn[16];       // (ns <= 16 is checked by ddmpc_closed_loop)
+  __shared__ double bsh[WARM_MAX_R];
+  __shared__ CwlLds s;
+  const BoxTab T(nbox, tab, bd);
+  const long long b = blockIdx.x;
+  const int tid = threadIdx.x, r = P.r, nrhs = nf + 1, m = P.m, p = P.p;
+  const int n = P.npu / m, nyp = nf - P.npu;
+  const double* A = pl;
+  const double* Bm = A + ns * ns;
+  const double* C = Bm + ns * m;
+  const double* Dm = C + p * ns;
+  for (int f = tid; f < nf; f += blockDim.x)
+    pv[f] = (f < P.npu) ? u_past[b * P.npu + f] : y_past[b * nyp + (f - P.npu)];
+  if (tid < ns) xs[tid] = x[b * ns + tid];
+  const int st0 = prep_status[b];
+  const bool refd = refined != nullptr && refined[b] != 0;
+  const double nanv = __longlong_as_double(0x7ff8000000000000LL);
+  const double* g = gain + b * (long long)nrhs * r;
+  const double* Mb = Mcol + b * (long long)nbox * r;
+  double* Sg = sg + b * (long long)(nbox * (nbox + 1) / 2);
+  const int nuse = n_mpc_step * m;
+  double* up = pv;
+  double* yp = pv + P.npu;
+  int stc = 0;                                        // worst status so far (ddmpc_plant_kernel's st_acc)
+  for (int t0 = 0; t0 < n_steps; t0 += n_mpc_step) {
+    __syncthreads();
+    const bool last = (t0 + n_mpc_step >= n_steps);
+    if (last)                                         // the window of the last solve, for ddmpc_get_solution
+      for (int f = tid; f < nf; f += blockDim.x) {
+        if (f < P.npu) lw_up[b * P.npu + f] = pv[f]; else lw_yp[b * nyp + (f - P.npu)] = pv[f];
+      }
+    int viol = 0;
+    for (int rho = tid; rho < r; rho += blockDim.x) {
+      const int oidx = P.tabi[2 * RPs + rho];
+      const int j = T.of[rho];
+      if ((oidx >= 0 && oidx < nuse) || j >= 0 || last) {
+        double beta = g[rho];
+        for (int f = 0; f < nf; ++f) beta += pv[f] * g[(long long)(1 + f) * r + rho];
+        bsh[rho] = beta;
+        if (j >= 0 && T.test(j, beta, 0) != 0) viol = 1;
+      }
+    }
+    viol = __syncthreads_or(viol);
+    int st = st0, it = 1;
+    const bool iterate = viol && st <= 1;
+    if (iterate) {
+      const int dst = box_iterate(P, T, Mb, Sg, bsh, s, &it);
+      if (dst) st = dst;
+      else if (st == 0 && refd && s.kfin > 0) st = 1;
+    }
+    int nonfin = 0;
+    for (int rho = tid; rho < r; rho += blockDim.x) {
+      const int oidx = P.tabi[2 * RPs + rho];
+      const int j = T.of[rho];
+      const bool use = oidx >= 0 && oidx < nuse;
+      if (use || j >= 0 || last) {
+        const int sa = (iterate && j >= 0) ? s.act[j] : 0;
+        const double beta = iterate ? s.beta(Mb, r, bsh[rho], rho) : bsh[rho];
+        nonfin |= !(fabs(beta) < 1e300);
+        if (use) {
+          double z;
+          (void)box_component(P, RPs, T, rho, j, beta, sa, pv, &z);
+          uo[oidx] = z;
+        }
+        if (last && beta_ws) { beta_ws[b * (long long)P.rE + rho] = beta; act_ws[b * (long long)P.rE + rho] = (signed char)sa; }
+      }
+    }
+    if (__syncthreads_or(nonfin)) st = 4;
+    stc = (st > stc) ? st : stc;
+    if (tid == 0) {
+      const int nsub = (t0 + n_mpc_step <= n_steps) ? n_mpc_step : n_steps - t0;
+      for (int j = 0; j < nsub; ++j) {
+        const int k = t0 + j;
+        double* us = u_sys + (b * n_steps + k) * m;
+        double* ys = y_sys + (b * n_steps + k) * p;
+        if (stc > 1) {
+          for (int i = 0; i < m; ++i) us[i] = nanv;
+          for (int i = 0; i < p; ++i) ys[i] = nanv;
+          continue;
+        }
+        const double* uk = uo + j * m;
+        const double* wk = w + (b * n_steps + k) * p;
+        for (int i = 0; i < p; ++i) {              // y = C x + D u + w with the state BEFORE the update
+          double sum = wk[i];
+          for (int q = 0; q < ns; ++q) sum += C[i * ns + q] * xs[q];
+          for (int q = 0; q < m; ++q) sum += Dm[i * m + q] * uk[q];
+          ys[i] = sum;
+        }
+        for (int i = 0; i < ns; ++i) {
+          double sum = 0.0;
+          for (int q = 0; q < ns; ++q) sum += A[i * ns + q] * xs[q];
+          for (int q = 0; q < m; ++q) sum += Bm[i * m + q] * uk[q];
+          xn[i] = sum;
+        }
+        for (int i = 0; i < ns; ++i) xs[i] = xn[i];
+        for (int i = 0; i < m; ++i) us[i] = uk[i];
+        for (int i = 0; i < (n - 1) * m; ++i) up[i] = up[i + m];       // FIFO shift
+        for (int i = 0; i < m; ++i) up[(n - 1) * m + i] = uk[i];
+        for (int i = 0; i < (n - 1) * p; ++i) yp[i] = yp[i + p];
+        for (int i = 0; i < p; ++i) yp[(n - 1) * p + i] = ys[i];      // (p is not bounded: no private copy of y)
+      }
+    }
+  }
+  __syncthreads();
+  for (int f = tid; f < nf; f += blockDim.x) {
+    if (f < P.npu) u_past[b * P.npu + f] = pv[f]; else y_past[b * nyp + (f - P.npu)] = pv[f];
+  }
+  if (tid < ns) x[b * ns + tid] = xs[tid];
+  if (tid == 0) status_out[b] = stc;
+}
+
+}  // namespace ddmpc

@@ -236,6 +236,8 @@ class DirectDataDrivenMPCController:
                 use_terminal_constraint=self.use_terminal_constraint, device=self._device)
             self._engine.set_data(np.asarray(self.u_d, dtype=np.float64)[None],
                                   np.asarray(self.y_d, dtype=np.float64)[None])
+            if getattr(self, "_input_bounds", None) is not None:
+                self._engine.set_input_bounds(*self._input_bounds)
         if not hasattr(self, "problem") or self.problem is None:
             self.problem = _Problem(self)
 
@@ -311,6 +313,17 @@ class DirectDataDrivenMPCController:
                 f"{expected_y_dim}. Got {y_past.shape} instead.")
         self.u_past = u_past
         self.y_past = y_past
+
+    def set_input_bounds(self, u_min, u_max) -> None:
+        """Actuator limits u_min <= u <= u_max on the free prediction steps (the input constraint set of the robust scheme;
+        the reference leaves it out): m entries each, -inf / +inf = no bound on that side, both None removes them.  The
+        problem is solved again with them, as after `set_input_output_setpoints`."""
+        if self._engine is not None:
+            self._engine.set_input_bounds(u_min, u_max)
+        self._input_bounds = None if u_min is None and u_max is None else (u_min, u_max)
+        if self._engine is not None:
+            self._cold_solved = False
+            self.problem.solve()
 
     def set_input_output_setpoints(self, u_s: np.ndarray, y_s: np.ndarray) -> None:
         if u_s.shape != self.u_s.shape:                                            # :970-972

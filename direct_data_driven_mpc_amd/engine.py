@@ -344,6 +344,16 @@ class BatchedDDMPC:
         L.check(self._lib.ddmpc_set_setpoints(self._h, C.c_void_p(us.ctypes.data), C.c_void_p(ys.ctypes.data)))
         self._us, self._ys = us, ys
 
+    def set_input_bounds(self, u_min, u_max) -> None:
+        """Box on the predicted inputs of the free prediction steps, u_min[ch] <= ubar[k][ch] <= u_max[ch]
+        (`ddmpc_set_input_bounds`): arrays of m entries (a scalar is broadcast), -inf / +inf = no bound on that side; both
+        None removes the bounds.  ROBUST controllers up to 271 rows with scalar / diagonal weights; takes effect at the next
+        solve and drops the prepared law and the last solution."""
+        lo = None if u_min is None else np.ascontiguousarray(np.broadcast_to(np.asarray(u_min, dtype=np.float64), (self.m,)))
+        hi = None if u_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(u_max, dtype=np.float64), (self.m,)))
+        L.check(self._lib.ddmpc_set_input_bounds(self._h, C.c_void_p(lo.ctypes.data) if lo is not None else C.c_void_p(),
+                                                 C.c_void_p(hi.ctypes.data) if hi is not None else C.c_void_p()))
+
     def get_solution(self, what: str) -> np.ndarray:
         """`.value` of alpha / ubar / ybar / sigma after the last solve (host array)."""
         sel = {"alpha": L.SOL_ALPHA, "ubar": L.SOL_UBAR, "ybar": L.SOL_YBAR, "sigma": L.SOL_SIGMA}[what]

@@ -283,6 +283,38 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value);
 /* set_input_output_setpoints (controller.py:945-982); takes effect at the next solve. */
 int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
 
+/* Box on the predicted inputs: u_min[ch] <= ubar[k][ch] <= u_max[ch] on every FREE prediction step (the rows that
+ * carry R; with the terminal constraint the last n steps stay fixed to u_s) -- the constraint u_k in U of the robust scheme.
+ * u_min, u_max: HOST, [m]; -INFINITY / +INFINITY = no bound on that side; both NULL removes the bounds.  Shared by the batch,
+ * like every controller parameter.  Takes effect at the next solve; forgets what ddmpc_prepare kept and the last solution,
+ * as ddmpc_set_setpoints does (ddmpc_get_solution: DDMPC_ERR_NOT_READY).  Bounds that are all infinite are accepted and leave
+ * every result bit-equal to a handle that never had the call.
+ *   DDMPC_ERR_INVALID: NaN in either array; u_min[ch] >= u_max[ch]; only one pointer NULL; with the terminal constraint, u_s
+ *     outside [u_min, u_max] (the QP is infeasible by construction; ddmpc_set_setpoints checks the same on a bounded handle).
+ *   DDMPC_ERR_UNSUPPORTED: NOMINAL controllers; (m+p)(L+n) > 271; DDMPC_WEIGHT_DENSE; a bounded channel with an R entry of 0 on
+ *     a free prediction step; with the CONVEX slack box a Q entry of 0 on one; DDMPC_REFINE_ALWAYS (refused by ddmpc_set_option
+ *     too once bounds are set); n(m+p) > 256, the one shape for which ddmpc_prepare forms no law at that size (trajectories
+ *     beyond the LDS are served: their law comes from the streamed Gram).  ddmpc_solve_from_host on a bounded handle is
+ *     DDMPC_ERR_UNSUPPORTED.
+ * How a bounded handle is served.  A bound that is active makes its input row hard, a diagonal rank-k change of the system of
+ * the empty active set, exactly what the slack box does.  Every call runs the primal-dual active-set iteration
+ * over the whole box list -- the slack components (CONVEX) and the free input rows of the bounded channels, from the empty set; an
+ * inactive component goes to the bound it violates, an active one is released when its multiplier changes sign (never moved to
+ * the other bound in one step, the rule of the full-space formulation) -- on the affine law and M = K0^-1 E_box that ddmpc_prepare forms
+ * (DDMPC_OPT_CONVEX_WARM_LAW and DDMPC_OPT_CONVEX_UPDATE are accepted and have no effect: the handle is always on the law).
+ * Same solve count, max_iter cap and status 4 (solver_error) at the cap or on a non-positive pivot as under the slack box; a box
+ * tight enough to make the rule cycle ends there.  In the solution an active input equals its bound exactly.
+ *   ddmpc_prepare: law + M, nbox r doubles per instance with nbox = [p L or p (L - n) when CONVEX] + [free steps x bounded
+ *     channels] -- 122 KB at L = 30, n = 4, m = p = 2, CONVEX, both channels bounded: 0.5 GB at 4096 instances -- plus
+ *     nbox (nbox + 1) / 2 doubles of k x k scratch when nbox > 16.  An allocation failure is DDMPC_ERR_HIP.
+ *   ddmpc_step / ddmpc_closed_loop (paths AUTO, WARM: one fused launch, "ddmpc_closed_loop_box_kernel"): no read of the
+ *     trajectories.  Instances whose law ddmpc_prepare took from refining solves (DDMPC_REFINE_AUTO, flagged) iterate on that law
+ *     and the unrefined M like the others and report DDMPC_STATUS_OPTIMAL_INACCURATE when their final active set is not empty.
+ *   ddmpc_solve / DDMPC_PATH_COLD: the cold contract -- the trajectories are read anew, into a preparation of the call's own
+ *     (a second set of the buffers above) that is dropped afterwards; a kept ddmpc_prepare stays valid.
+ *     DDMPC_OPT_CLOSED_LOOP_GRAPH is ignored. */
+int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max);
+
 /* Values of the optimisation variables of the last ddmpc_solve, ddmpc_solve_from_host, ddmpc_step or ddmpc_closed_loop
  * (controller.py:434-445 `.value`); `out` sized as listed at DDMPC_SOL_*.  DDMPC_ERR_NOT_READY before any of them and after
  * ddmpc_set_data, ddmpc_set_setpoints or a ddmpc_prepare on the register-resident kernels ((m+p)(L+n) <= 271); a
@@ -356,7 +388,7 @@ int ddmpc_cost_model(ddmpc_handle* h, double* flops_per_solve, double* bytes_per
 const char* ddmpc_kernel_name(ddmpc_handle* h);
 
 /* Name of the kernel that stepped the plant in the last ddmpc_closed_loop: "ddmpc_closed_loop_warm_kernel" or
- * "ddmpc_closed_loop_convex_warm_kernel" when the whole loop ran fused in one launch, "ddmpc_plant_kernel" when it ran
+ * "ddmpc_closed_loop_convex_warm_kernel" / "ddmpc_closed_loop_box_kernel" (input bounds) when the whole loop ran fused in one launch, "ddmpc_plant_kernel" when it ran
  * per step (DDMPC_PATH_COLD, shapes beyond the fused loops' bounds, NOMINAL instances without a law, laws taken from
  * refining solves under DDMPC_OPT_CONVEX_WARM_LAW, handles beyond 271 rows); "" before the first loop.  Read-only. */
 const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h);
