@@ -255,6 +255,7 @@ struct ddmpc_handle {
   int convex_update = 1;                        // DDMPC_OPT_CONVEX_UPDATE: active-set iterations keep the first factor (rank-k update)
   int convex_warm = 0;                     // DDMPC_OPT_CONVEX_WARM_LAW: warm steps under the slack box run the active-set iteration on the law
   DevBuf d_mcol, d_cwl_tab, d_cwl_sg, d_cwl_ref;   // ... M = K0^-1 E_box [batch][nbox][r]; [box_rho | box_of]; k x k scratch; refined-law flags (+ count)
+  int box_safeguard = 0;                   // DDMPC_OPT_BOX_SAFEGUARD: Route::BoxLaw instances at the max_iter cap are finished by box_safeguard
   // input bounds (ddmpc_set_input_bounds): per channel, +-infinity = none; `bounded` = some bound is finite (Route::BoxLaw)
   std::vector<double> umin_h, umax_h;
   bool bounded = false;
@@ -1366,7 +1367,9 @@ static int launch_box_step(ddmpc_handle* h, const double* up, const double* yp, 
   int rc;
   if ((rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure((size_t)h->batch * h->kp.rE)))
     return rc;
-  hipLaunchKernelGGL(ddmpc_box_step_kernel, dim3((unsigned)h->batch), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
+  // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard: its registers and LDS are the kernel's own)
+  hipLaunchKernelGGL(h->box_safeguard ? ddmpc_box_step_kernel<true> : ddmpc_box_step_kernel<false>, dim3((unsigned)h->batch),
+                     dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
                      16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo,
                      cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox,
                      (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
@@ -2184,6 +2187,10 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       h->convex_warm = value;
       forget_prep(h);
       return DDMPC_OK;
+    case DDMPC_OPT_BOX_SAFEGUARD:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_BOX_SAFEGUARD must be 0 or 1");
+      h->box_safeguard = value;           // (which instantiation of the box kernels is launched: nothing prepared depends on it)
+      return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
       if (value == 1 && !h->gram_valu_ok) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_gram_tiles_kernel stages the whole trajectory in LDS: not at this shape");
@@ -2530,7 +2537,8 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
     if ((rc = ddmpc_prepare(h))) return rc;
     if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
     begin_solve(h, Route::BoxLaw);
-    hipLaunchKernelGGL(ddmpc_closed_loop_box_kernel, dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
+    hipLaunchKernelGGL(h->box_safeguard ? ddmpc_closed_loop_box_kernel<true> : ddmpc_closed_loop_box_kernel<false>,
+                       dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
                        16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
                        (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
                        (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,

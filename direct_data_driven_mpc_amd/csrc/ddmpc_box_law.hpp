@@ -147,6 +147,186 @@ __device__ int box_iterate(const KParams& P, const BoxTab& T, const double* __re
   return st;
 }
 
+// LDS of the safeguard, in the box kernels' SAFE instantiations only (CwlLds is shared with the slack-only kernels and stays
+// as it is): the primal iterate v by boxed component, and one (key, component) pair per wave for the two selections.
+constexpr int BOX_NONE = 0x7fffffff;
+
+struct BoxSafeLds {
+  double v[WARM_MAX_R];
+  double wkey[16];
+  int widx[16];
+};
+
+// The smallest key over the workgroup, the lowest idx among equal keys, to every thread (idx = BOX_NONE: no candidate).
+__device__ __forceinline__ void box_argmin(double& key, int& idx, BoxSafeLds& q) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  for (int o = 32; o > 0; o >>= 1) {
+    const double k2 = __shfl_xor(key, o);
+    const int i2 = __shfl_xor(idx, o);
+    if (k2 < key || (k2 == key && i2 < idx)) { key = k2; idx = i2; }
+  }
+  if (lane == 0) { q.wkey[wave] = key; q.widx[wave] = idx; }
+  __syncthreads();
+  key = q.wkey[0]; idx = q.widx[0];
+  for (int w = 1; w < nw; ++w) {
+    const double k2 = q.wkey[w];
+    const int i2 = q.widx[w];
+    if (k2 < key || (k2 == key && i2 < idx)) { key = k2; idx = i2; }
+  }
+  __syncthreads();
+}
+
+// The solve of box_iterate's loop body for the signed set in s.act, by the whole workgroup (s.act settled by a barrier before
+// the call): the set in ascending order (s.al), LDS slots for columns of M that enter it for the first time, the k x k system,
+// its Cholesky factorisation, ev and s.kfin, then s.bc = the beta of every boxed component (no barrier after it).  True on a
+// non-positive pivot (s.fail; s.kfin = 0: the beta of the empty set).  A twin of that loop body, not a part factored out of it:
+// with the body in a function of its own the compiler allocates the registers of ddmpc_box_step_kernel differently and its
+// default instantiation measured 1.2 % slower than before on [0, 2] at 4096 instances (outside the run-to-run spread), so
+// box_iterate keeps its text and the kernels without the safeguard their code.
+__device__ __forceinline__ bool box_solve_set(const KParams& P, const BoxTab& T, const double* __restrict__ Mb,
+                                              double* __restrict__ Sg, const double* b0, CwlLds& s) {
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, r = P.r, nbox = T.nbox;
+  // the active set in ascending order: one ballot per wave (nbox < blockDim.x: thread s looks at component s)
+  const bool a = tid < nbox && s.act[tid] != 0;
+  const unsigned long long mk = __ballot(a);
+  if (lane == 0) s.wcnt[wave] = __popcll(mk);
+  __syncthreads();
+  int off = 0, k = 0;
+  for (int w = 0; w < (nthr >> 6); ++w) { off += (w < wave) ? s.wcnt[w] : 0; k += s.wcnt[w]; }
+  if (a) s.al[off + __popcll(mk & ((1ull << lane) - 1ull))] = tid;
+  const int n0 = s.nslots;                                          // (read by all before thread 0 changes it)
+  __syncthreads();
+  if (tid == 0) {                                                   // LDS slots for columns that enter A for the first time
+    int ns_ = n0;
+    for (int i = 0; i < k && ns_ < CWL_CC; ++i) {
+      const int j = s.al[i];
+      if (s.slot[j] < 0) { s.slot[j] = ns_; s.slotj[ns_] = j; ++ns_; }
+    }
+    s.nslots = ns_;
+  }
+  __syncthreads();
+  const int n1 = s.nslots;
+  for (int e = tid; e < (n1 - n0) * r; e += nthr) {                 // coalesced r-vectors
+    const int sl = n0 + e / r, rho = e - (e / r) * r;
+    s.Mc[sl][rho] = Mb[(long long)s.slotj[sl] * r + rho];
+  }
+  __syncthreads();
+  // S = diag(1/d_A) - M[A,A] (lower triangle) and the right-hand side beta0[A] + M[A,A] shift_A
+  double* Sp = (k <= CWL_KLDS) ? s.S : Sg;
+  for (int e = tid; e < k * k; e += nthr) {
+    const int i = e / k, l = e - i * k;
+    if (l <= i) {
+      const int ri = T.rho[s.al[i]];
+      double v = -s.m(Mb, r, s.al[l], ri);
+      if (l == i) v += T.invd[s.al[i]];
+      Sp[i * (i + 1) / 2 + l] = v;
+    }
+  }
+  for (int i = tid; i < k; i += nthr) {
+    const int ri = T.rho[s.al[i]];
+    double g = b0[ri];
+    for (int l = 0; l < k; ++l) g += s.m(Mb, r, s.al[l], ri) * T.shift(s.al[l], s.act[s.al[l]]);
+    s.ev[i] = g;
+  }
+  __syncthreads();
+  // Cholesky, right-looking, one column per step
+  for (int c = 0; c < k; ++c) {
+    if (tid == 0) {
+      const double pv = Sp[c * (c + 1) / 2 + c];
+      if (!(pv > 0.0)) s.fail = 1; else Sp[c * (c + 1) / 2 + c] = sqrt(pv);
+    }
+    __syncthreads();
+    if (s.fail) break;
+    const double dc = Sp[c * (c + 1) / 2 + c];
+    for (int i = c + 1 + tid; i < k; i += nthr) Sp[i * (i + 1) / 2 + c] /= dc;
+    __syncthreads();
+    const int nt = k - c - 1;
+    for (int e = tid; e < nt * nt; e += nthr) {
+      const int ii = e / nt, jj = e - ii * nt;
+      if (jj <= ii) {
+        const int i = c + 1 + ii, j = c + 1 + jj;
+        Sp[i * (i + 1) / 2 + j] -= Sp[i * (i + 1) / 2 + c] * Sp[j * (j + 1) / 2 + c];
+      }
+    }
+    __syncthreads();
+  }
+  if (s.fail) { if (tid == 0) s.kfin = 0; __syncthreads(); return true; }
+  if (tid == 0) {                                                   // L y = g, L' x = y, ev = shift + x
+    for (int i = 0; i < k; ++i) {
+      double v = s.ev[i];
+      for (int l = 0; l < i; ++l) v -= Sp[i * (i + 1) / 2 + l] * s.ev[l];
+      s.ev[i] = v / Sp[i * (i + 1) / 2 + i];
+    }
+    for (int i = k - 1; i >= 0; --i) {
+      double v = s.ev[i];
+      for (int l = i + 1; l < k; ++l) v -= Sp[l * (l + 1) / 2 + i] * s.ev[l];
+      s.ev[i] = v / Sp[i * (i + 1) / 2 + i];
+    }
+    for (int i = 0; i < k; ++i) s.ev[i] += T.shift(s.al[i], s.act[s.al[i]]);
+    s.kfin = k;
+  }
+  __syncthreads();
+  for (int j = tid; j < nbox; j += nthr) s.bc[j] = s.beta(Mb, r, b0[T.rho[j]], T.rho[j]);
+  return false;
+}
+
+// DDMPC_OPT_BOX_SAFEGUARD: an instance whose iteration above ended at the max_iter cap is solved again by a primal active-set
+// method on the same law, M and table, by the whole workgroup.  The bounded problem is a strictly convex box QP
+// in the boxed values; box_solve_set is its equality-constrained subproblem for a signed working set W.  From the empty set's
+// law (not from where the iteration stopped: the result does not depend on max_iter): v = clip(hat, lo, hi), W = the violated
+// components.  Per solve, with v+ = hat(W) outside W: a component that would leave the box blocks at
+// alpha = (bound - v) / (v+ - v); the smallest alpha (lowest s on ties) moves v by alpha (v+ - v), and that component joins W at
+// its bound.  With none blocking v = v+, and the active component with the largest g = act (bound - hat) / |c| > 0 -- a
+// multiplier of the wrong sign, lowest s on ties -- is released; none: W is optimal.  The cost falls with every move, so no set
+// comes back.  Status 4 at 4 nbox + 16 solves or on a non-positive pivot.  *solves = the solves; s.act / s.al / s.ev / s.kfin
+// describe the result as after box_iterate (thread s owns component s: blockDim.x > nbox).
+__device__ int box_safeguard(const KParams& P, const BoxTab& T, const double* __restrict__ Mb, double* __restrict__ Sg,
+                             const double* b0, CwlLds& s, BoxSafeLds& q, int* solves) {
+  const int tid = threadIdx.x, nbox = T.nbox, cap = 4 * nbox + 16;
+  const bool own = tid < nbox;
+  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  __syncthreads();                                                    // (everyone has read what box_iterate left)
+  if (own) {
+    const double beta = b0[T.rho[tid]];
+    const int act = T.test(tid, beta, 0);
+    s.act[tid] = (signed char)act;
+    q.v[tid] = act ? T.bound(tid, act) : fma(T.c[tid], beta, T.a[tid]);
+  }
+  if (tid == 0) s.kfin = 0;
+  int n = 0, st = 0;
+  for (;;) {
+    __syncthreads();
+    if (n >= cap) { st = 4; break; }
+    ++n;
+    if (box_solve_set(P, T, Mb, Sg, b0, s)) { st = 4; break; }
+    __syncthreads();
+    const int act = own ? s.act[tid] : 0;
+    const double hat = own ? fma(T.c[tid], s.bc[tid], T.a[tid]) : 0.0;
+    const double vj = own ? q.v[tid] : 0.0;
+    const int side = (own && act == 0) ? (hat > T.hi[tid]) - (hat < T.lo[tid]) : 0;
+    double key = inf;
+    int idx = BOX_NONE;
+    if (side != 0) { key = fmax((T.bound(tid, side) - vj) / (hat - vj), 0.0); idx = tid; }
+    box_argmin(key, idx, q);
+    if (idx != BOX_NONE) {                                             // a blocking component: partial step, it joins W
+      if (tid == idx) { s.act[tid] = (signed char)side; q.v[tid] = T.bound(tid, side); }
+      else if (own && act == 0) q.v[tid] = fma(key, hat - vj, vj);
+      continue;
+    }
+    if (own && act == 0) q.v[tid] = hat;
+    key = inf;
+    if (act != 0) {
+      const double g = act * (T.bound(tid, act) - hat) / fabs(T.c[tid]);
+      if (g > 0.0) { key = -g; idx = tid; }
+    }
+    box_argmin(key, idx, q);
+    if (idx == BOX_NONE) break;                                        // every multiplier has the right sign
+    if (tid == idx) s.act[tid] = 0;                                   // (v stays at the bound it leaves)
+  }
+  *solves = n;
+  return st;
+}
+
 // Output stage of one component with its active flag (j: its place in the box list, or -1): cwl_component, and an input row
 // held at a bound is that bound exactly (t = bound, D1 = 0); its cost term is the K_UFREE one.
 __device__ __forceinline__ double box_component(const KParams& P, int RPs, const BoxTab& T, int rho, int j, double beta, int sa,
@@ -177,6 +357,9 @@ __device__ __forceinline__ double box_component(const KParams& P, int RPs, const
 // sg [batch][nbox (nbox + 1) / 2] (used for k > CWL_KLDS only).  No cold hand-over: no cold kernel serves these handles.
 // `refined` (may be null): instances whose law came from refining solves (ddmpc_prepare, AUTO); their M is the unrefined
 // factor's, so a solve of theirs that ends with a non-empty active set is reported optimal_inaccurate.
+// SAFE (DDMPC_OPT_BOX_SAFEGUARD = 1): an instance that ends at the max_iter cap is finished by box_safeguard; iters = max_iter +
+// its solves.  The host launches <false> when the option is 0: that instantiation is the kernel as it was.
+template <bool SAFE>
 __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                       const int* __restrict__ prep_status, const double* __restrict__ u_past,
                                       const double* __restrict__ y_past, double* __restrict__ u_opt, double* __restrict__ cost,
@@ -219,7 +402,16 @@ __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* 
   const double* Mb = Mcol + b * (long long)nbox * r;
   const bool iterate = viol && st <= 1;               // (a failed factorisation: nothing to iterate on)
   if (iterate) {
-    const int dst = box_iterate(P, T, Mb, sg + b * (long long)(nbox * (nbox + 1) / 2), bsh, s, &it);
+    double* Sg = sg + b * (long long)(nbox * (nbox + 1) / 2);
+    int dst = box_iterate(P, T, Mb, Sg, bsh, s, &it);
+    if constexpr (SAFE) {
+      __shared__ BoxSafeLds q;
+      if (dst == 4 && !s.fail) {                      // at the cap (not a pivot)
+        int more;
+        dst = box_safeguard(P, T, Mb, Sg, bsh, s, q, &more);
+        it += more;
+      }
+    }
     if (dst) st = dst;
     else if (st == 0 && refined != nullptr && refined[b] != 0 && s.kfin > 0) st = 1;
   }
@@ -259,7 +451,9 @@ __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* 
 // Whole closed loop of one instance of a bounded handle in one workgroup: the twin of ddmpc_closed_loop_convex_warm_kernel
 // (same fixed-size arrays and the same checks of ddmpc_closed_loop behind them).  Per solve the law on the boxed rows and the
 // n_mpc_step * m input rows in use, the iteration of ddmpc_box_step_kernel, the M_A ev correction of those rows, then the
-// plant / FIFO steps of ddmpc_plant_kernel; everything on the last solve.
+// plant / FIFO steps of ddmpc_plant_kernel; everything on the last solve.  SAFE: as in ddmpc_box_step_kernel; an instance the
+// safeguard finishes carries on with the loop.
+template <bool SAFE>
 __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                              const int* __restrict__ prep_status, int ns, const double* __restrict__ pl,
                                              int n_steps, int n_mpc_step, double* __restrict__ x, double* __restrict__ u_past,
@@ -316,7 +510,15 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
     int st = st0, it = 1;
     const bool iterate = viol && st <= 1;
     if (iterate) {
-      const int dst = box_iterate(P, T, Mb, Sg, bsh, s, &it);
+      int dst = box_iterate(P, T, Mb, Sg, bsh, s, &it);
+      if constexpr (SAFE) {
+        __shared__ BoxSafeLds q;
+        if (dst == 4 && !s.fail) {
+          int more;
+          dst = box_safeguard(P, T, Mb, Sg, bsh, s, q, &more);
+          it += more;
+        }
+      }
       if (dst) st = dst;
       else if (st == 0 && refd && s.kfin > 0) st = 1;
     }

@@ -238,6 +238,8 @@ class DirectDataDrivenMPCController:
                                   np.asarray(self.y_d, dtype=np.float64)[None])
             if getattr(self, "_input_bounds", None) is not None:
                 self._engine.set_input_bounds(*self._input_bounds)
+            if getattr(self, "_box_safeguard", False):
+                self._engine.set_box_safeguard(True)
         if not hasattr(self, "problem") or self.problem is None:
             self.problem = _Problem(self)
 
@@ -322,6 +324,15 @@ class DirectDataDrivenMPCController:
             self._engine.set_input_bounds(u_min, u_max)
         self._input_bounds = None if u_min is None and u_max is None else (u_min, u_max)
         if self._engine is not None:
+            self._cold_solved = False
+            self.problem.solve()
+
+    def set_box_safeguard(self, on: bool) -> None:
+        """With input bounds: solve a box on which the active-set iteration cycles by a primal active-set method instead of
+        reporting solver_error (`BatchedDDMPC.set_box_safeguard`).  The problem is solved again, as after `set_input_bounds`."""
+        self._box_safeguard = bool(on)
+        if self._engine is not None:
+            self._engine.set_box_safeguard(self._box_safeguard)
             self._cold_solved = False
             self.problem.solve()
 

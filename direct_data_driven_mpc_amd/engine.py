@@ -354,6 +354,13 @@ class BatchedDDMPC:
         L.check(self._lib.ddmpc_set_input_bounds(self._h, C.c_void_p(lo.ctypes.data) if lo is not None else C.c_void_p(),
                                                  C.c_void_p(hi.ctypes.data) if hi is not None else C.c_void_p()))
 
+    def set_box_safeguard(self, on: bool) -> None:
+        """Input bounds: True = an instance whose active-set iteration reaches `max_iter` without a stable set is finished by a
+        primal active-set method instead of reporting solver_error (DDMPC_OPT_BOX_SAFEGUARD; `iters` = max_iter + its solves),
+        False (default) = solver_error at the cap.  Instances below the cap are unchanged; no effect without finite bounds;
+        a kept `prepare` stays valid."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_BOX_SAFEGUARD, 1 if on else 0))
+
     def get_solution(self, what: str) -> np.ndarray:
         """`.value` of alpha / ubar / ybar / sigma after the last solve (host array)."""
         sel = {"alpha": L.SOL_ALPHA, "ubar": L.SOL_UBAR, "ybar": L.SOL_YBAR, "sigma": L.SOL_SIGMA}[what]

@@ -46,6 +46,8 @@ def parse_args():
     ap.add_argument("--plot", default=None, help="write a PNG of the closed-loop inputs/outputs (median, band, instance 0)")
     ap.add_argument("--u_min", type=float, nargs="+", default=None, help="lower input bounds (m values, or one for all channels)")
     ap.add_argument("--u_max", type=float, nargs="+", default=None, help="upper input bounds; give both or neither")
+    ap.add_argument("--box_safeguard", action="store_true",
+                    help="with input bounds: finish solves on which the active-set iteration cycles by a primal active-set method")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     return ap.parse_args()
 
@@ -89,6 +91,8 @@ def main():
         raise ValueError("--u_min and --u_max go together (use inf / -inf for a side without a bound)")
     if a.u_min is not None:
         eng.set_input_bounds(a.u_min if len(a.u_min) > 1 else a.u_min[0], a.u_max if len(a.u_max) > 1 else a.u_max[0])
+    if a.box_safeguard:
+        eng.set_box_safeguard(True)
     eng.set_data(data["u_d"], data["y_d"])
     up = data["u_d"][:, -n:, :].reshape(B, -1)                                   # controller.py:184-185
     yp = data["y_d"][:, -n:, :].reshape(B, -1)

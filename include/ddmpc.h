@@ -162,6 +162,19 @@ extern "C" {
                                          takes the per-step path when there is any.  0 (default) = the filtered cold re-solve.  Setting
                                          it invalidates the prepared law.  DDMPC_ERR_UNSUPPORTED with dense weights, beyond 271 rows and
                                          for a boxed output component without weight (Q entry 0); no effect without the slack box */
+#define DDMPC_OPT_BOX_SAFEGUARD 11      /* handles with input bounds (ddmpc_set_input_bounds): 1 = an instance whose primal-dual active-set
+                                         iteration reaches max_iter without a stable set is not reported DDMPC_STATUS_SOLVER_ERROR but
+                                         solved again, in the same launch, by a primal active-set method on the same law, M and box
+                                         table (one component enters or leaves the working set per solve, the cost falls with every
+                                         move: it ends at the optimum of the strictly convex QP).  It starts from the
+                                         empty set, so the result does not depend on max_iter; `iters` reports max_iter plus its solves
+                                         (at most 4 nbox + 16, status 4 there or on a non-positive pivot).  Instances that converge
+                                         below the cap are bit-equal to 0 in inputs, cost, status and iters.  Honoured by ddmpc_solve,
+                                         ddmpc_step and ddmpc_closed_loop (both paths; in the fused loop such an instance carries on).
+                                         0 (default) = status 4 at the cap.  Values other than 0 / 1: DDMPC_ERR_INVALID.  Accepted on
+                                         any handle, no effect without finite bounds; keeps what ddmpc_prepare kept.  A CONVEX handle
+                                         without bounds keeps the slack-only kernels and is not covered: one finite bound puts it on
+                                         this route */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -303,7 +316,8 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
  * the other bound in one step, the rule of the full-space formulation) -- on the affine law and M = K0^-1 E_box that ddmpc_prepare forms
  * (DDMPC_OPT_CONVEX_WARM_LAW and DDMPC_OPT_CONVEX_UPDATE are accepted and have no effect: the handle is always on the law).
  * Same solve count, max_iter cap and status 4 (solver_error) at the cap or on a non-positive pivot as under the slack box; a box
- * tight enough to make the rule cycle ends there.  In the solution an active input equals its bound exactly.
+ * tight enough to make the rule cycle (width 0.2 around u_s at the data tail) ends there unless DDMPC_OPT_BOX_SAFEGUARD = 1, which
+ * finishes such an instance by a primal active-set method.  In the solution an active input equals its bound exactly.
  *   ddmpc_prepare: law + M, nbox r doubles per instance with nbox = [p L or p (L - n) when CONVEX] + [free steps x bounded
  *     channels] -- 122 KB at L = 30, n = 4, m = p = 2, CONVEX, both channels bounded: 0.5 GB at 4096 instances -- plus
  *     nbox (nbox + 1) / 2 doubles of k x k scratch when nbox > 16.  An allocation failure is DDMPC_ERR_HIP.
