@@ -159,6 +159,19 @@ enum class Route {
                     // law and M = K0^-1 E_box (ddmpc_box_law.hpp); the cold kernels serve its preparation only
 };
 
+// What steps the plant in a ddmpc_closed_loop (select_loop_path): one fused launch, or per control step a solve and
+// ddmpc_plant_kernel.  kLoopKernel is what ddmpc_closed_loop_kernel_name reports.
+enum class LoopPath {
+  FusedAffine,      // affine law, no inequality: the whole loop of an instance inside one workgroup
+  FusedConvex,      // ... with the slack box on the law (DDMPC_OPT_CONVEX_WARM_LAW, no refined law)
+  FusedBox,         // ... with input bounds (Route::BoxLaw)
+  StepPrepared,     // per step, step_on_route on what ddmpc_prepare kept
+  SolvePerStep,     // per step, solve_on_route
+};
+static const char* const kLoopKernel[] = {"ddmpc_closed_loop_warm_kernel", "ddmpc_closed_loop_convex_warm_kernel",
+                                          "ddmpc_closed_loop_box_kernel", "ddmpc_plant_kernel", "ddmpc_plant_kernel"};
+static bool fused(LoopPath p) { return p == LoopPath::FusedAffine || p == LoopPath::FusedConvex || p == LoopPath::FusedBox; }
+
 // What a launch of the global-workspace routes does: the whole solve, the data-dependent factors alone (ddmpc_prepare), or a
 // solve on the factors ddmpc_prepare kept (ddmpc_step).  The values are the template argument of the one-workgroup kernels.
 enum class Stage { Solve = 0, Factors = 1, OnFactors = 2 };
@@ -296,6 +309,15 @@ static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; }
 // A call that writes solve outputs starts the record afresh (nothing of an earlier call survives) and makes it readable at its end.
 static Route begin_solve(ddmpc_handle* h, Route route) { h->last = LastSolve{}; h->last.route = route; return route; }
 static void end_solve(ddmpc_handle* h, const double* up, const double* yp) { h->last.up = up; h->last.yp = yp; h->last.valid = true; }
+
+// A parameter table of upload_params (d_tabi: 3 rows, d_tabd: 4 rows of 16 NT entries) read back to the host.  The blocking copy
+// is also a synchronisation point: ddmpc_prepare without input bounds has no other one before it overwrites d_cwl_tab.
+template <class T>
+static int read_table(const DevBuf& d, size_t count, std::vector<T>* out) {
+  out->resize(count);
+  HIP_TRY(hipMemcpy(out->data(), d.p, count * sizeof(T), hipMemcpyDeviceToHost));
+  return DDMPC_OK;
+}
 
 extern "C" {
 
@@ -1226,13 +1248,20 @@ static void enqueue_cold(ddmpc_handle* h, ColdPass pass, KParams k, ColdArgs a, 
                      (int*)a.iters, a.beta, a.act, a.stamps, a.lfac, a.lfacT, a.flag, a.only, a.nbatch, a.count);
 }
 
+// The beta / active-set workspace of the whole batch (what ddmpc_get_solution reconstructs from).
+static int reserve_beta(ddmpc_handle* h) {
+  const size_t n = (size_t)h->batch * h->kp.rE;
+  if (int rc = h->d_beta.ensure(n * sizeof(double))) return rc;
+  return h->d_act.ensure(n);
+}
+
 // What a handle's cold sequence writes besides its outputs, sized before it is enqueued (ddmpc_closed_loop: before a graph
 // capture, inside which nothing may allocate or set an attribute): beta / active set (ws); under AUTO (flags) the flags + counter
 // word, cleared when first allocated, and beyond the LDS the Hankel sums and Hankel kernel LDS of the streamed residual check.
 static int reserve_cold(ddmpc_handle* h, bool ws, bool flags) {
   const size_t B = (size_t)h->batch, bytes = (B + 1) * sizeof(int);
   int rc;
-  if (ws && ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE)))) return rc;
+  if (ws && (rc = reserve_beta(h))) return rc;
   if (!flags) return DDMPC_OK;
   const bool fresh = h->d_rflag.bytes < bytes;
   if ((rc = h->d_rflag.ensure(bytes))) return rc;
@@ -1318,11 +1347,20 @@ static int launch_cold(ddmpc_handle* h, const double* up, const double* yp, doub
 
 static bool convex_warm_on(const ddmpc_handle* h) { return h->convex_warm && h->kp.convex && !h->large; }
 
+// One evaluation of the affine law ddmpc_prepare kept.  keep: also write the beta / active-set workspace; need: under the slack
+// box, where the kernel marks the instances whose law leaves it.
+static void enqueue_warm_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
+                              int32_t* iters, bool keep, int* need) {
+  hipLaunchKernelGGL(ddmpc_warm_step_kernel, dim3((unsigned)h->batch), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
+                     16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo, cost,
+                     (int*)status, (int*)iters, keep ? (double*)h->d_beta.p : (double*)nullptr,
+                     keep ? (signed char*)h->d_act.p : (signed char*)nullptr, need);
+}
+
 static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost,
                        int32_t* status, int32_t* iters) {
   int rc;
-  if ((rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double)))) return rc;
-  if ((rc = h->d_act.ensure((size_t)h->batch * h->kp.rE))) return rc;
+  if ((rc = reserve_beta(h))) return rc;
   const int nf = h->prm.n * h->kp.nch;
   const unsigned threads = warm_threads(h->kp.r);
   if (convex_warm_on(h)) {
@@ -1350,10 +1388,7 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
   // beta / active set are only needed by ddmpc_get_solution (and by the filtered cold launch below): without the slack
   // box the step skips that 1.2 KB of writes per instance and ddmpc_get_solution re-evaluates the law on demand
   const bool keep = h->kp.convex != 0;
-  hipLaunchKernelGGL(ddmpc_warm_step_kernel, dim3((unsigned)h->batch), dim3(threads), 0, h->stream, h->kp,
-                     16 * h->kc.NT, nf, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo, cost,
-                     (int*)status, (int*)iters, keep ? (double*)h->d_beta.p : (double*)nullptr,
-                     keep ? (signed char*)h->d_act.p : (signed char*)nullptr, need);
+  enqueue_warm_step(h, up, yp, uo, cost, status, iters, keep, need);
   HIP_TRY(hipGetLastError());
   if (!keep) h->last.beta = BetaState::ReEvalLaw;
   // instances with an active slack bound: full active-set solve, same launch geometry, others exit at once
@@ -1364,9 +1399,7 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
 // Route::BoxLaw (input bounds): a control step on what ddmpc_prepare kept -- the law, M for the whole box list and the table.
 static int launch_box_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                            int32_t* iters) {
-  int rc;
-  if ((rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure((size_t)h->batch * h->kp.rE)))
-    return rc;
+  if (int rc = reserve_beta(h)) return rc;
   // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard: its registers and LDS are the kernel's own)
   hipLaunchKernelGGL(h->box_safeguard ? ddmpc_box_step_kernel<true> : ddmpc_box_step_kernel<false>, dim3((unsigned)h->batch),
                      dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
@@ -1911,6 +1944,209 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
   return DDMPC_OK;
 }
 
+// ---- ddmpc_prepare on the register-resident routes (Route::Cold, Route::BoxLaw), step by step ----
+
+// AUTO decides from the exact-Hankel residual of a solve, which depends on the right-hand side -- and the factor-export
+// solve of ddmpc_prepare runs at the ZERO past window (with zero setpoints its right-hand side vanishes: beta = 0, residual 0,
+// nothing would ever be flagged).  So the data sets are probed once more with a plain solve at the window a controller
+// starts from, the last n steps of its own data (controller.py:184-185), and the two sets of flags are joined.
+static int prep_probe_tail(ddmpc_handle* h, const KParams& k0) {
+  const ddmpc_params& p = h->prm;
+  const size_t B = (size_t)h->batch;
+  const int npu = p.n * p.m, npy = p.n * p.p;
+  int rc;
+  if ((rc = h->d_status.ensure(B * sizeof(int32_t))) || (rc = h->d_need.ensure((B + 1) * sizeof(int)))) return rc;
+  double* pu = (double*)h->d_zero.p;
+  double* py = pu + B * (size_t)npu;
+  hipLaunchKernelGGL(ddmpc_tail_past_kernel, dim3((unsigned)((B * (size_t)(npu + npy) + 255) / 256)), dim3(256), 0, h->stream,
+                     (long long)B, p.N, p.m, p.p, p.n, h->ud, h->yd, pu, py);
+  HIP_TRY(hipMemsetAsync(h->d_need.p, 0, (B + 1) * sizeof(int), h->stream));
+  KParams kprobe = k0;
+  kprobe.epoch = h->prep.epoch;
+  if ((rc = gram_pre_launch(h, kprobe, h->ud, h->yd, B, 0, true))) return rc;
+  ColdArgs a{h->ud, h->yd, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p};
+  a.flag = (int*)h->d_need.p; a.count = a.flag + B;
+  enqueue_cold(h, ColdPass::Plain, kprobe, a, B);       // (k0: no slack box, so the plain kernel fn2)
+  hipLaunchKernelGGL(ddmpc_or_flags_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, (long long)B,
+                     h->prep.epoch, (const int*)h->d_need.p, (int*)h->d_rflag.p);
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
+// DDMPC_OPT_CONVEX_WARM_LAW: the boxed components, whose columns M = K0^-1 E_box are nbox more right-hand sides of the gain
+// kernel.  Route::BoxLaw (umin / umax given): the same for its whole box list, the slack components (CONVEX) and the free input
+// rows of the channels with a finite bound in ascending row order, with the table of ddmpc_box_law.hpp.  Host arithmetic on the
+// parameter tables (ti: 3 rows, td: 4 rows of RP entries; td is read under input bounds only).
+struct BoxList {
+  int nbox = 0;
+  std::vector<int> tab;        // [rows of the boxed components | per row its place in the list, or -1]
+  std::vector<double> bd;      // Route::BoxLaw: [a | c | lo | hi | 1/d] per boxed component
+};
+static BoxList build_box_list(const KParams& k, int RP, const std::vector<int>& ti, const std::vector<double>& td,
+                              const double* umin, const double* umax) {
+  const bool box = umin != nullptr;
+  BoxList bl;
+  std::vector<int>& tab = bl.tab;
+  std::vector<int> box_of((size_t)k.r, -1);
+  auto bounded_row = [&](int rho) {
+    const int ch = rho % k.nch;
+    return box && ti[rho] == K_UFREE && (std::isfinite(umin[ch]) || std::isfinite(umax[ch]));
+  };
+  for (int rho = 0; rho < k.r; ++rho)
+    if ((k.convex && (ti[rho] == K_WPRED || ti[rho] == K_WTERM)) || bounded_row(rho)) { box_of[rho] = (int)tab.size(); tab.push_back(rho); }
+  const int nbox = bl.nbox = (int)tab.size();
+  if (box) {
+    bl.bd.resize(5 * (size_t)nbox);
+    for (int s = 0; s < nbox; ++s) {
+      const int rho = tab[s], ch = rho % k.nch;
+      const double D0 = td[rho], D1 = td[RP + rho];
+      const bool inp = ti[rho] == K_UFREE;
+      bl.bd[0 * nbox + s] = inp ? td[2 * RP + rho] : 0.0;
+      bl.bd[1 * nbox + s] = inp ? -k.lam * D0 : k.sig_scale;
+      bl.bd[2 * nbox + s] = inp ? umin[ch] : -k.bound;
+      bl.bd[3 * nbox + s] = inp ? umax[ch] : k.bound;
+      bl.bd[4 * nbox + s] = 1.0 / (k.lam * (inp ? D0 : D0 - D1));
+    }
+  }
+  tab.insert(tab.end(), box_of.begin(), box_of.end());
+  return bl;
+}
+
+// ... its tables on the device, room for M and the k x k scratch beyond the LDS, and the refined-law flags (+ count) cleared.
+static int upload_box_list(ddmpc_handle* h, const BoxList& bl, bool box) {
+  const size_t B = (size_t)h->batch;
+  int rc;
+  if (box) {
+    if ((rc = h->d_box_bd.ensure(bl.bd.size() * sizeof(double)))) return rc;
+    HIP_TRY(hipMemcpy(h->d_box_bd.p, bl.bd.data(), bl.bd.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if ((rc = h->d_cwl_tab.ensure(bl.tab.size() * sizeof(int))) || (rc = h->d_mcol.ensure(B * (size_t)bl.nbox * h->kp.r * sizeof(double))) ||
+      (rc = h->d_cwl_ref.ensure((B + 1) * sizeof(int))))
+    return rc;
+  if (bl.nbox > CWL_KLDS && (rc = h->d_cwl_sg.ensure(B * (size_t)(bl.nbox * (bl.nbox + 1) / 2) * sizeof(double)))) return rc;
+  HIP_TRY(hipMemcpy(h->d_cwl_tab.p, bl.tab.data(), bl.tab.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemsetAsync(h->d_cwl_ref.p, 0, (B + 1) * sizeof(int), h->stream));
+  return DDMPC_OK;
+}
+
+// The affine law (and M for nbox boxed components) by substitutions through the exported factor.
+static int enqueue_gain(ddmpc_handle* h, int nf, int nbox) {
+  const int NT = h->kc.NT;
+  bool launched = false;
+#define DDMPC_INSTANCE(NT_, W_)                                                                              \
+  if (!launched && NT == NT_) {                                                                               \
+    const size_t glds = (size_t)(2 * NT_ * 256 + 32) * sizeof(double);                                        \
+    if (glds > 64 * 1024)                                                                                     \
+      HIP_TRY(raise_lds_limit((const void*)ddmpc_gain_kernel<NT_>, glds)); \
+    hipLaunchKernelGGL(ddmpc_gain_kernel<NT_>, dim3((unsigned)h->batch), dim3(256), glds, h->stream, h->kp, 16 * NT, nf, \
+                       (const double*)h->d_lfac.p, (const double*)h->d_lfacT.p, (const double*)h->d_beta.p,  \
+                       (double*)h->d_gain.p, nbox, (const int*)h->d_cwl_tab.p, (double*)h->d_mcol.p);         \
+    launched = true;                                                                                          \
+  }
+#include "ddmpc_instances.inc"
+#undef DDMPC_INSTANCE
+  if (!launched) return fail(DDMPC_ERR_UNSUPPORTED, "no gain kernel for %d tile rows", NT);
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
+// The substitutions of the gain kernel went through the unrefined factor, whose error is the Gram route's (cond(H) squared).
+// Replace columns of the law by refining cold solves: beta is affine in the past window, so column 1 + f =
+// beta(e_f) - beta(0).  nf + 1 launches of the refining kernel variant, once per data set -- ALWAYS: for every
+// instance; AUTO: a filtered launch that only works on the instances the factor-export launch flagged (it reads one
+// word per workgroup and leaves when there is none: the benchmark data).
+static int prep_refine_columns(ddmpc_handle* h, const KParams& k0) {
+  const ddmpc_params& p = h->prm;
+  const KParams& k = h->kp;
+  const size_t B = (size_t)h->batch;
+  const int nrhs = p.n * k.nch + 1;
+  const bool flagged_only = k.refine == DDMPC_REFINE_AUTO;
+  const int npu = p.n * p.m, npy = p.n * p.p;
+  double* pu = (double*)h->d_zero.p;               // the zero past window of the factor export becomes e_f (its own buffer:
+  double* py = pu + B * (size_t)npu;               // the handle's staging buffers may hold a caller's window)
+  KParams kr = k0;
+  kr.refine = DDMPC_REFINE_ALWAYS;
+  ColdSeq sr; sr.kp = &kr;
+  ColdArgs a{h->ud, h->yd, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p};
+  a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p;
+  const unsigned gp = (unsigned)((B * (size_t)(npu + npy) + 255) / 256), gg = (unsigned)((B * (size_t)k.r + 255) / 256);
+  for (int j = 0; j < nrhs; ++j) {
+    hipLaunchKernelGGL(ddmpc_unit_past_kernel, dim3(gp), dim3(256), 0, h->stream, (long long)B, npu, npy, j - 1,
+                       pu, py);
+    if (!flagged_only) {
+      if (int rc = launch_cold(h, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p, nullptr, sr))
+        return rc;
+    } else {
+      // (trajectory beyond the LDS: the flags are those of the a-priori bound alone, no streamed check)
+      kr.epoch = h->prep.epoch;
+      if (int rc = gram_pre_launch(h, kr, h->ud, h->yd, B, 0, true)) return rc;
+      enqueue_cold(h, ColdPass::Filtered, kr, a, B);
+    }
+    hipLaunchKernelGGL(ddmpc_gain_column_kernel, dim3(gg), dim3(256), 0, h->stream, (long long)B, k.r, k.rE, nrhs, j,
+                       (const double*)h->d_beta.p, (double*)h->d_gain.p,
+                       flagged_only ? (const int*)h->d_rflag.p : (const int*)nullptr, h->prep.epoch);
+  }
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
+// Factor export, AUTO probe, box list, gain launch, refined columns, refined-instance mark and its count, in this order.
+static int prepare_register_resident(ddmpc_handle* h, bool box) {
+  const ddmpc_params& p = h->prm;
+  const KParams& k = h->kp;
+  const int nf = p.n * k.nch, nrhs = nf + 1, NT = h->kc.NT;
+  if (nf > WARM_MAX_NF) return fail(DDMPC_ERR_UNSUPPORTED, "warm path supports n*(m+p) <= %d", WARM_MAX_NF);
+  const size_t B = (size_t)h->batch;
+  const size_t lf_bytes = B * (size_t)(NT * (NT + 1) / 2) * 256 * sizeof(double);
+  h->last.valid = false;                           // (the launches below overwrite the outputs and the workspace of the last solve)
+  int rc;
+  if ((rc = h->d_lfac.ensure(lf_bytes)) || (rc = h->d_lfacT.ensure(lf_bytes)) || (rc = h->d_gain.ensure(B * nrhs * k.r * sizeof(double))) ||
+      (rc = h->d_prep_status.ensure(B * sizeof(int32_t))) || (rc = h->d_zero.ensure(B * nf * sizeof(double))) ||
+      (rc = h->d_uopt.ensure(B * p.L * p.m * sizeof(double))) || (rc = h->d_cost.ensure(B * sizeof(double))))
+    return rc;
+  HIP_TRY(hipMemsetAsync(h->d_zero.p, 0, B * nf * sizeof(double), h->stream));
+  const double* z = (const double*)h->d_zero.p;
+  // one cold factorisation with the factor exported (its solution for a zero past window is discarded)
+  KParams k0 = h->kp;                              // slack box: factor of the EMPTY active set (one iteration)
+  k0.convex = 0;
+  ColdSeq s0; s0.kp = &k0; s0.lfac = (double*)h->d_lfac.p; s0.lfacT = (double*)h->d_lfacT.p;
+  if ((rc = launch_cold(h, z, z + B * p.n * p.m, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p, nullptr, s0)))
+    return rc;
+  const bool refinable = k.lam != 0.0;
+  if (refinable && k.refine == DDMPC_REFINE_AUTO && (rc = prep_probe_tail(h, k0))) return rc;
+  if (B * (size_t)(NT * (NT + 1) / 2) > 0x7fffffffULL) return fail(DDMPC_ERR_INVALID, "batch too large for ddmpc_prepare");
+  const bool cwl = convex_warm_on(h) || box;
+  int nbox = 0;
+  if (cwl) {
+    const int RP = 16 * NT;
+    std::vector<int> ti;
+    std::vector<double> td;
+    if (box) HIP_TRY(hipStreamSynchronize(h->stream));     // (a step in flight may still read the tables written below)
+    if ((rc = read_table(h->d_tabi, 3 * (size_t)RP, &ti)) || (box && (rc = read_table(h->d_tabd, 4 * (size_t)RP, &td)))) return rc;
+    const BoxList bl = build_box_list(k, RP, ti, td, box ? h->umin_h.data() : nullptr, box ? h->umax_h.data() : nullptr);
+    if ((rc = upload_box_list(h, bl, box))) return rc;
+    nbox = bl.nbox;
+  }
+  h->prep.cwl_nbox = nbox;
+  if ((rc = enqueue_gain(h, nf, nbox))) return rc;
+  if (refinable && (k.refine == DDMPC_REFINE_ALWAYS || k.refine == DDMPC_REFINE_AUTO) && (rc = prep_refine_columns(h, k0))) return rc;
+  if (cwl) {
+    // M comes from the unrefined factor: instances whose law was refined keep the filtered cold launch for their box
+    // (ddmpc_step), and their presence sends ddmpc_closed_loop to the per-step path
+    const int mode = refinable ? k.refine : DDMPC_REFINE_OFF;
+    hipLaunchKernelGGL(ddmpc_cwl_mark_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, (long long)B, mode,
+                       h->prep.epoch, (const int*)h->d_rflag.p, (int*)h->d_cwl_ref.p);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->prep.cwl_nref = 0;
+  if (cwl) HIP_TRY(hipMemcpy(&h->prep.cwl_nref, (const int*)h->d_cwl_ref.p + B, sizeof(int), hipMemcpyDeviceToHost));
+  h->d_lfac.release();                           // the factor is only needed to form the gain
+  h->d_lfacT.release();
+  h->prep.valid = true;
+  return DDMPC_OK;
+}
+
 int ddmpc_prepare(ddmpc_handle* h) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
   if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_prepare");
@@ -1939,159 +2175,7 @@ int ddmpc_prepare(ddmpc_handle* h) {
     h->prep.valid = rc == DDMPC_OK;
     return rc;
   }
-  const ddmpc_params& p = h->prm;
-  const KParams& k = h->kp;
-  const int nf = p.n * k.nch, nrhs = nf + 1, NT = h->kc.NT;
-  if (nf > WARM_MAX_NF) return fail(DDMPC_ERR_UNSUPPORTED, "warm path supports n*(m+p) <= %d", WARM_MAX_NF);
-  const size_t B = (size_t)h->batch;
-  const size_t lf_bytes = B * (size_t)(NT * (NT + 1) / 2) * 256 * sizeof(double);
-  h->last.valid = false;                           // (the launches below overwrite the outputs and the workspace of the last solve)
-  int rc;
-  if ((rc = h->d_lfac.ensure(lf_bytes)) || (rc = h->d_lfacT.ensure(lf_bytes)) || (rc = h->d_gain.ensure(B * nrhs * k.r * sizeof(double))) ||
-      (rc = h->d_prep_status.ensure(B * sizeof(int32_t))) || (rc = h->d_zero.ensure(B * nf * sizeof(double))) ||
-      (rc = h->d_uopt.ensure(B * p.L * p.m * sizeof(double))) || (rc = h->d_cost.ensure(B * sizeof(double))))
-    return rc;
-  HIP_TRY(hipMemsetAsync(h->d_zero.p, 0, B * nf * sizeof(double), h->stream));
-  const double* z = (const double*)h->d_zero.p;
-  // one cold factorisation with the factor exported (its solution for a zero past window is discarded)
-  KParams k0 = h->kp;                              // slack box: factor of the EMPTY active set (one iteration)
-  k0.convex = 0;
-  ColdSeq s0; s0.kp = &k0; s0.lfac = (double*)h->d_lfac.p; s0.lfacT = (double*)h->d_lfacT.p;
-  if ((rc = launch_cold(h, z, z + B * p.n * p.m, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p, nullptr, s0)))
-    return rc;
-  if (k.lam != 0.0 && k.refine == DDMPC_REFINE_AUTO) {
-    // AUTO decides from the exact-Hankel residual of a solve, which depends on the right-hand side -- and the factor-export
-    // solve above runs at the ZERO past window (with zero setpoints its right-hand side vanishes: beta = 0, residual 0,
-    // nothing would ever be flagged).  So the data sets are probed once more with a plain solve at the window a controller
-    // starts from, the last n steps of its own data (controller.py:184-185), and the two sets of flags are joined.
-    const int npu = p.n * p.m, npy = p.n * p.p;
-    if ((rc = h->d_status.ensure(B * sizeof(int32_t))) || (rc = h->d_need.ensure((B + 1) * sizeof(int)))) return rc;
-    double* pu = (double*)h->d_zero.p;
-    double* py = pu + B * (size_t)npu;
-    hipLaunchKernelGGL(ddmpc_tail_past_kernel, dim3((unsigned)((B * (size_t)(npu + npy) + 255) / 256)), dim3(256), 0, h->stream,
-                       (long long)B, p.N, p.m, p.p, p.n, h->ud, h->yd, pu, py);
-    HIP_TRY(hipMemsetAsync(h->d_need.p, 0, (B + 1) * sizeof(int), h->stream));
-    KParams kprobe = k0;
-    kprobe.epoch = h->prep.epoch;
-    if ((rc = gram_pre_launch(h, kprobe, h->ud, h->yd, B, 0, true))) return rc;
-    ColdArgs a{h->ud, h->yd, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p};
-    a.flag = (int*)h->d_need.p; a.count = a.flag + B;
-    enqueue_cold(h, ColdPass::Plain, kprobe, a, B);       // (k0: no slack box, so the plain kernel fn2)
-    hipLaunchKernelGGL(ddmpc_or_flags_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, (long long)B,
-                       h->prep.epoch, (const int*)h->d_need.p, (int*)h->d_rflag.p);
-    HIP_TRY(hipGetLastError());
-  }
-  const size_t ntiles = B * (size_t)(NT * (NT + 1) / 2);
-  if (ntiles > 0x7fffffffULL) return fail(DDMPC_ERR_INVALID, "batch too large for ddmpc_prepare");
-  // DDMPC_OPT_CONVEX_WARM_LAW: the boxed components and M = K0^-1 E_box, nbox more right-hand sides of the gain kernel
-  // Route::BoxLaw: the same for its whole box list, the slack components (CONVEX) and the free input rows of the channels with a
-  // finite bound in ascending row order, with the table of ddmpc_box_law.hpp
-  const bool cwl = convex_warm_on(h) || box;
-  int nbox = 0;
-  if (cwl) {
-    const int RP = 16 * NT;
-    std::vector<int> ti(3 * (size_t)RP);
-    if (box) HIP_TRY(hipStreamSynchronize(h->stream));     // (a step in flight may still read the tables written below)
-    HIP_TRY(hipMemcpy(ti.data(), h->d_tabi.p, ti.size() * sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<int> tab;
-    std::vector<int> box_of((size_t)k.r, -1);
-    auto bounded_row = [&](int rho) {
-      const int ch = rho % k.nch;
-      return box && ti[rho] == K_UFREE && (std::isfinite(h->umin_h[ch]) || std::isfinite(h->umax_h[ch]));
-    };
-    for (int rho = 0; rho < k.r; ++rho)
-      if ((k.convex && (ti[rho] == K_WPRED || ti[rho] == K_WTERM)) || bounded_row(rho)) { box_of[rho] = (int)tab.size(); tab.push_back(rho); }
-    nbox = (int)tab.size();
-    if (box) {
-      std::vector<double> td(4 * (size_t)RP);
-      HIP_TRY(hipMemcpy(td.data(), h->d_tabd.p, td.size() * sizeof(double), hipMemcpyDeviceToHost));
-      std::vector<double> bd(5 * (size_t)nbox);
-      for (int s = 0; s < nbox; ++s) {
-        const int rho = tab[s], ch = rho % k.nch;
-        const double D0 = td[rho], D1 = td[RP + rho];
-        const bool inp = ti[rho] == K_UFREE;
-        bd[0 * nbox + s] = inp ? td[2 * RP + rho] : 0.0;
-        bd[1 * nbox + s] = inp ? -k.lam * D0 : k.sig_scale;
-        bd[2 * nbox + s] = inp ? h->umin_h[ch] : -k.bound;
-        bd[3 * nbox + s] = inp ? h->umax_h[ch] : k.bound;
-        bd[4 * nbox + s] = 1.0 / (k.lam * (inp ? D0 : D0 - D1));
-      }
-      if ((rc = h->d_box_bd.ensure(bd.size() * sizeof(double)))) return rc;
-      HIP_TRY(hipMemcpy(h->d_box_bd.p, bd.data(), bd.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    tab.insert(tab.end(), box_of.begin(), box_of.end());
-    if ((rc = h->d_cwl_tab.ensure(tab.size() * sizeof(int))) || (rc = h->d_mcol.ensure(B * (size_t)nbox * k.r * sizeof(double))) ||
-        (rc = h->d_cwl_ref.ensure((B + 1) * sizeof(int))))
-      return rc;
-    if (nbox > CWL_KLDS && (rc = h->d_cwl_sg.ensure(B * (size_t)(nbox * (nbox + 1) / 2) * sizeof(double)))) return rc;
-    HIP_TRY(hipMemcpy(h->d_cwl_tab.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(h->d_cwl_ref.p, 0, (B + 1) * sizeof(int), h->stream));
-  }
-  h->prep.cwl_nbox = nbox;
-  bool launched = false;
-#define DDMPC_INSTANCE(NT_, W_)                                                                              \
-  if (!launched && NT == NT_) {                                                                               \
-    const size_t glds = (size_t)(2 * NT_ * 256 + 32) * sizeof(double);                                        \
-    if (glds > 64 * 1024)                                                                                     \
-      HIP_TRY(raise_lds_limit((const void*)ddmpc_gain_kernel<NT_>, glds)); \
-    hipLaunchKernelGGL(ddmpc_gain_kernel<NT_>, dim3((unsigned)B), dim3(256), glds, h->stream, k, 16 * NT, nf, \
-                       (const double*)h->d_lfac.p, (const double*)h->d_lfacT.p, (const double*)h->d_beta.p,  \
-                       (double*)h->d_gain.p, nbox, (const int*)h->d_cwl_tab.p, (double*)h->d_mcol.p);         \
-    launched = true;                                                                                          \
-  }
-#include "ddmpc_instances.inc"
-#undef DDMPC_INSTANCE
-  if (!launched) return fail(DDMPC_ERR_UNSUPPORTED, "no gain kernel for %d tile rows", NT);
-  HIP_TRY(hipGetLastError());
-  if (k.lam != 0.0 && (k.refine == DDMPC_REFINE_ALWAYS || k.refine == DDMPC_REFINE_AUTO)) {
-    // The substitutions above went through the unrefined factor, whose error is the Gram route's (cond(H) squared).
-    // Replace columns of the law by refining cold solves: beta is affine in the past window, so column 1 + f =
-    // beta(e_f) - beta(0).  nf + 1 launches of the refining kernel variant, once per data set -- ALWAYS: for every
-    // instance; AUTO: a filtered launch that only works on the instances the factor-export launch flagged (it reads one
-    // word per workgroup and leaves when there is none: the benchmark data).
-    const bool flagged_only = k.refine == DDMPC_REFINE_AUTO;
-    const int npu = p.n * p.m, npy = p.n * p.p;
-    double* pu = (double*)h->d_zero.p;               // the zero past window of the launch above becomes e_f (its own buffer:
-    double* py = pu + B * (size_t)npu;               // the handle's staging buffers may hold a caller's window)
-    KParams kr = k0;
-    kr.refine = DDMPC_REFINE_ALWAYS;
-    ColdSeq sr; sr.kp = &kr;
-    ColdArgs a{h->ud, h->yd, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p};
-    a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p;
-    const unsigned gp = (unsigned)((B * (size_t)(npu + npy) + 255) / 256), gg = (unsigned)((B * (size_t)k.r + 255) / 256);
-    for (int j = 0; j < nrhs; ++j) {
-      hipLaunchKernelGGL(ddmpc_unit_past_kernel, dim3(gp), dim3(256), 0, h->stream, (long long)B, npu, npy, j - 1,
-                         pu, py);
-      if (!flagged_only) {
-        if ((rc = launch_cold(h, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p, nullptr, sr)))
-          return rc;
-      } else {
-        // (trajectory beyond the LDS: the flags are those of the a-priori bound alone, no streamed check)
-        kr.epoch = h->prep.epoch;
-        if ((rc = gram_pre_launch(h, kr, h->ud, h->yd, B, 0, true))) return rc;
-        enqueue_cold(h, ColdPass::Filtered, kr, a, B);
-      }
-      hipLaunchKernelGGL(ddmpc_gain_column_kernel, dim3(gg), dim3(256), 0, h->stream, (long long)B, k.r, k.rE, nrhs, j,
-                         (const double*)h->d_beta.p, (double*)h->d_gain.p,
-                         flagged_only ? (const int*)h->d_rflag.p : (const int*)nullptr, h->prep.epoch);
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  if (cwl) {
-    // M comes from the unrefined factor: instances whose law was refined keep the filtered cold launch for their box
-    // (ddmpc_step), and their presence sends ddmpc_closed_loop to the per-step path
-    const int mode = (k.lam != 0.0) ? k.refine : DDMPC_REFINE_OFF;
-    hipLaunchKernelGGL(ddmpc_cwl_mark_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, (long long)B, mode,
-                       h->prep.epoch, (const int*)h->d_rflag.p, (int*)h->d_cwl_ref.p);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->prep.cwl_nref = 0;
-  if (cwl) HIP_TRY(hipMemcpy(&h->prep.cwl_nref, (const int*)h->d_cwl_ref.p + B, sizeof(int), hipMemcpyDeviceToHost));
-  h->d_lfac.release();                           // the factor is only needed to form the gain
-  h->d_lfacT.release();
-  h->prep.valid = true;
-  return DDMPC_OK;
+  return prepare_register_resident(h, box);
 }
 
 int ddmpc_step(ddmpc_handle* h, const double* u_past, const double* y_past, double* u_opt, double* cost,
@@ -2176,10 +2260,10 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
         // every boxed component must change its diagonal entry when its slack reaches the bound (d_s > 0): a zero output
         // weight makes 1/q swallow 1/lamb_sigma
         const int RP = 16 * h->kc.NT;
-        std::vector<double> td(4 * (size_t)RP);
-        std::vector<int> ti(3 * (size_t)RP);
-        HIP_TRY(hipMemcpy(td.data(), h->d_tabd.p, td.size() * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(ti.data(), h->d_tabi.p, ti.size() * sizeof(int), hipMemcpyDeviceToHost));
+        std::vector<double> td;
+        std::vector<int> ti;
+        if (int rc = read_table(h->d_tabd, 4 * (size_t)RP, &td)) return rc;
+        if (int rc = read_table(h->d_tabi, 3 * (size_t)RP, &ti)) return rc;
         for (int rho = 0; rho < h->kp.r; ++rho)
           if ((ti[rho] == K_WPRED || ti[rho] == K_WTERM) && !(td[rho] - td[RP + rho] > 0.0))
             return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_CONVEX_WARM_LAW: a boxed output component has no weight (Q entry 0)");
@@ -2321,10 +2405,8 @@ int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
       if ((rc = launch_cold(h, l.up, l.yp, uo, co, st, it))) return rc;
       break;
     case BetaState::ReEvalLaw:       // evaluate the affine law once more, keeping beta / active set
-      if ((rc = h->d_beta.ensure(B * k.rE * sizeof(double))) || (rc = h->d_act.ensure(B * k.rE))) return rc;
-      hipLaunchKernelGGL(ddmpc_warm_step_kernel, dim3((unsigned)B), dim3(warm_threads(k.r)), 0, h->stream, k, 16 * h->kc.NT,
-                         h->prm.n * k.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, l.up, l.yp, uo, co, (int*)st,
-                         (int*)it, (double*)h->d_beta.p, (signed char*)h->d_act.p, (int*)nullptr);
+      if ((rc = reserve_beta(h))) return rc;
+      enqueue_warm_step(h, l.up, l.yp, uo, co, st, it, true, nullptr);
       HIP_TRY(hipGetLastError());
       break;
   }
@@ -2439,6 +2521,182 @@ int ddmpc_pe_guard(const double* u_d, int64_t batch, int32_t N, int32_t m, int32
   return DDMPC_OK;
 }
 
+// ---- ddmpc_closed_loop ----
+
+// Arguments the three fused closed-loop kernels share, in their order (after the law, around each kernel's own tail); the
+// per-step loop works on the same buffers.
+struct LoopArgs {
+  int ns; const double* pl; int n_steps, n_mpc_step;      // plant [A | B | C | D] and steps
+  double *x, *up, *yp;                                     // state and past windows, moved on in place
+  const double* w;
+  double *usys, *ysys;
+  int* stacc;                                              // status accumulator
+  double* beta = nullptr; signed char* act = nullptr;      // beta / active set of the last solve (launch_fused_loop)
+  double *lwup = nullptr, *lwyp = nullptr;                 // the past window of the last solve
+};
+struct LoopBytes { size_t x, up, yp, w, us; };             // state, windows, w (= y_sys) and u_sys of the whole batch
+
+// The one decision of what steps the plant.  It may call ddmpc_prepare: the prep_status of a NOMINAL handle and the refined
+// laws under the slack box (prep.cwl_nref) are known after it only.  "fits": the fused loops keep the window and the inputs in
+// use in LDS arrays of WARM_MAX_NF doubles, n_mpc_step * m <= WARM_MAX_NF and n (m + p) <= WARM_MAX_NF (ddmpc_plant_kernel sizes
+// nothing by m, p, n or n_mpc_step).  First match:
+//
+//   DDMPC_PATH_COLD                                                     SolvePerStep   no ddmpc_prepare
+//   beyond 271 rows                                                     StepPrepared   ddmpc_prepare
+//   does not fit                                                        SolvePerStep   no ddmpc_prepare
+//   input bounds (Route::BoxLaw)                                        FusedBox       ddmpc_prepare
+//   slack box, DDMPC_OPT_CONVEX_WARM_LAW and no law refined             FusedConvex    ddmpc_prepare
+//   slack box otherwise (affine iterate + filtered cold re-solve)       StepPrepared   ddmpc_prepare
+//   NOMINAL, an instance with a singular Gram matrix (exact data)       SolvePerStep   ddmpc_prepare (its solves go through the
+//                                                                                      rank-revealing rescue kernel: no law)
+//   no inequality otherwise                                             FusedAffine    ddmpc_prepare
+//
+// DDMPC_PATH_WARM and DDMPC_PATH_AUTO choose alike.
+static int select_loop_path(ddmpc_handle* h, int n_mpc_step, LoopPath* path) {
+  const ddmpc_params& p = h->prm;
+  *path = LoopPath::SolvePerStep;
+  if (h->closed_loop_path == DDMPC_PATH_COLD) return DDMPC_OK;
+  const bool fits = (size_t)n_mpc_step * p.m <= (size_t)WARM_MAX_NF && p.n * h->kp.nch <= WARM_MAX_NF;
+  if (!h->large && !fits) return DDMPC_OK;
+  if (int rc = ddmpc_prepare(h)) return rc;
+  if (h->large) {
+    *path = LoopPath::StepPrepared;
+  } else if (select_route(h) == Route::BoxLaw) {
+    *path = LoopPath::FusedBox;
+  } else if (h->kp.convex) {
+    *path = convex_warm_on(h) && h->prep.cwl_nref == 0 ? LoopPath::FusedConvex : LoopPath::StepPrepared;
+  } else {
+    if (p.controller_type == DDMPC_NOMINAL) {
+      std::vector<int32_t> ps((size_t)h->batch);
+      HIP_TRY(hipMemcpy(ps.data(), h->d_prep_status.p, ps.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      for (int32_t st : ps)
+        if (st != 0) return DDMPC_OK;
+    }
+    *path = LoopPath::FusedAffine;
+  }
+  return DDMPC_OK;
+}
+
+// The fused loop of `path`: the whole loop of an instance runs inside one workgroup, active-set iterations included.
+static int launch_fused_loop(ddmpc_handle* h, LoopPath path, LoopArgs a) {
+  if (int rc = reserve_beta(h)) return rc;
+  a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p;
+  begin_solve(h, path == LoopPath::FusedBox ? Route::BoxLaw : Route::Cold);
+  auto launch = [&](auto kernel, auto... tail) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp, 16 * h->kc.NT,
+                       h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps,
+                       a.n_mpc_step, a.x, a.up, a.yp, a.w, a.usys, a.ysys, a.stacc, a.beta, a.act, tail..., a.lwup, a.lwyp);
+  };
+  const int nbox = h->prep.cwl_nbox;
+  const int* tab = (const int*)h->d_cwl_tab.p;
+  const double* mcol = (const double*)h->d_mcol.p;
+  double* sg = (double*)h->d_cwl_sg.p;
+  if (path == LoopPath::FusedAffine) {
+    launch(ddmpc_closed_loop_warm_kernel);
+  } else if (path == LoopPath::FusedConvex) {
+    launch(ddmpc_closed_loop_convex_warm_kernel, nbox, tab, mcol, sg);
+  } else {    // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard, as launch_box_step)
+    const double* bd = (const double*)h->d_box_bd.p;
+    const int* ref = h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr;
+    if (h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true>, nbox, tab, bd, mcol, sg, ref);
+    else launch(ddmpc_closed_loop_box_kernel<false>, nbox, tab, bd, mcol, sg, ref);
+  }
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
+// The per-step paths are loops of two or three small launches per control step.  Optionally
+// (DDMPC_OPT_CLOSED_LOOP_GRAPH) they are recorded into a HIP graph and replayed with a single launch; all
+// buffers the loop touches are sized before the capture starts.  Off by default: measured on MI355X the
+// asynchronous launches already keep the GPU busy (14.8 us per launch, 4096 x 401 one-step loop in 17.8 ms),
+// while instantiating the ~1200-node graph costs more than it saves (25.2 ms) -- it only pays if a graph is
+// replayed many times, which a closed loop with new data is not.
+static int run_step_loop(ddmpc_handle* h, LoopPath path, const LoopArgs& a, const LoopBytes& nb) {
+  const ddmpc_params& p = h->prm;
+  const size_t B = (size_t)h->batch;
+  const Route route = select_route(h);
+  const int n_solves = (a.n_steps + a.n_mpc_step - 1) / a.n_mpc_step;
+  bool use_graph = h->closed_loop_graph && n_solves >= 4 &&
+                   !h->large && p.controller_type != DDMPC_NOMINAL && route != Route::BoxLaw;   // those paths size workspaces / set attributes per launch
+  int rc;
+  if ((rc = reserve_beta(h))) return rc;
+  if (path == LoopPath::StepPrepared && !h->large && (rc = h->d_need.ensure(B * sizeof(int)))) return rc;   // (the slack box: launch_warm)
+  // what launch_cold allocates or sets: sized before a capture starts
+  if (route == Route::Cold && (rc = reserve_cold(h, true, true))) return rc;
+  if (use_graph && hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+    (void)hipGetLastError();                          // e.g. a caller-provided legacy stream: launch the steps directly
+    use_graph = false;
+  }
+  auto enqueue_steps = [&]() -> int {
+    const unsigned pblocks = (unsigned)((B + 127) / 128);
+    for (int t = 0; t < a.n_steps; t += a.n_mpc_step) {
+      if (t + a.n_mpc_step >= a.n_steps) {            // the last solve: keep its window
+        HIP_TRY(hipMemcpyAsync(a.lwup, a.up, nb.up, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(a.lwyp, a.yp, nb.yp, hipMemcpyDeviceToDevice, h->stream));
+      }
+      int rcs = (path == LoopPath::StepPrepared ? step_on_route : solve_on_route)(h, a.up, a.yp, (double*)h->d_uopt.p, (double*)h->d_cost.p,
+                                                                                  (int32_t*)h->d_status.p, nullptr);
+      if (rcs) return rcs;
+      const int nsub = (t + a.n_mpc_step <= a.n_steps) ? a.n_mpc_step : a.n_steps - t;
+      hipLaunchKernelGGL(ddmpc_plant_kernel, dim3(pblocks), dim3(128), 0, h->stream, (long long)B, a.ns, p.m, p.p, p.n,
+                         p.L * p.m, a.pl, t, nsub, a.n_steps, (const double*)h->d_uopt.p,
+                         (const int*)h->d_status.p, a.stacc, a.x, a.up, a.yp, a.w, a.usys, a.ysys);
+      HIP_TRY(hipGetLastError());
+    }
+    return DDMPC_OK;
+  };
+  rc = enqueue_steps();
+  hipGraph_t graph = nullptr;
+  if (rc) {
+    if (use_graph) {                                  // leave the stream usable: close and drop the partial capture
+      (void)hipStreamEndCapture(h->stream, &graph);
+      if (graph) (void)hipGraphDestroy(graph);
+    }
+    return rc;
+  }
+  if (use_graph) {
+    hipGraphExec_t exec = nullptr;
+    HIP_TRY(hipStreamEndCapture(h->stream, &graph));
+    hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (e == hipSuccess) e = hipGraphLaunch(exec, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (exec) (void)hipGraphExecDestroy(exec);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) return fail(DDMPC_ERR_HIP, "closed-loop graph: %s", hipGetErrorString(e));
+  }
+  return DDMPC_OK;
+}
+
+// mem == DDMPC_MEM_HOST: the loop runs on the handle's own buffers, the caller's inputs (user) copied in ...
+static int stage_loop_inputs(ddmpc_handle* h, const LoopBytes& nb, const LoopArgs& user, LoopArgs* a) {
+  int rc;
+  if ((rc = h->d_x.ensure(nb.x)) || (rc = h->d_up.ensure(nb.up)) || (rc = h->d_yp.ensure(nb.yp)) ||
+      (rc = h->d_w.ensure(nb.w)) || (rc = h->d_usys.ensure(nb.us)) || (rc = h->d_ysys.ensure(nb.w)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(h->d_x.p, user.x, nb.x, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_up.p, user.up, nb.up, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_yp.p, user.yp, nb.yp, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_w.p, user.w, nb.w, hipMemcpyHostToDevice, h->stream));
+  a->x = (double*)h->d_x.p; a->up = (double*)h->d_up.p; a->yp = (double*)h->d_yp.p; a->w = (const double*)h->d_w.p;
+  a->usys = (double*)h->d_usys.p; a->ysys = (double*)h->d_ysys.p;
+  return DDMPC_OK;
+}
+
+// ... and its outputs copied out; the accumulated statuses go to the caller's memory either way.
+static int copy_loop_outputs(ddmpc_handle* h, int mem, const LoopBytes& nb, const LoopArgs& a, const LoopArgs& user, int32_t* status) {
+  const bool host = mem == DDMPC_MEM_HOST;
+  if (host) {
+    HIP_TRY(hipMemcpyAsync(user.x, a.x, nb.x, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(user.up, a.up, nb.up, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(user.yp, a.yp, nb.yp, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(user.usys, a.usys, nb.us, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(user.ysys, a.ysys, nb.w, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(status, a.stacc, (size_t)h->batch * sizeof(int32_t), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+  if (host) HIP_TRY(hipStreamSynchronize(h->stream));
+  return DDMPC_OK;
+}
+
 int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps, int32_t n_mpc_step, double* x,
                       double* u_past, double* y_past, const double* w, double* u_sys, double* y_sys,
                       int32_t* status, int mem) {
@@ -2470,153 +2728,21 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   if ((rc = h->d_status.ensure(B * sizeof(int32_t)))) return rc;
   if ((rc = h->d_stacc.ensure(B * sizeof(int32_t)))) return rc;
   HIP_TRY(hipMemsetAsync(h->d_stacc.p, 0, B * sizeof(int32_t), h->stream));
-  double *dx = x, *dup = u_past, *dyp = y_past, *dus = u_sys, *dys = y_sys;
-  const double* dw = w;
-  const size_t nx = B * ns * sizeof(double), nup = B * n * m * sizeof(double), nyp = B * n * pp * sizeof(double);
-  const size_t nw = B * (size_t)n_steps * pp * sizeof(double), nus = B * (size_t)n_steps * m * sizeof(double);
-  if (mem == DDMPC_MEM_HOST) {
-    if ((rc = h->d_x.ensure(nx)) || (rc = h->d_up.ensure(nup)) || (rc = h->d_yp.ensure(nyp)) ||
-        (rc = h->d_w.ensure(nw)) || (rc = h->d_usys.ensure(nus)) || (rc = h->d_ysys.ensure(nw)))
-      return rc;
-    HIP_TRY(hipMemcpyAsync(h->d_x.p, x, nx, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_up.p, u_past, nup, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_yp.p, y_past, nyp, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_w.p, w, nw, hipMemcpyHostToDevice, h->stream));
-    dx = (double*)h->d_x.p; dup = (double*)h->d_up.p; dyp = (double*)h->d_yp.p; dw = (const double*)h->d_w.p;
-    dus = (double*)h->d_usys.p; dys = (double*)h->d_ysys.p;
-  }
-  // the fused loops keep the window and the inputs in use in LDS arrays of WARM_MAX_NF doubles: shapes beyond them take the
-  // per-step path (ddmpc_plant_kernel sizes nothing by m, p, n or n_mpc_step)
-  const bool warm_ok = h->closed_loop_path != DDMPC_PATH_COLD &&
-                       (size_t)n_mpc_step * m <= (size_t)WARM_MAX_NF && n * h->kp.nch <= WARM_MAX_NF;
+  const LoopBytes nb{B * ns * sizeof(double), B * n * m * sizeof(double), B * n * pp * sizeof(double),
+                     B * (size_t)n_steps * pp * sizeof(double), B * (size_t)n_steps * m * sizeof(double)};
+  const LoopArgs user{ns, (const double*)h->d_pl.p, n_steps, n_mpc_step, x, u_past, y_past, w, u_sys, y_sys, (int*)h->d_stacc.p};
+  LoopArgs a = user;
+  if (mem == DDMPC_MEM_HOST && (rc = stage_loop_inputs(h, nb, user, &a))) return rc;
   // the record of the loop is its last solve, at the window that solve saw (the `.value`s the reference holds after its loop):
   // the plant steps that follow it move u_past / y_past on, so that window is kept apart
-  if ((rc = h->d_lwup.ensure(nup)) || (rc = h->d_lwyp.ensure(nyp))) return rc;
-  double *lwup = (double*)h->d_lwup.p, *lwyp = (double*)h->d_lwyp.p;
-  const bool warm_large = h->large && h->closed_loop_path != DDMPC_PATH_COLD;           // per step, on what ddmpc_prepare kept
-  const bool ubox = select_route(h) == Route::BoxLaw;  // input bounds: the fused loop of ddmpc_box_law.hpp, or per step ddmpc_solve's sequence
-  bool warm = warm_ok && !h->kp.convex && !h->large && !ubox;   // no inequality: fused loop, one launch
-  const bool warm_box = warm_ok && h->kp.convex && !h->large && !ubox;     // slack box: per step, affine iterate + cold re-solve where a bound is active
-  if ((warm_large || warm_box) && (rc = ddmpc_prepare(h))) return rc;
-  if (warm && p.controller_type == DDMPC_NOMINAL) {
-    // nominal scheme: an instance with a singular Gram matrix (exact data) has no affine law; if there is one,
-    // run the per-step path, whose solves go through the rank-revealing rescue kernel
-    if ((rc = ddmpc_prepare(h))) return rc;
-    std::vector<int32_t> ps(B);
-    HIP_TRY(hipMemcpy(ps.data(), h->d_prep_status.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < B; ++i)
-      if (ps[i] != 0) { warm = false; break; }
-  }
-  h->loop_kernel = "ddmpc_plant_kernel";
-  if (warm) {
-    // affine control law: the whole loop of an instance runs inside one workgroup
-    if ((rc = ddmpc_prepare(h))) return rc;
-    h->loop_kernel = "ddmpc_closed_loop_warm_kernel";
-    if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
-    begin_solve(h, Route::Cold);
-    hipLaunchKernelGGL(ddmpc_closed_loop_warm_kernel, dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
-                       16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
-                       (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
-                       (double*)h->d_beta.p, (signed char*)h->d_act.p, lwup, lwyp);
-    HIP_TRY(hipGetLastError());
-  }
-  if (warm_box && convex_warm_on(h) && h->prep.cwl_nref == 0) {
-    // DDMPC_OPT_CONVEX_WARM_LAW: the whole loop of an instance in one workgroup, active-set iterations included
-    if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
-    begin_solve(h, Route::Cold);
-    hipLaunchKernelGGL(ddmpc_closed_loop_convex_warm_kernel, dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
-                       16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
-                       (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
-                       (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,
-                       (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p, lwup, lwyp);
-    HIP_TRY(hipGetLastError());
-    h->loop_kernel = "ddmpc_closed_loop_convex_warm_kernel";
-    warm = true;                                   // (no per-step launches below)
-  }
-  if (ubox && warm_ok) {
-    if ((rc = ddmpc_prepare(h))) return rc;
-    if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
-    begin_solve(h, Route::BoxLaw);
-    hipLaunchKernelGGL(h->box_safeguard ? ddmpc_closed_loop_box_kernel<true> : ddmpc_closed_loop_box_kernel<false>,
-                       dim3((unsigned)B), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
-                       16 * h->kc.NT, n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, ns,
-                       (const double*)h->d_pl.p, n_steps, n_mpc_step, dx, dup, dyp, dw, dus, dys, (int*)h->d_stacc.p,
-                       (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,
-                       (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
-                       h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, lwup, lwyp);
-    HIP_TRY(hipGetLastError());
-    h->loop_kernel = "ddmpc_closed_loop_box_kernel";
-    warm = true;                                   // (no per-step launches below)
-  }
-  const unsigned pblocks = (unsigned)((B + 127) / 128);
-  // The per-step paths are loops of two or three small launches per control step.  Optionally
-  // (DDMPC_OPT_CLOSED_LOOP_GRAPH) they are recorded into a HIP graph and replayed with a single launch; all
-  // buffers the loop touches are sized before the capture starts.  Off by default: measured on MI355X the
-  // asynchronous launches already keep the GPU busy (14.8 us per launch, 4096 x 401 one-step loop in 17.8 ms),
-  // while instantiating the ~1200-node graph costs more than it saves (25.2 ms) -- it only pays if a graph is
-  // replayed many times, which a closed loop with new data is not.
-  const int n_solves = (n_steps + n_mpc_step - 1) / n_mpc_step;
-  bool use_graph = !warm && h->closed_loop_graph && n_solves >= 4 &&
-                   !h->large && p.controller_type != DDMPC_NOMINAL && !ubox;   // those paths size workspaces / set attributes per launch
-  hipGraph_t graph = nullptr;
-  if (!warm) {
-    if ((rc = h->d_beta.ensure(B * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure(B * h->kp.rE))) return rc;
-    if (warm_box && (rc = h->d_need.ensure(B * sizeof(int)))) return rc;
-    // what launch_cold allocates or sets: sized before a capture starts
-    if (select_route(h) == Route::Cold && (rc = reserve_cold(h, true, true))) return rc;
-  }
-  if (use_graph && hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    (void)hipGetLastError();                          // e.g. a caller-provided legacy stream: launch the steps directly
-    use_graph = false;
-  }
-  auto enqueue_steps = [&]() -> int {
-    for (int t = 0; !warm && t < n_steps; t += n_mpc_step) {
-      if (t + n_mpc_step >= n_steps) {                // the last solve: keep its window
-        HIP_TRY(hipMemcpyAsync(lwup, dup, nup, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(lwyp, dyp, nyp, hipMemcpyDeviceToDevice, h->stream));
-      }
-      int rcs = (warm_box || warm_large ? step_on_route : solve_on_route)(h, dup, dyp, (double*)h->d_uopt.p, (double*)h->d_cost.p,
-                                                                          (int32_t*)h->d_status.p, nullptr);
-      if (rcs) return rcs;
-      const int nsub = (t + n_mpc_step <= n_steps) ? n_mpc_step : n_steps - t;
-      hipLaunchKernelGGL(ddmpc_plant_kernel, dim3(pblocks), dim3(128), 0, h->stream, (long long)B, ns, m, pp, n,
-                         p.L * m, (const double*)h->d_pl.p, t, nsub, n_steps, (const double*)h->d_uopt.p,
-                         (const int*)h->d_status.p, (int*)h->d_stacc.p, dx, dup, dyp, dw, dus, dys);
-      HIP_TRY(hipGetLastError());
-    }
-    return DDMPC_OK;
-  };
-  rc = enqueue_steps();
-  if (rc) {
-    if (use_graph) {                                  // leave the stream usable: close and drop the partial capture
-      (void)hipStreamEndCapture(h->stream, &graph);
-      if (graph) (void)hipGraphDestroy(graph);
-    }
-    return rc;
-  }
-  if (use_graph) {
-    hipGraphExec_t exec = nullptr;
-    HIP_TRY(hipStreamEndCapture(h->stream, &graph));
-    hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (e == hipSuccess) e = hipGraphLaunch(exec, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (exec) (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) return fail(DDMPC_ERR_HIP, "closed-loop graph: %s", hipGetErrorString(e));
-  }
-  end_solve(h, lwup, lwyp);        // (the last solve's window: the per-step cold path re-solves there, the other paths wrote its beta)
-  if (mem == DDMPC_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(x, dx, nx, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(u_past, dup, nup, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(y_past, dyp, nyp, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(u_sys, dus, nus, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(y_sys, dys, nw, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(status, h->d_stacc.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  } else {
-    HIP_TRY(hipMemcpyAsync(status, h->d_stacc.p, B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
-  }
-  return DDMPC_OK;
+  if ((rc = h->d_lwup.ensure(nb.up)) || (rc = h->d_lwyp.ensure(nb.yp))) return rc;
+  a.lwup = (double*)h->d_lwup.p; a.lwyp = (double*)h->d_lwyp.p;
+  LoopPath path;
+  if ((rc = select_loop_path(h, n_mpc_step, &path))) return rc;
+  h->loop_kernel = kLoopKernel[(int)path];
+  if ((rc = fused(path) ? launch_fused_loop(h, path, a) : run_step_loop(h, path, a, nb))) return rc;
+  end_solve(h, a.lwup, a.lwyp);    // (the last solve's window: the per-step cold path re-solves there, the other paths wrote its beta)
+  return copy_loop_outputs(h, mem, nb, a, user, status);
 }
 
 int ddmpc_cost_model(ddmpc_handle* h, double* flops_per_solve, double* bytes_per_solve) {

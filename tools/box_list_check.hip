@@ -1,0 +1,44 @@
+// Host check of build_box_list (ddmpc_api.hip) under the address and undefined-behaviour sanitizers: no device is used.
+//
+//   python -m direct_data_driven_mpc_amd.build
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Xarch_host -fsanitize=address,undefined -Idirect_data_driven_mpc_amd/csrc \
+//         -c tools/box_list_check.hip -o tools/box_list_check.o
+//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined tools/box_list_check.o direct_data_driven_mpc_amd/_build/ddmpc_inst*.o \
+//         -o tools/box_list_check && tools/box_list_check
+//
+// A 22-row (m = p = 1, L = 10, n = 1) and a 136-row (m = p = 2, L = 30, n = 4) table with the terminal constraint, with and
+// without the CONVEX slack box, without input bounds, with one channel bounded and with all of them.  The vectors have exactly
+// the sizes ddmpc_prepare passes, so a read or write past them is reported.
+#include "../direct_data_driven_mpc_amd/csrc/ddmpc_api.hip"
+
+int main() {
+  const double inf = std::numeric_limits<double>::infinity();
+  const int shapes[2][4] = {{1, 11, 1, 2}, {2, 34, 4, 9}};     // m (= p), L + n, n, tile rows NT
+  int bad = 0;
+  for (const auto& sh : shapes)
+    for (int convex = 0; convex < 2; ++convex)
+      for (int bounded = 0; bounded <= sh[0]; bounded += std::max(1, sh[0] - 1)) {   // channels with a finite bound: 0, 1, all
+        const int m = sh[0], nch = 2 * m, Ln = sh[1], n = sh[2], RP = 16 * sh[3], nfree = Ln - 2 * n;
+        KParams k{};
+        k.nch = nch; k.r = nch * Ln; k.convex = convex; k.lam = 0.04; k.sig_scale = -8e-5; k.bound = 0.002;
+        std::vector<int> ti(3 * (size_t)RP, K_UFIX);
+        std::vector<double> td(4 * (size_t)RP, 0.0);
+        for (int rho = 0; rho < k.r; ++rho) {
+          const int step = rho / nch, ch = rho % nch;
+          const bool pred = step >= n, term = step >= Ln - n;
+          ti[rho] = ch < m ? (pred && !term ? K_UFREE : K_UFIX) : (!pred ? K_WINT : term ? K_WTERM : K_WPRED);
+          td[rho] = 2.0 + ch; td[RP + rho] = 0.5; td[2 * RP + rho] = 1.0;
+        }
+        std::vector<double> lo(m, -inf), hi(m, inf);
+        for (int ch = 0; ch < bounded; ++ch) { lo[ch] = -4.0; hi[ch] = 6.0; }
+        const BoxList bl = bounded ? build_box_list(k, RP, ti, td, lo.data(), hi.data())
+                                   : build_box_list(k, RP, ti, std::vector<double>(), nullptr, nullptr);
+        const int want = (convex ? m * (Ln - n) : 0) + bounded * nfree;
+        bool ok = bl.nbox == want && bl.tab.size() == (size_t)(want + k.r) && bl.bd.size() == (bounded ? 5 * (size_t)want : 0);
+        for (int s = 0; ok && s < bl.nbox; ++s)
+          ok = bl.tab[bl.nbox + bl.tab[s]] == s && (s == 0 || bl.tab[s] > bl.tab[s - 1]) && (!bounded || std::isfinite(bl.bd[4 * want + s]));
+        printf("%3d rows  convex %d  bounded channels %d: nbox %3d (want %3d) %s\n", k.r, convex, bounded, bl.nbox, want, ok ? "ok" : "BAD");
+        bad += !ok;
+      }
+  return bad != 0;
+}
