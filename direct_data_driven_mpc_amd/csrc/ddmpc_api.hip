@@ -204,6 +204,7 @@ struct Prep {
   bool law = false;                        // beyond 271 rows: the affine law was formed (DDMPC_OPT_LARGE_AFFINE_LAW)
   int r3_nolaw = 0;                        // ... ROBUST: instances whose law missed the refinement threshold (their steps take the filtered re-solve)
   int cwl_nbox = 0;                        // DDMPC_OPT_CONVEX_WARM_LAW, Route::BoxLaw: boxed components
+  int box_threads = 0;                     // Route::BoxLaw: block of the box kernels (max(r, nbox) rounded up to 64)
   int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch;
                                            //     BoxLaw: they iterate like the others and report optimal_inaccurate with a non-empty active set)
   int epoch = 0;                           // stamp of the flags recorded by the factor-export launch (AUTO)
@@ -269,10 +270,11 @@ struct ddmpc_handle {
   int convex_warm = 0;                     // DDMPC_OPT_CONVEX_WARM_LAW: warm steps under the slack box run the active-set iteration on the law
   DevBuf d_mcol, d_cwl_tab, d_cwl_sg, d_cwl_ref;   // ... M = K0^-1 E_box [batch][nbox][r]; [box_rho | box_of]; k x k scratch; refined-law flags (+ count)
   int box_safeguard = 0;                   // DDMPC_OPT_BOX_SAFEGUARD: Route::BoxLaw instances at the max_iter cap are finished by box_safeguard
-  // input bounds (ddmpc_set_input_bounds): per channel, +-infinity = none; `bounded` = some bound is finite (Route::BoxLaw)
-  std::vector<double> umin_h, umax_h;
+  // input bounds (ddmpc_set_input_bounds) and output bounds (ddmpc_set_output_bounds): per channel, +-infinity = none; the
+  // vectors are empty without a finite bound of their kind; `bounded` = some bound of either kind is finite (Route::BoxLaw)
+  std::vector<double> umin_h, umax_h, ymin_h, ymax_h;
   bool bounded = false;
-  DevBuf d_box_bd, d_ubnd;                 // ... [a | c | lo | hi | 1/d] of the box list (ddmpc_box_law.hpp); [u_min | u_max] for the reconstruction
+  DevBuf d_box_bd, d_ubnd, d_ybnd;         // ... [a | c | lo | hi | 1/d] of the box list (ddmpc_box_law.hpp); [u_min | u_max], [y_min | y_max] for the reconstruction
   DevBuf s_gain, s_prep_status, s_mcol, s_cwl_ref;   // ... the preparation of ddmpc_solve's own (solve_box): a kept ddmpc_prepare survives the solve
   int epoch = 0;                           // cold launches so far (KParams::epoch)
   int flag_epoch = 0;                      // latest stamp written into d_rflag
@@ -808,7 +810,7 @@ int ddmpc_destroy(ddmpc_handle* h) {
                     &h->d_pl, &h->d_x, &h->d_w, &h->d_usys, &h->d_ysys, &h->d_stacc,
                     &h->d_lfac, &h->d_lfacT, &h->d_gain, &h->d_prep_status, &h->d_zero, &h->d_dmat, &h->d_need, &h->d_io, &h->d_rr, &h->d_alpha, &h->d_zws, &h->d_resc, &h->d_xws, &h->d_rflag, &h->d_rrmeta, &h->d_gpre, &h->d_perm, &h->d_rr2d, &h->d_rr2res, &h->d_rr2mt, &h->d_rr2v, &h->d_rr2zp, &h->d_rr2sc, &h->d_wz, &h->d_gz, &h->d_gres, &h->d_zvirt, &h->d_rr3w, &h->d_rr3k, &h->d_rr_fb, &h->d_rrmeta_fb, &h->d_rr2cand, &h->d_rr2tol, &h->d_rr2rank, &h->d_wd, &h->d_rr2y,
                     &h->d_mcol, &h->d_cwl_tab, &h->d_cwl_sg, &h->d_cwl_ref, &h->d_r3y, &h->d_r3res, &h->d_r3zp, &h->d_r3flag,
-                    &h->d_box_bd, &h->d_ubnd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp};
+                    &h->d_box_bd, &h->d_ubnd, &h->d_ybnd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp};
   for (DevBuf* b : bufs) b->release();
   h->h_io.release();
   h->h_flag.release();
@@ -1401,8 +1403,12 @@ static int launch_box_step(ddmpc_handle* h, const double* up, const double* yp, 
                            int32_t* iters) {
   if (int rc = reserve_beta(h)) return rc;
   // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard: its registers and LDS are the kernel's own)
-  hipLaunchKernelGGL(h->box_safeguard ? ddmpc_box_step_kernel<true> : ddmpc_box_step_kernel<false>, dim3((unsigned)h->batch),
-                     dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
+  // (output bounds: the instantiations with the output components, block = max(r, nbox) rounded up to 64)
+  const bool yb = !h->ymin_h.empty();
+  auto kernel = yb ? (h->box_safeguard ? ddmpc_box_step_kernel<true, true> : ddmpc_box_step_kernel<false, true>)
+                   : (h->box_safeguard ? ddmpc_box_step_kernel<true, false> : ddmpc_box_step_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch),
+                     dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0, h->stream, h->kp,
                      16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo,
                      cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox,
                      (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
@@ -1846,6 +1852,9 @@ int ddmpc_solve_from_host(ddmpc_handle* h, const double* u_d, const double* y_d,
   if (!h || !u_d || !y_d || !u_past || !y_past || !u_opt || !cost || !status)
     return fail(DDMPC_ERR_INVALID, "null argument");
   if (h->batch > 0x7fffffffLL) return fail(DDMPC_ERR_INVALID, "batch too large for one launch");
+  if (h->bounded && h->umin_h.empty())
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_solve_from_host does not serve a handle with output bounds (ddmpc_set_output_bounds): "
+                "use ddmpc_set_data + ddmpc_solve");
   if (h->bounded)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_solve_from_host does not serve a handle with input bounds (ddmpc_set_input_bounds): "
                 "use ddmpc_set_data + ddmpc_solve");
@@ -1976,31 +1985,54 @@ static int prep_probe_tail(ddmpc_handle* h, const KParams& k0) {
 // DDMPC_OPT_CONVEX_WARM_LAW: the boxed components, whose columns M = K0^-1 E_box are nbox more right-hand sides of the gain
 // kernel.  Route::BoxLaw (umin / umax given): the same for its whole box list, the slack components (CONVEX) and the free input
 // rows of the channels with a finite bound in ascending row order, with the table of ddmpc_box_law.hpp.  Host arithmetic on the
-// parameter tables (ti: 3 rows, td: 4 rows of RP entries; td is read under input bounds only).
+// parameter tables (ti: 3 rows, td: 4 rows of RP entries; td is read under bounds only).  Output bounds (ymin / ymax given) add
+// the K_WPRED rows of the channels with a finite bound as components of a third kind, after the slack component of the same
+// row where there is one; the two share their column of M, so M is keyed by boxed row (ncol <= nbox columns) and the table
+// grows by [col | box_ofy | ncol | col_rho] (ddmpc_box_law.hpp).  Without them the list is the one it was.
 struct BoxList {
   int nbox = 0;
-  std::vector<int> tab;        // [rows of the boxed components | per row its place in the list, or -1]
+  int ncol = 0;                // columns of M: the boxed rows (= nbox without output bounds)
+  std::vector<int> tab;        // [rows of the boxed components | per row its place in the list, or -1]  (+ the output part)
   std::vector<double> bd;      // Route::BoxLaw: [a | c | lo | hi | 1/d] per boxed component
 };
 static BoxList build_box_list(const KParams& k, int RP, const std::vector<int>& ti, const std::vector<double>& td,
-                              const double* umin, const double* umax) {
-  const bool box = umin != nullptr;
+                              const double* umin, const double* umax, const double* ymin = nullptr, const double* ymax = nullptr) {
+  const bool box = umin != nullptr || ymin != nullptr;
   BoxList bl;
   std::vector<int>& tab = bl.tab;
-  std::vector<int> box_of((size_t)k.r, -1);
+  std::vector<int> box_of((size_t)k.r, -1), box_ofy, col, col_rho;
+  std::vector<char> outp;      // per component: the output of its row
+  if (ymin) box_ofy.assign((size_t)k.r, -1);
   auto bounded_row = [&](int rho) {
     const int ch = rho % k.nch;
-    return box && ti[rho] == K_UFREE && (std::isfinite(umin[ch]) || std::isfinite(umax[ch]));
+    return umin != nullptr && ti[rho] == K_UFREE && (std::isfinite(umin[ch]) || std::isfinite(umax[ch]));
   };
-  for (int rho = 0; rho < k.r; ++rho)
-    if ((k.convex && (ti[rho] == K_WPRED || ti[rho] == K_WTERM)) || bounded_row(rho)) { box_of[rho] = (int)tab.size(); tab.push_back(rho); }
+  auto bounded_output = [&](int rho) {
+    const int cy = rho % k.nch - k.m;
+    return ymin != nullptr && ti[rho] == K_WPRED && (std::isfinite(ymin[cy]) || std::isfinite(ymax[cy]));
+  };
+  for (int rho = 0; rho < k.r; ++rho) {
+    const bool first = (k.convex && (ti[rho] == K_WPRED || ti[rho] == K_WTERM)) || bounded_row(rho), second = bounded_output(rho);
+    if (first) { box_of[rho] = (int)tab.size(); tab.push_back(rho); outp.push_back(0); col.push_back((int)col_rho.size()); }
+    if (second) { box_ofy[rho] = (int)tab.size(); tab.push_back(rho); outp.push_back(1); col.push_back((int)col_rho.size()); }
+    if (first || second) col_rho.push_back(rho);
+  }
   const int nbox = bl.nbox = (int)tab.size();
+  bl.ncol = (int)col_rho.size();
   if (box) {
     bl.bd.resize(5 * (size_t)nbox);
     for (int s = 0; s < nbox; ++s) {
       const int rho = tab[s], ch = rho % k.nch;
       const double D0 = td[rho], D1 = td[RP + rho];
       const bool inp = ti[rho] == K_UFREE;
+      if (outp[s]) {           // hat = y_s - lam beta / q, held at y_min / y_max: d = lam / q (D1 = 1 / q on a K_WPRED row)
+        bl.bd[0 * nbox + s] = td[2 * RP + rho];
+        bl.bd[1 * nbox + s] = -k.lam * D1;
+        bl.bd[2 * nbox + s] = ymin[ch - k.m];
+        bl.bd[3 * nbox + s] = ymax[ch - k.m];
+        bl.bd[4 * nbox + s] = 1.0 / (k.lam * D1);
+        continue;
+      }
       bl.bd[0 * nbox + s] = inp ? td[2 * RP + rho] : 0.0;
       bl.bd[1 * nbox + s] = inp ? -k.lam * D0 : k.sig_scale;
       bl.bd[2 * nbox + s] = inp ? umin[ch] : -k.bound;
@@ -2009,6 +2041,12 @@ static BoxList build_box_list(const KParams& k, int RP, const std::vector<int>& 
     }
   }
   tab.insert(tab.end(), box_of.begin(), box_of.end());
+  if (ymin) {
+    tab.insert(tab.end(), col.begin(), col.end());
+    tab.insert(tab.end(), box_ofy.begin(), box_ofy.end());
+    tab.push_back(bl.ncol);
+    tab.insert(tab.end(), col_rho.begin(), col_rho.end());
+  }
   return bl;
 }
 
@@ -2020,7 +2058,7 @@ static int upload_box_list(ddmpc_handle* h, const BoxList& bl, bool box) {
     if ((rc = h->d_box_bd.ensure(bl.bd.size() * sizeof(double)))) return rc;
     HIP_TRY(hipMemcpy(h->d_box_bd.p, bl.bd.data(), bl.bd.size() * sizeof(double), hipMemcpyHostToDevice));
   }
-  if ((rc = h->d_cwl_tab.ensure(bl.tab.size() * sizeof(int))) || (rc = h->d_mcol.ensure(B * (size_t)bl.nbox * h->kp.r * sizeof(double))) ||
+  if ((rc = h->d_cwl_tab.ensure(bl.tab.size() * sizeof(int))) || (rc = h->d_mcol.ensure(B * (size_t)bl.ncol * h->kp.r * sizeof(double))) ||
       (rc = h->d_cwl_ref.ensure((B + 1) * sizeof(int))))
     return rc;
   if (bl.nbox > CWL_KLDS && (rc = h->d_cwl_sg.ensure(B * (size_t)(bl.nbox * (bl.nbox + 1) / 2) * sizeof(double)))) return rc;
@@ -2030,7 +2068,7 @@ static int upload_box_list(ddmpc_handle* h, const BoxList& bl, bool box) {
 }
 
 // The affine law (and M for nbox boxed components) by substitutions through the exported factor.
-static int enqueue_gain(ddmpc_handle* h, int nf, int nbox) {
+static int enqueue_gain(ddmpc_handle* h, int nf, int nbox, const int* box_rho) {
   const int NT = h->kc.NT;
   bool launched = false;
 #define DDMPC_INSTANCE(NT_, W_)                                                                              \
@@ -2040,7 +2078,7 @@ static int enqueue_gain(ddmpc_handle* h, int nf, int nbox) {
       HIP_TRY(raise_lds_limit((const void*)ddmpc_gain_kernel<NT_>, glds)); \
     hipLaunchKernelGGL(ddmpc_gain_kernel<NT_>, dim3((unsigned)h->batch), dim3(256), glds, h->stream, h->kp, 16 * NT, nf, \
                        (const double*)h->d_lfac.p, (const double*)h->d_lfacT.p, (const double*)h->d_beta.p,  \
-                       (double*)h->d_gain.p, nbox, (const int*)h->d_cwl_tab.p, (double*)h->d_mcol.p);         \
+                       (double*)h->d_gain.p, nbox, box_rho, (double*)h->d_mcol.p);                            \
     launched = true;                                                                                          \
   }
 #include "ddmpc_instances.inc"
@@ -2116,19 +2154,29 @@ static int prepare_register_resident(ddmpc_handle* h, bool box) {
   if (refinable && k.refine == DDMPC_REFINE_AUTO && (rc = prep_probe_tail(h, k0))) return rc;
   if (B * (size_t)(NT * (NT + 1) / 2) > 0x7fffffffULL) return fail(DDMPC_ERR_INVALID, "batch too large for ddmpc_prepare");
   const bool cwl = convex_warm_on(h) || box;
-  int nbox = 0;
+  int nbox = 0, ncol = 0;
+  const int* col_rho = nullptr;                    // output bounds: the rows of M's columns (the end of the table)
   if (cwl) {
     const int RP = 16 * NT;
     std::vector<int> ti;
     std::vector<double> td;
     if (box) HIP_TRY(hipStreamSynchronize(h->stream));     // (a step in flight may still read the tables written below)
     if ((rc = read_table(h->d_tabi, 3 * (size_t)RP, &ti)) || (box && (rc = read_table(h->d_tabd, 4 * (size_t)RP, &td)))) return rc;
-    const BoxList bl = build_box_list(k, RP, ti, td, box ? h->umin_h.data() : nullptr, box ? h->umax_h.data() : nullptr);
+    const bool ub = box && !h->umin_h.empty(), yb = box && !h->ymin_h.empty();
+    const BoxList bl = build_box_list(k, RP, ti, td, ub ? h->umin_h.data() : nullptr, ub ? h->umax_h.data() : nullptr,
+                                      yb ? h->ymin_h.data() : nullptr, yb ? h->ymax_h.data() : nullptr);
+    // (thread s of the box kernels looks at component s, and the LDS arrays by component hold WARM_MAX_R entries)
+    if (bl.nbox > WARM_MAX_R)
+      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: the box list has %d components (slack, input and output), the kernels hold %d",
+                  bl.nbox, WARM_MAX_R);
     if ((rc = upload_box_list(h, bl, box))) return rc;
     nbox = bl.nbox;
+    ncol = bl.ncol;
+    if (yb) col_rho = (const int*)h->d_cwl_tab.p + 2 * (nbox + k.r) + 1;
+    h->prep.box_threads = (int)warm_threads(std::max(k.r, nbox));
   }
   h->prep.cwl_nbox = nbox;
-  if ((rc = enqueue_gain(h, nf, nbox))) return rc;
+  if ((rc = enqueue_gain(h, nf, ncol, col_rho ? col_rho : (const int*)h->d_cwl_tab.p))) return rc;
   if (refinable && (k.refine == DDMPC_REFINE_ALWAYS || k.refine == DDMPC_REFINE_AUTO) && (rc = prep_refine_columns(h, k0))) return rc;
   if (cwl) {
     // M comes from the unrefined factor: instances whose law was refined keep the filtered cold launch for their box
@@ -2218,6 +2266,8 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
     case DDMPC_OPT_REFINE:
       if (value != DDMPC_REFINE_OFF && value != DDMPC_REFINE_AUTO && value != DDMPC_REFINE_ALWAYS)
         return fail(DDMPC_ERR_INVALID, "refinement mode must be DDMPC_REFINE_OFF, _AUTO or _ALWAYS");
+      if (value == DDMPC_REFINE_ALWAYS && h->bounded && h->umin_h.empty())
+        return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_REFINE_ALWAYS is not available on a handle with output bounds (ddmpc_set_output_bounds)");
       if (value == DDMPC_REFINE_ALWAYS && h->bounded)       // (M comes from the unrefined factor: no refined iteration on it)
         return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_REFINE_ALWAYS is not available on a handle with input bounds (ddmpc_set_input_bounds)");
       h->kp.refine = value;
@@ -2345,22 +2395,98 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->last.valid = false;
   forget_prep(h);
-  h->bounded = any;
+  h->bounded = any || !h->ymin_h.empty();
   if (!any) { h->umin_h.clear(); h->umax_h.clear(); return DDMPC_OK; }
   h->umin_h.assign(u_min, u_min + p.m);
   h->umax_h.assign(u_max, u_max + p.m);
   std::vector<double> ub(h->umin_h);
   ub.insert(ub.end(), h->umax_h.begin(), h->umax_h.end());
   int rc;
-  if ((rc = h->d_ubnd.ensure(ub.size() * sizeof(double)))) { h->bounded = false; return rc; }
+  if ((rc = h->d_ubnd.ensure(ub.size() * sizeof(double)))) { h->umin_h.clear(); h->umax_h.clear(); h->bounded = !h->ymin_h.empty(); return rc; }
   HIP_TRY(hipMemcpy(h->d_ubnd.p, ub.data(), ub.size() * sizeof(double), hipMemcpyHostToDevice));
+  return DDMPC_OK;
+}
+
+// With the terminal constraint the last n predicted outputs are fixed to y_s (the bounds act on the free steps, but a setpoint
+// the free steps may not reach makes the QP infeasible under the CONVEX slack box, and pointless otherwise).
+static const char* output_setpoint_outside_bounds(const ddmpc_handle* h, const double* y_s, const double* y_min, const double* y_max) {
+  if (!h->prm.use_terminal_constraint) return nullptr;
+  for (int ch = 0; ch < h->prm.p; ++ch)
+    if (y_s[ch] < y_min[ch] || y_s[ch] > y_max[ch]) return "y_s lies outside [y_min, y_max] and the terminal constraint fixes the last n outputs to it";
+  return nullptr;
+}
+
+int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* y_max) {
+  if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
+  if ((y_min == nullptr) != (y_max == nullptr))
+    return fail(DDMPC_ERR_INVALID, "%s is null: pass both y_min and y_max, or neither to remove the bounds", y_min ? "y_max" : "y_min");
+  const ddmpc_params& p = h->prm;
+  bool any = false;
+  if (y_min) {
+    for (int ch = 0; ch < p.p; ++ch) {
+      if (y_min[ch] != y_min[ch]) return fail(DDMPC_ERR_INVALID, "y_min[%d] is NaN", ch);
+      if (y_max[ch] != y_max[ch]) return fail(DDMPC_ERR_INVALID, "y_max[%d] is NaN", ch);
+      if (y_min[ch] >= y_max[ch]) return fail(DDMPC_ERR_INVALID, "y_min[%d] >= y_max[%d]: the box is empty or a point", ch, ch);
+      any = any || std::isfinite(y_min[ch]) || std::isfinite(y_max[ch]);
+    }
+  }
+  if (any) {
+    if (const char* msg = output_setpoint_outside_bounds(h, h->ys_h.data(), y_min, y_max)) return fail(DDMPC_ERR_INVALID, "y_min / y_max: %s", msg);
+    if (p.controller_type != DDMPC_ROBUST)
+      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: ROBUST controllers only (a NOMINAL one has no regularised reduced system to iterate on)");
+    if (h->large)
+      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels)", h->kp.r);
+    if (p.weight_kind == DDMPC_WEIGHT_DENSE)
+      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)");
+    if (p.n * h->kp.nch > WARM_MAX_NF)
+      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: n*(m+p) = %d, the affine law of ddmpc_prepare holds %d", p.n * h->kp.nch, WARM_MAX_NF);
+    if (h->kp.refine == DDMPC_REFINE_ALWAYS)
+      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: not with DDMPC_REFINE_ALWAYS (DDMPC_OPT_REFINE must be OFF or AUTO)");
+    const int nfree = p.use_terminal_constraint ? p.L - p.n : p.L;
+    const bool diag = p.weight_kind == DDMPC_WEIGHT_DIAG;
+    int nout = 0;
+    for (int ch = 0; ch < p.p; ++ch) {
+      if (!std::isfinite(y_min[ch]) && !std::isfinite(y_max[ch])) continue;
+      nout += nfree;
+      for (int kp = 0; kp < nfree; ++kp)
+        if (!((diag ? h->Qh[(size_t)kp * p.p + ch] : h->Qh[0]) > 0.0))
+          return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: channel %d is bounded and has a Q entry of 0 on a free prediction step (limit: Q > 0 there)", ch);
+    }
+    if (h->kp.convex)        // (the slack components join the box list: each must change its diagonal entry at the bound)
+      for (int i = 0; i < (diag ? nfree * p.p : 1); ++i)
+        if (!(h->Qh[(size_t)i] > 0.0))
+          return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: with the CONVEX slack box every Q entry of a free prediction step must be positive (limit: Q > 0 there)");
+    // the box list: the slack components (CONVEX: every predicted step), the bounded inputs and the bounded outputs of the free steps
+    int nin = 0;
+    for (int ch = 0; ch < p.m && !h->umin_h.empty(); ++ch)
+      if (std::isfinite(h->umin_h[ch]) || std::isfinite(h->umax_h[ch])) nin += nfree;
+    const int nlist = (h->kp.convex ? p.L * p.p : 0) + nin + nout;
+    if (nlist > WARM_MAX_R)
+      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: the box list has %d components (slack, input and output), the kernels hold %d", nlist,
+                  WARM_MAX_R);
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->last.valid = false;
+  forget_prep(h);
+  h->bounded = any || !h->umin_h.empty();
+  if (!any) { h->ymin_h.clear(); h->ymax_h.clear(); return DDMPC_OK; }
+  h->ymin_h.assign(y_min, y_min + p.p);
+  h->ymax_h.assign(y_max, y_max + p.p);
+  std::vector<double> yb(h->ymin_h);
+  yb.insert(yb.end(), h->ymax_h.begin(), h->ymax_h.end());
+  int rc;
+  if ((rc = h->d_ybnd.ensure(yb.size() * sizeof(double)))) { h->ymin_h.clear(); h->ymax_h.clear(); h->bounded = !h->umin_h.empty(); return rc; }
+  HIP_TRY(hipMemcpy(h->d_ybnd.p, yb.data(), yb.size() * sizeof(double), hipMemcpyHostToDevice));
   return DDMPC_OK;
 }
 
 int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s) {
   if (!h || !u_s || !y_s) return fail(DDMPC_ERR_INVALID, "null argument");
-  if (h->bounded)
+  if (!h->umin_h.empty())
     if (const char* msg = setpoint_outside_bounds(h, u_s, h->umin_h.data(), h->umax_h.data())) return fail(DDMPC_ERR_INVALID, "%s", msg);
+  if (!h->ymin_h.empty())
+    if (const char* msg = output_setpoint_outside_bounds(h, y_s, h->ymin_h.data(), h->ymax_h.data())) return fail(DDMPC_ERR_INVALID, "%s", msg);
   HIP_TRY(hipSetDevice(h->device));
   h->us_h.assign(u_s, u_s + h->prm.m);
   h->ys_h.assign(y_s, y_s + h->prm.p);
@@ -2435,7 +2561,8 @@ int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
                      h->yd, l.up, l.yp, (const double*)h->d_beta.p, (const signed char*)h->d_act.p, dst,
                      resc ? (const double*)h->d_zws.p : (const double*)nullptr, resc ? (const int*)h->d_resc.p : (const int*)nullptr,
                      resc ? (const double*)h->d_xws.p : (const double*)nullptr,
-                     h->bounded ? (const double*)h->d_ubnd.p : (const double*)nullptr);
+                     !h->umin_h.empty() ? (const double*)h->d_ubnd.p : (const double*)nullptr,
+                     !h->ymin_h.empty() ? (const double*)h->d_ybnd.p : (const double*)nullptr);
   HIP_TRY(hipGetLastError());
   if (mem == DDMPC_MEM_HOST) {
     HIP_TRY(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -2582,8 +2709,10 @@ static int launch_fused_loop(ddmpc_handle* h, LoopPath path, LoopArgs a) {
   if (int rc = reserve_beta(h)) return rc;
   a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p;
   begin_solve(h, path == LoopPath::FusedBox ? Route::BoxLaw : Route::Cold);
+  const bool yb = path == LoopPath::FusedBox && !h->ymin_h.empty();
+  const unsigned threads = yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r);
   auto launch = [&](auto kernel, auto... tail) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp, 16 * h->kc.NT,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(threads), 0, h->stream, h->kp, 16 * h->kc.NT,
                        h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps,
                        a.n_mpc_step, a.x, a.up, a.yp, a.w, a.usys, a.ysys, a.stacc, a.beta, a.act, tail..., a.lwup, a.lwyp);
   };
@@ -2598,8 +2727,10 @@ static int launch_fused_loop(ddmpc_handle* h, LoopPath path, LoopArgs a) {
   } else {    // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard, as launch_box_step)
     const double* bd = (const double*)h->d_box_bd.p;
     const int* ref = h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr;
-    if (h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true>, nbox, tab, bd, mcol, sg, ref);
-    else launch(ddmpc_closed_loop_box_kernel<false>, nbox, tab, bd, mcol, sg, ref);
+    if (yb && h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true, true>, nbox, tab, bd, mcol, sg, ref);
+    else if (yb) launch(ddmpc_closed_loop_box_kernel<false, true>, nbox, tab, bd, mcol, sg, ref);
+    else if (h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true, false>, nbox, tab, bd, mcol, sg, ref);
+    else launch(ddmpc_closed_loop_box_kernel<false, false>, nbox, tab, bd, mcol, sg, ref);
   }
   HIP_TRY(hipGetLastError());
   return DDMPC_OK;

@@ -31,14 +31,17 @@ __global__ void ddmpc_hankel_kernel(const double* __restrict__ X, double* __rest
 // controller.py:434-445) from the beta / active-set workspace of the last solve.
 // what: 0 alpha, 1 ubar, 2 ybar, 3 sigma.  One workgroup per instance.
 // `RPs` is the row stride of the component tables.  `ubnd` (null without input bounds): [u_min (m) | u_max (m)] of
-// ddmpc_set_input_bounds; a free input row in the active set is held at its bound (t = bound, D = 0).
+// ddmpc_set_input_bounds; a free input row in the active set is held at its bound (t = bound, D = 0).  `ybnd` (null without
+// output bounds): [y_min (p) | y_max (p)] of ddmpc_set_output_bounds; the workspace then holds sa + 4 say per row (sa: slack or
+// input, say: output), and a K_WPRED row with say != 0 has ybar = its bound exactly, sigma = +- c eps_max or -lam beta / lamb_sigma.
 // --------------------------------------------------------------------------
 __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const double* __restrict__ u_d,
                                          const double* __restrict__ y_d, const double* __restrict__ u_past,
                                          const double* __restrict__ y_past, const double* __restrict__ beta_ws,
                                          const signed char* __restrict__ act_ws, double* __restrict__ out,
                                          const double* __restrict__ z_ws, const int* __restrict__ rescued,
-                                         const double* __restrict__ x_ws, const double* __restrict__ ubnd) {
+                                         const double* __restrict__ x_ws, const double* __restrict__ ubnd,
+                                         const double* __restrict__ ybnd) {
   const long long b = blockIdx.x;
   const int n = P.npu / P.m;
   const bool resc = rescued != nullptr && rescued[b] != 0;
@@ -73,7 +76,8 @@ __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const dou
   }
   for (int rho = threadIdx.x; rho < P.r; rho += blockDim.x) {
     const int k = rho / P.nch, ch = rho - k * P.nch;
-    const int s_act = aw[rho];
+    int s_act = aw[rho], y_act = 0;
+    if (ybnd != nullptr) { const int code = s_act + 5; y_act = (code >> 2) - 1; s_act = (code & 3) - 1; }
     const int kind = P.tabi[0 * RPs + rho];
     const int pidx = P.tabi[1 * RPs + rho];
     const double tb = P.tabd[2 * RPs + rho];
@@ -95,6 +99,12 @@ __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const dou
     }
     const int cy = ch - P.m;
     double sg = 0.0;
+    if (y_act != 0 && kind == K_WPRED) {
+      sg = (s_act != 0) ? s_act * P.bound : -P.lam * bb / P.lamb_sigma;
+      if (what == 2) out[b * (long long)(P.Ln * P.p) + k * P.p + cy] = ybnd[(y_act > 0 ? P.p : 0) + cy];
+      if (what == 3) out[b * (long long)(P.Ln * P.p) + k * P.p + cy] = sg;
+      continue;
+    }
     if (kind == K_WINT) sg = z - tpast;
     else if (kind == K_WTERM) sg = z - tb;
     else if (kind == K_WPRED) sg = (s_act != 0) ? s_act * P.bound : -P.lam * bb / P.lamb_sigma;

@@ -16,9 +16,19 @@
 //           while hat_s < lo_s, and is released otherwise (BoxTab::test);  shift_s = (hi_s or lo_s) - a_s.
 //       slack:  a = 0,  c = -lam / lamb_sigma, lo / hi = -+ c_param eps_max, d = lam (D0 - D1)
 //       input:  a = tb (= u_s), c = -lam D0,   lo / hi = u_min / u_max of the channel (either may be infinite), d = lam D0
+//       output: a = tb (= y_s), c = -lam / q,  lo / hi = y_min / y_max of the channel,                   d = lam / q
+// Output bounds (ddmpc_set_output_bounds, the YB instantiations): a K_WPRED row carries ybar AND sigma, so a CONVEX handle has
+// two boxed components on such a row, the slack before the output; D_rho = [slack free] / lamb_sigma + [output free] / q, and
+// with both active the row is hard.  Both change the same diagonal entry, so M keeps ONE column per boxed row: the table grows
+//     tab = [box_rho (nbox) | box_of (r): the slack or input component | col (nbox): column of M | box_ofy (r): the output
+//            component, or -1 | ncol | col_rho (ncol)]
+// and the kernels run with max(r, nbox) threads rounded up to 64 (thread s looks at component s; nbox <= WARM_MAX_R).  The
+// instantiations without YB never look beyond [box_rho | box_of]: col(s) = s there.
 // The k x k system lives in LDS up to CWL_KLDS components and in the instance's slice of `sg` beyond; M = K0^-1 E_box is
 // nbox * r doubles per instance (122 KB at L = 30, n = 4, m = p = 2, CONVEX, both channels bounded: 0.5 GB at 4096 instances).
 #pragma once
+#include <type_traits>
+
 #include "ddmpc_aux_kernels.hpp"
 
 namespace ddmpc {
@@ -42,9 +52,40 @@ struct BoxTab {
   __device__ __forceinline__ double shift(int j, int act) const { return bound(j, act) - a[j]; }
 };
 
+// ... with output bounds: the column of M of every component, the output component of every row, the columns of M.
+struct BoxTabY : BoxTab {
+  const int *col, *ofy;
+  int ncol;
+  __device__ __forceinline__ BoxTabY(int nbox_, const int* __restrict__ tab, const double* __restrict__ bd, int r)
+      : BoxTab(nbox_, tab, bd), col(tab + nbox_ + r), ofy(tab + 2 * nbox_ + r), ncol(tab[2 * (nbox_ + r)]) {}
+};
+template <bool YB> using BoxTabT = std::conditional_t<YB, BoxTabY, BoxTab>;
+template <bool YB>
+__device__ __forceinline__ BoxTabT<YB> box_table(int nbox, const int* __restrict__ tab, const double* __restrict__ bd, int r) {
+  if constexpr (YB) return BoxTabY(nbox, tab, bd, r); else return BoxTab(nbox, tab, bd);
+}
+// the column of M of component j, and CwlLds::m / CwlLds::beta through it (the LDS slots are keyed by column)
+template <bool YB>
+__device__ __forceinline__ int box_col(const BoxTabT<YB>& T, int j) {
+  if constexpr (YB) return T.col[j]; else return j;
+}
+template <bool YB>
+__device__ __forceinline__ double box_beta(const CwlLds& s, const BoxTabT<YB>& T, const double* __restrict__ Mb, int r, double b0,
+                                           int rho) {
+  if constexpr (YB) {
+    double v = b0;
+    for (int i = 0; i < s.kfin; ++i) v += s.m(Mb, r, T.col[s.al[i]], rho) * s.ev[i];
+    return v;
+  } else {
+    return s.beta(Mb, r, b0, rho);
+  }
+}
+
 // The active-set iteration of one instance by the whole workgroup: cwl_iterate with the table (same control flow, same
-// count of solves, status 4 at the cap or on a non-positive pivot of the k x k system; blockDim.x >= r > nbox).
-__device__ int box_iterate(const KParams& P, const BoxTab& T, const double* __restrict__ Mb, double* __restrict__ Sg,
+// count of solves, status 4 at the cap or on a non-positive pivot of the k x k system; blockDim.x >= r and > nbox).  YB: two
+// active components of one row share their column of M (box_col) and its LDS slot.
+template <bool YB>
+__device__ int box_iterate(const KParams& P, const BoxTabT<YB>& T, const double* __restrict__ Mb, double* __restrict__ Sg,
                            const double* b0, CwlLds& s, int* iters) {
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, r = P.r, nbox = T.nbox;
   for (int j = tid; j < nbox; j += nthr) { s.bc[j] = b0[T.rho[j]]; s.act[j] = 0; s.slot[j] = -1; }
@@ -74,7 +115,7 @@ __device__ int box_iterate(const KParams& P, const BoxTab& T, const double* __re
     if (tid == 0) {                                                   // LDS slots for columns that enter A for the first time
       int ns_ = n0;
       for (int i = 0; i < k && ns_ < CWL_CC; ++i) {
-        const int j = s.al[i];
+        const int j = box_col<YB>(T, s.al[i]);
         if (s.slot[j] < 0) { s.slot[j] = ns_; s.slotj[ns_] = j; ++ns_; }
       }
       s.nslots = ns_;
@@ -92,7 +133,7 @@ __device__ int box_iterate(const KParams& P, const BoxTab& T, const double* __re
       const int i = e / k, l = e - i * k;
       if (l <= i) {
         const int ri = T.rho[s.al[i]];
-        double v = -s.m(Mb, r, s.al[l], ri);
+        double v = -s.m(Mb, r, box_col<YB>(T, s.al[l]), ri);
         if (l == i) v += T.invd[s.al[i]];
         Sp[i * (i + 1) / 2 + l] = v;
       }
@@ -100,7 +141,7 @@ __device__ int box_iterate(const KParams& P, const BoxTab& T, const double* __re
     for (int i = tid; i < k; i += nthr) {
       const int ri = T.rho[s.al[i]];
       double g = b0[ri];
-      for (int l = 0; l < k; ++l) g += s.m(Mb, r, s.al[l], ri) * T.shift(s.al[l], s.act[s.al[l]]);
+      for (int l = 0; l < k; ++l) g += s.m(Mb, r, box_col<YB>(T, s.al[l]), ri) * T.shift(s.al[l], s.act[s.al[l]]);
       s.ev[i] = g;
     }
     __syncthreads();
@@ -141,7 +182,7 @@ __device__ int box_iterate(const KParams& P, const BoxTab& T, const double* __re
       s.kfin = k;
     }
     __syncthreads();
-    for (int j = tid; j < nbox; j += nthr) s.bc[j] = s.beta(Mb, r, b0[T.rho[j]], T.rho[j]);
+    for (int j = tid; j < nbox; j += nthr) s.bc[j] = box_beta<YB>(s, T, Mb, r, b0[T.rho[j]], T.rho[j]);
   }
   *iters = iter;
   return st;
@@ -183,7 +224,8 @@ __device__ __forceinline__ void box_argmin(double& key, int& idx, BoxSafeLds& q)
 // with the body in a function of its own the compiler allocates the registers of ddmpc_box_step_kernel differently and its
 // default instantiation measured 1.2 % slower than before on [0, 2] at 4096 instances (outside the run-to-run spread), so
 // box_iterate keeps its text and the kernels without the safeguard their code.
-__device__ __forceinline__ bool box_solve_set(const KParams& P, const BoxTab& T, const double* __restrict__ Mb,
+template <bool YB>
+__device__ __forceinline__ bool box_solve_set(const KParams& P, const BoxTabT<YB>& T, const double* __restrict__ Mb,
                                               double* __restrict__ Sg, const double* b0, CwlLds& s) {
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, r = P.r, nbox = T.nbox;
   // the active set in ascending order: one ballot per wave (nbox < blockDim.x: thread s looks at component s)
@@ -199,7 +241,7 @@ __device__ __forceinline__ bool box_solve_set(const KParams& P, const BoxTab& T,
   if (tid == 0) {                                                   // LDS slots for columns that enter A for the first time
     int ns_ = n0;
     for (int i = 0; i < k && ns_ < CWL_CC; ++i) {
-      const int j = s.al[i];
+      const int j = box_col<YB>(T, s.al[i]);
       if (s.slot[j] < 0) { s.slot[j] = ns_; s.slotj[ns_] = j; ++ns_; }
     }
     s.nslots = ns_;
@@ -217,7 +259,7 @@ __device__ __forceinline__ bool box_solve_set(const KParams& P, const BoxTab& T,
     const int i = e / k, l = e - i * k;
     if (l <= i) {
       const int ri = T.rho[s.al[i]];
-      double v = -s.m(Mb, r, s.al[l], ri);
+      double v = -s.m(Mb, r, box_col<YB>(T, s.al[l]), ri);
       if (l == i) v += T.invd[s.al[i]];
       Sp[i * (i + 1) / 2 + l] = v;
     }
@@ -225,7 +267,7 @@ __device__ __forceinline__ bool box_solve_set(const KParams& P, const BoxTab& T,
   for (int i = tid; i < k; i += nthr) {
     const int ri = T.rho[s.al[i]];
     double g = b0[ri];
-    for (int l = 0; l < k; ++l) g += s.m(Mb, r, s.al[l], ri) * T.shift(s.al[l], s.act[s.al[l]]);
+    for (int l = 0; l < k; ++l) g += s.m(Mb, r, box_col<YB>(T, s.al[l]), ri) * T.shift(s.al[l], s.act[s.al[l]]);
     s.ev[i] = g;
   }
   __syncthreads();
@@ -266,7 +308,7 @@ __device__ __forceinline__ bool box_solve_set(const KParams& P, const BoxTab& T,
     s.kfin = k;
   }
   __syncthreads();
-  for (int j = tid; j < nbox; j += nthr) s.bc[j] = s.beta(Mb, r, b0[T.rho[j]], T.rho[j]);
+  for (int j = tid; j < nbox; j += nthr) s.bc[j] = box_beta<YB>(s, T, Mb, r, b0[T.rho[j]], T.rho[j]);
   return false;
 }
 
@@ -280,7 +322,8 @@ __device__ __forceinline__ bool box_solve_set(const KParams& P, const BoxTab& T,
 // multiplier of the wrong sign, lowest s on ties -- is released; none: W is optimal.  The cost falls with every move, so no set
 // comes back.  Status 4 at 4 nbox + 16 solves or on a non-positive pivot.  *solves = the solves; s.act / s.al / s.ev / s.kfin
 // describe the result as after box_iterate (thread s owns component s: blockDim.x > nbox).
-__device__ int box_safeguard(const KParams& P, const BoxTab& T, const double* __restrict__ Mb, double* __restrict__ Sg,
+template <bool YB>
+__device__ int box_safeguard(const KParams& P, const BoxTabT<YB>& T, const double* __restrict__ Mb, double* __restrict__ Sg,
                              const double* b0, CwlLds& s, BoxSafeLds& q, int* solves) {
   const int tid = threadIdx.x, nbox = T.nbox, cap = 4 * nbox + 16;
   const bool own = tid < nbox;
@@ -298,7 +341,7 @@ __device__ int box_safeguard(const KParams& P, const BoxTab& T, const double* __
     __syncthreads();
     if (n >= cap) { st = 4; break; }
     ++n;
-    if (box_solve_set(P, T, Mb, Sg, b0, s)) { st = 4; break; }
+    if (box_solve_set<YB>(P, T, Mb, Sg, b0, s)) { st = 4; break; }
     __syncthreads();
     const int act = own ? s.act[tid] : 0;
     const double hat = own ? fma(T.c[tid], s.bc[tid], T.a[tid]) : 0.0;
@@ -352,6 +395,20 @@ __device__ __forceinline__ double box_component(const KParams& P, int RPs, const
   return contrib;
 }
 
+// ... of a K_WPRED row whose output component jy is held at its bound (say != 0; sa: its slack): ybar is that bound exactly,
+// sigma = z - bound with the row's weight lamb_sigma, or +- c eps_max with both active (the row is hard).
+__device__ __forceinline__ double box_component_y(const KParams& P, int RPs, const BoxTab& T, int rho, int jy, double beta, int sa,
+                                                  int say, double* z_out) {
+  const double tb = P.tabd[2 * RPs + rho];
+  const double wq = P.tabd[3 * RPs + rho];
+  const double yb = T.bound(jy, say);
+  const double sg = (sa != 0) ? sa * P.bound : -P.lam * beta / P.lamb_sigma;
+  const double z = yb + sg;
+  const double dlt = yb - tb;
+  *z_out = z;
+  return P.lam * beta * z + wq * dlt * dlt + P.lamb_sigma * sg * sg;
+}
+
 // One control step of a bounded handle for the batch: grid = batch, block = r rounded up to 64 (the geometry of
 // ddmpc_warm_step_kernel): law, violation test with the table, iteration, M_A ev correction, outputs.  Mcol [batch][nbox][r],
 // sg [batch][nbox (nbox + 1) / 2] (used for k > CWL_KLDS only).  No cold hand-over: no cold kernel serves these handles.
@@ -359,7 +416,9 @@ __device__ __forceinline__ double box_component(const KParams& P, int RPs, const
 // factor's, so a solve of theirs that ends with a non-empty active set is reported optimal_inaccurate.
 // SAFE (DDMPC_OPT_BOX_SAFEGUARD = 1): an instance that ends at the max_iter cap is finished by box_safeguard; iters = max_iter +
 // its solves.  The host launches <false> when the option is 0: that instantiation is the kernel as it was.
-template <bool SAFE>
+// YB (ddmpc_set_output_bounds): the table with the output components; block = max(r, nbox) rounded up to 64; the active-set
+// workspace holds sa + 4 say per row (sa: slack or input, say: output).  Without YB the kernel is the one it was.
+template <bool SAFE, bool YB>
 __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                       const int* __restrict__ prep_status, const double* __restrict__ u_past,
                                       const double* __restrict__ y_past, double* __restrict__ u_opt, double* __restrict__ cost,
@@ -371,9 +430,10 @@ __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* 
   __shared__ double red[32];
   __shared__ double bsh[WARM_MAX_R];
   __shared__ CwlLds s;
-  const BoxTab T(nbox, tab, bd);
+  const int r = P.r;
+  const BoxTabT<YB> T = box_table<YB>(nbox, tab, bd, r);
   const long long b = blockIdx.x;
-  const int tid = threadIdx.x, r = P.r, nrhs = nf + 1;
+  const int tid = threadIdx.x, nrhs = nf + 1;
   const int nyp = nf - P.npu;
   for (int f = tid; f < nf; f += blockDim.x)
     pv[f] = (f < P.npu) ? u_past[b * P.npu + f] : y_past[b * nyp + (f - P.npu)];
@@ -396,19 +456,25 @@ __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* 
     bsh[rho] = beta;
     const int j = T.of[rho];
     if (j >= 0 && T.test(j, beta, 0) != 0) viol = 1;
+    if constexpr (YB) {
+      const int jy = T.ofy[rho];
+      if (jy >= 0 && T.test(jy, beta, 0) != 0) viol = 1;
+    }
   }
   viol = __syncthreads_or(viol);
   int st = prep_status[b], it = 1;
-  const double* Mb = Mcol + b * (long long)nbox * r;
+  int ncol = nbox;
+  if constexpr (YB) ncol = T.ncol;
+  const double* Mb = Mcol + b * (long long)ncol * r;
   const bool iterate = viol && st <= 1;               // (a failed factorisation: nothing to iterate on)
   if (iterate) {
     double* Sg = sg + b * (long long)(nbox * (nbox + 1) / 2);
-    int dst = box_iterate(P, T, Mb, Sg, bsh, s, &it);
+    int dst = box_iterate<YB>(P, T, Mb, Sg, bsh, s, &it);
     if constexpr (SAFE) {
       __shared__ BoxSafeLds q;
       if (dst == 4 && !s.fail) {                      // at the cap (not a pivot)
         int more;
-        dst = box_safeguard(P, T, Mb, Sg, bsh, s, q, &more);
+        dst = box_safeguard<YB>(P, T, Mb, Sg, bsh, s, q, &more);
         it += more;
       }
     }
@@ -425,8 +491,15 @@ __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* 
     } else {
       const int j = T.of[rho];
       sa = (j >= 0) ? s.act[j] : 0;
-      beta = s.beta(Mb, r, beta, rho);
-      part += box_component(P, RPs, T, rho, j, beta, sa, pv, &z);
+      beta = box_beta<YB>(s, T, Mb, r, beta, rho);
+      int say = 0, jy = -1;
+      if constexpr (YB) {
+        jy = T.ofy[rho];
+        say = (jy >= 0) ? s.act[jy] : 0;
+      }
+      if (say != 0) part += box_component_y(P, RPs, T, rho, jy, beta, sa, say, &z);
+      else part += box_component(P, RPs, T, rho, j, beta, sa, pv, &z);
+      sa += 4 * say;
     }
     finite = finite && (fabs(beta) < 1e300);
     const int oidx = P.tabi[2 * RPs + rho];
@@ -452,8 +525,8 @@ __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* 
 // (same fixed-size arrays and the same checks of ddmpc_closed_loop behind them).  Per solve the law on the boxed rows and the
 // n_mpc_step * m input rows in use, the iteration of ddmpc_box_step_kernel, the M_A ev correction of those rows, then the
 // plant / FIFO steps of ddmpc_plant_kernel; everything on the last solve.  SAFE: as in ddmpc_box_step_kernel; an instance the
-// safeguard finishes carries on with the loop.
-template <bool SAFE>
+// safeguard finishes carries on with the loop.  YB: as in ddmpc_box_step_kernel.
+template <bool SAFE, bool YB>
 __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                              const int* __restrict__ prep_status, int ns, const double* __restrict__ pl,
                                              int n_steps, int n_mpc_step, double* __restrict__ x, double* __restrict__ u_past,
@@ -467,9 +540,10 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
   __shared__ double xs[16], xn[16];       // (ns <= 16 is checked by ddmpc_closed_loop)
   __shared__ double bsh[WARM_MAX_R];
   __shared__ CwlLds s;
-  const BoxTab T(nbox, tab, bd);
+  const int r = P.r;
+  const BoxTabT<YB> T = box_table<YB>(nbox, tab, bd, r);
   const long long b = blockIdx.x;
-  const int tid = threadIdx.x, r = P.r, nrhs = nf + 1, m = P.m, p = P.p;
+  const int tid = threadIdx.x, nrhs = nf + 1, m = P.m, p = P.p;
   const int n = P.npu / m, nyp = nf - P.npu;
   const double* A = pl;
   const double* Bm = A + ns * ns;
@@ -482,7 +556,9 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
   const bool refd = refined != nullptr && refined[b] != 0;
   const double nanv = __longlong_as_double(0x7ff8000000000000LL);
   const double* g = gain + b * (long long)nrhs * r;
-  const double* Mb = Mcol + b * (long long)nbox * r;
+  int ncol = nbox;
+  if constexpr (YB) ncol = T.ncol;
+  const double* Mb = Mcol + b * (long long)ncol * r;
   double* Sg = sg + b * (long long)(nbox * (nbox + 1) / 2);
   const int nuse = n_mpc_step * m;
   double* up = pv;
@@ -499,23 +575,26 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
     for (int rho = tid; rho < r; rho += blockDim.x) {
       const int oidx = P.tabi[2 * RPs + rho];
       const int j = T.of[rho];
-      if ((oidx >= 0 && oidx < nuse) || j >= 0 || last) {
+      int jy = -1;
+      if constexpr (YB) jy = T.ofy[rho];
+      if ((oidx >= 0 && oidx < nuse) || j >= 0 || jy >= 0 || last) {
         double beta = g[rho];
         for (int f = 0; f < nf; ++f) beta += pv[f] * g[(long long)(1 + f) * r + rho];
         bsh[rho] = beta;
         if (j >= 0 && T.test(j, beta, 0) != 0) viol = 1;
+        if (jy >= 0 && T.test(jy, beta, 0) != 0) viol = 1;
       }
     }
     viol = __syncthreads_or(viol);
     int st = st0, it = 1;
     const bool iterate = viol && st <= 1;
     if (iterate) {
-      int dst = box_iterate(P, T, Mb, Sg, bsh, s, &it);
+      int dst = box_iterate<YB>(P, T, Mb, Sg, bsh, s, &it);
       if constexpr (SAFE) {
         __shared__ BoxSafeLds q;
         if (dst == 4 && !s.fail) {
           int more;
-          dst = box_safeguard(P, T, Mb, Sg, bsh, s, q, &more);
+          dst = box_safeguard<YB>(P, T, Mb, Sg, bsh, s, q, &more);
           it += more;
         }
       }
@@ -526,16 +605,19 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
     for (int rho = tid; rho < r; rho += blockDim.x) {
       const int oidx = P.tabi[2 * RPs + rho];
       const int j = T.of[rho];
+      int jy = -1;
+      if constexpr (YB) jy = T.ofy[rho];
       const bool use = oidx >= 0 && oidx < nuse;
-      if (use || j >= 0 || last) {
-        const int sa = (iterate && j >= 0) ? s.act[j] : 0;
-        const double beta = iterate ? s.beta(Mb, r, bsh[rho], rho) : bsh[rho];
+      if (use || j >= 0 || jy >= 0 || last) {
+        int sa = (iterate && j >= 0) ? s.act[j] : 0;
+        const double beta = iterate ? box_beta<YB>(s, T, Mb, r, bsh[rho], rho) : bsh[rho];
         nonfin |= !(fabs(beta) < 1e300);
-        if (use) {
+        if (use) {                                    // (an input row: no output component)
           double z;
           (void)box_component(P, RPs, T, rho, j, beta, sa, pv, &z);
           uo[oidx] = z;
         }
+        if (iterate && jy >= 0) sa += 4 * s.act[jy];
         if (last && beta_ws) { beta_ws[b * (long long)P.rE + rho] = beta; act_ws[b * (long long)P.rE + rho] = (signed char)sa; }
       }
     }

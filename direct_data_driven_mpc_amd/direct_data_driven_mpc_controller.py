@@ -238,6 +238,8 @@ class DirectDataDrivenMPCController:
                                   np.asarray(self.y_d, dtype=np.float64)[None])
             if getattr(self, "_input_bounds", None) is not None:
                 self._engine.set_input_bounds(*self._input_bounds)
+            if getattr(self, "_output_bounds", None) is not None:
+                self._engine.set_output_bounds(*self._output_bounds)
             if getattr(self, "_box_safeguard", False):
                 self._engine.set_box_safeguard(True)
         if not hasattr(self, "problem") or self.problem is None:
@@ -327,8 +329,19 @@ class DirectDataDrivenMPCController:
             self._cold_solved = False
             self.problem.solve()
 
+    def set_output_bounds(self, y_min, y_max) -> None:
+        """Limits y_min <= y <= y_max on the predicted outputs of the free prediction steps (the output constraint set of the
+        robust scheme; the reference leaves it out): p entries each, -inf / +inf = no bound on that side, both None removes
+        them.  Independent of `set_input_bounds`.  The problem is solved again with them."""
+        if self._engine is not None:
+            self._engine.set_output_bounds(y_min, y_max)
+        self._output_bounds = None if y_min is None and y_max is None else (y_min, y_max)
+        if self._engine is not None:
+            self._cold_solved = False
+            self.problem.solve()
+
     def set_box_safeguard(self, on: bool) -> None:
-        """With input bounds: solve a box on which the active-set iteration cycles by a primal active-set method instead of
+        """With input or output bounds: solve a box on which the active-set iteration cycles by a primal active-set method instead of
         reporting solver_error (`BatchedDDMPC.set_box_safeguard`).  The problem is solved again, as after `set_input_bounds`."""
         self._box_safeguard = bool(on)
         if self._engine is not None:

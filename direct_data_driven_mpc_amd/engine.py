@@ -354,8 +354,19 @@ class BatchedDDMPC:
         L.check(self._lib.ddmpc_set_input_bounds(self._h, C.c_void_p(lo.ctypes.data) if lo is not None else C.c_void_p(),
                                                  C.c_void_p(hi.ctypes.data) if hi is not None else C.c_void_p()))
 
+    def set_output_bounds(self, y_min, y_max) -> None:
+        """Box on the predicted outputs of the free prediction steps, y_min[ch] <= ybar[k][ch] <= y_max[ch]
+        (`ddmpc_set_output_bounds`): arrays of p entries (a scalar is broadcast), -inf / +inf = no bound on that side; both
+        None removes the bounds.  Same controllers and effects as `set_input_bounds`, and independent of it: either call keeps
+        the other's bounds.  The bound is on ybar, not on ybar + sigma; under the CONVEX slack box an infeasible box ends in
+        solver_error (there is no infeasibility detection)."""
+        lo = None if y_min is None else np.ascontiguousarray(np.broadcast_to(np.asarray(y_min, dtype=np.float64), (self.p,)))
+        hi = None if y_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(y_max, dtype=np.float64), (self.p,)))
+        L.check(self._lib.ddmpc_set_output_bounds(self._h, C.c_void_p(lo.ctypes.data) if lo is not None else C.c_void_p(),
+                                                  C.c_void_p(hi.ctypes.data) if hi is not None else C.c_void_p()))
+
     def set_box_safeguard(self, on: bool) -> None:
-        """Input bounds: True = an instance whose active-set iteration reaches `max_iter` without a stable set is finished by a
+        """Input / output bounds: True = an instance whose active-set iteration reaches `max_iter` without a stable set is finished by a
         primal active-set method instead of reporting solver_error (DDMPC_OPT_BOX_SAFEGUARD; `iters` = max_iter + its solves),
         False (default) = solver_error at the cap.  Instances below the cap are unchanged; no effect without finite bounds;
         a kept `prepare` stays valid."""

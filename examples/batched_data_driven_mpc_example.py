@@ -46,6 +46,8 @@ def parse_args():
     ap.add_argument("--plot", default=None, help="write a PNG of the closed-loop inputs/outputs (median, band, instance 0)")
     ap.add_argument("--u_min", type=float, nargs="+", default=None, help="lower input bounds (m values, or one for all channels)")
     ap.add_argument("--u_max", type=float, nargs="+", default=None, help="upper input bounds; give both or neither")
+    ap.add_argument("--y_min", type=float, nargs="+", default=None, help="lower output bounds (p values, or one for all channels)")
+    ap.add_argument("--y_max", type=float, nargs="+", default=None, help="upper output bounds; give both or neither")
     ap.add_argument("--box_safeguard", action="store_true",
                     help="with input bounds: finish solves on which the active-set iteration cycles by a primal active-set method")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
@@ -91,6 +93,10 @@ def main():
         raise ValueError("--u_min and --u_max go together (use inf / -inf for a side without a bound)")
     if a.u_min is not None:
         eng.set_input_bounds(a.u_min if len(a.u_min) > 1 else a.u_min[0], a.u_max if len(a.u_max) > 1 else a.u_max[0])
+    if (a.y_min is None) != (a.y_max is None):
+        raise ValueError("--y_min and --y_max go together (use inf / -inf for a side without a bound)")
+    if a.y_min is not None:
+        eng.set_output_bounds(a.y_min if len(a.y_min) > 1 else a.y_min[0], a.y_max if len(a.y_max) > 1 else a.y_max[0])
     if a.box_safeguard:
         eng.set_box_safeguard(True)
     eng.set_data(data["u_d"], data["y_d"])

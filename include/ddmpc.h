@@ -329,6 +329,30 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
  *     DDMPC_OPT_CLOSED_LOOP_GRAPH is ignored. */
 int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max);
 
+/* Box on the predicted outputs: y_min[ch] <= ybar[k][ch] <= y_max[ch] on every FREE prediction step (the rows that carry Q;
+ * all L of them, or the first L - n with the terminal constraint, whose last n steps stay fixed to y_s).  The bound is on
+ * ybar, not on ybar + sigma: with DDMPC_SLACK_NONE sigma stays free and the problem is always feasible; with the CONVEX slack
+ * box it can be infeasible.  There is NO infeasibility detection: such an instance ends in DDMPC_STATUS_SOLVER_ERROR at the
+ * max_iter cap or on a non-positive pivot, as a box that makes the iteration cycle does.
+ * y_min, y_max: HOST, [p]; -INFINITY / +INFINITY = no bound on that side; both NULL removes the bounds.  Shared by the batch.
+ * Takes effect at the next solve; forgets what ddmpc_prepare kept and the last solution, exactly like ddmpc_set_input_bounds.
+ * Bounds that are all infinite leave every result bit-equal to a handle that never had the call.  Independent of the input
+ * bounds: a handle may have either or both, and either call keeps the other's bounds.
+ *   DDMPC_ERR_INVALID: NaN in either array; y_min[ch] >= y_max[ch]; only one pointer NULL; with the terminal constraint, y_s
+ *     outside [y_min, y_max] (ddmpc_set_setpoints checks the same on a bounded handle).
+ *   DDMPC_ERR_UNSUPPORTED: NOMINAL controllers; (m+p)(L+n) > 271; DDMPC_WEIGHT_DENSE; a bounded channel with a Q entry of 0 on
+ *     a free prediction step; with the CONVEX slack box a Q entry of 0 on any; DDMPC_REFINE_ALWAYS (refused by ddmpc_set_option
+ *     too once bounds are set); n(m+p) > 256; a box list of more than 288 components (slack + bounded inputs + bounded
+ *     outputs; the count is named, also by ddmpc_prepare when input bounds set later make the list too long).
+ *     ddmpc_solve_from_host on such a handle is DDMPC_ERR_UNSUPPORTED.
+ * How it is served: as an input-bounded handle (above), by ddmpc_solve, ddmpc_step, ddmpc_closed_loop (fused and per step),
+ * ddmpc_get_solution and DDMPC_OPT_BOX_SAFEGUARD.  The output is a third kind of boxed component: hat = y_s - lam beta / q,
+ * d = lam / q.  A predicted output row carries ybar and sigma, so a CONVEX handle has two components on such a row and both
+ * may be active at once (the row is then hard); M keeps one column per boxed ROW (112 columns for 164 components at L = 30,
+ * n = 4, m = p = 2, CONVEX with the terminal constraint, every channel bounded).  In the solution an active output equals its
+ * bound exactly and sigma = (ybar + sigma) - bound, or +- c eps_max with both active. */
+int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* y_max);
+
 /* Values of the optimisation variables of the last ddmpc_solve, ddmpc_solve_from_host, ddmpc_step or ddmpc_closed_loop
  * (controller.py:434-445 `.value`); `out` sized as listed at DDMPC_SOL_*.  DDMPC_ERR_NOT_READY before any of them and after
  * ddmpc_set_data, ddmpc_set_setpoints or a ddmpc_prepare on the register-resident kernels ((m+p)(L+n) <= 271); a

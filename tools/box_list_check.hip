@@ -7,8 +7,9 @@
 //         -o tools/box_list_check && tools/box_list_check
 //
 // A 22-row (m = p = 1, L = 10, n = 1) and a 136-row (m = p = 2, L = 30, n = 4) table with the terminal constraint, with and
-// without the CONVEX slack box, without input bounds, with one channel bounded and with all of them.  The vectors have exactly
-// the sizes ddmpc_prepare passes, so a read or write past them is reported.
+// without the CONVEX slack box, without input bounds, with one channel bounded and with all of them, each without output bounds
+// and with every output channel bounded (two components on a predicted output row under the slack box, one column of M per
+// boxed row).  The vectors have exactly the sizes ddmpc_prepare passes, so a read or write past them is reported.
 #include "../direct_data_driven_mpc_amd/csrc/ddmpc_api.hip"
 
 int main() {
@@ -17,7 +18,8 @@ int main() {
   int bad = 0;
   for (const auto& sh : shapes)
     for (int convex = 0; convex < 2; ++convex)
-      for (int bounded = 0; bounded <= sh[0]; bounded += std::max(1, sh[0] - 1)) {   // channels with a finite bound: 0, 1, all
+      for (int bounded = 0; bounded <= sh[0]; bounded += std::max(1, sh[0] - 1))     // channels with a finite bound: 0, 1, all
+      for (int ybounded = 0; ybounded < 2; ++ybounded) {                             // output channels with one: none, all
         const int m = sh[0], nch = 2 * m, Ln = sh[1], n = sh[2], RP = 16 * sh[3], nfree = Ln - 2 * n;
         KParams k{};
         k.nch = nch; k.r = nch * Ln; k.convex = convex; k.lam = 0.04; k.sig_scale = -8e-5; k.bound = 0.002;
@@ -31,13 +33,30 @@ int main() {
         }
         std::vector<double> lo(m, -inf), hi(m, inf);
         for (int ch = 0; ch < bounded; ++ch) { lo[ch] = -4.0; hi[ch] = 6.0; }
-        const BoxList bl = bounded ? build_box_list(k, RP, ti, td, lo.data(), hi.data())
+        k.m = m;
+        std::vector<double> ylo(m, 0.5), yhi(m, 1.5);
+        const double* ul = bounded ? lo.data() : nullptr;
+        const double* uh = bounded ? hi.data() : nullptr;
+        const BoxList bl = ybounded ? build_box_list(k, RP, ti, td, ul, uh, ylo.data(), yhi.data())
+                         : bounded ? build_box_list(k, RP, ti, td, ul, uh)
                                    : build_box_list(k, RP, ti, std::vector<double>(), nullptr, nullptr);
-        const int want = (convex ? m * (Ln - n) : 0) + bounded * nfree;
-        bool ok = bl.nbox == want && bl.tab.size() == (size_t)(want + k.r) && bl.bd.size() == (bounded ? 5 * (size_t)want : 0);
-        for (int s = 0; ok && s < bl.nbox; ++s)
-          ok = bl.tab[bl.nbox + bl.tab[s]] == s && (s == 0 || bl.tab[s] > bl.tab[s - 1]) && (!bounded || std::isfinite(bl.bd[4 * want + s]));
-        printf("%3d rows  convex %d  bounded channels %d: nbox %3d (want %3d) %s\n", k.r, convex, bounded, bl.nbox, want, ok ? "ok" : "BAD");
+        const int want = (convex ? m * (Ln - n) : 0) + bounded * nfree + ybounded * m * nfree;
+        const int wcol = (convex ? m * (Ln - n) : ybounded * m * nfree) + bounded * nfree;
+        const bool bd = bounded || ybounded;
+        bool ok = bl.nbox == want && bl.ncol == wcol && bl.bd.size() == (bd ? 5 * (size_t)want : 0) &&
+                  bl.tab.size() == (ybounded ? 2 * (size_t)(want + k.r) + 1 + wcol : (size_t)(want + k.r));
+        for (int s = 0; ok && s < bl.nbox; ++s) {
+          const int rho = bl.tab[s];
+          ok = (s == 0 || rho >= bl.tab[s - 1]) && (!bd || std::isfinite(bl.bd[4 * want + s]));
+          if (!ybounded) { ok = ok && bl.tab[bl.nbox + rho] == s && (s == 0 || rho > bl.tab[s - 1]); continue; }
+          const int* col = bl.tab.data() + want + k.r;
+          const int* ofy = col + want;
+          const int* crho = ofy + k.r + 1;
+          ok = ok && ofy[k.r] == wcol && col[s] >= 0 && col[s] < wcol && crho[col[s]] == rho &&
+               (bl.tab[bl.nbox + rho] == s || ofy[rho] == s) && (bl.tab[bl.nbox + rho] < 0 || ofy[rho] < 0 || ofy[rho] == bl.tab[bl.nbox + rho] + 1);
+        }
+        printf("%3d rows  convex %d  bounded channels %d  outputs %d: nbox %3d (want %3d) columns %3d (want %3d) %s\n", k.r, convex, bounded,
+               ybounded, bl.nbox, want, bl.ncol, wcol, ok ? "ok" : "BAD");
         bad += !ok;
       }
   return bad != 0;
