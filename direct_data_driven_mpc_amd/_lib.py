@@ -29,6 +29,7 @@ OPT_CONVEX_UPDATE = 8
 OPT_GRAM_LAUNCH = 9
 OPT_CONVEX_WARM_LAW = 10
 OPT_BOX_SAFEGUARD = 11
+OPT_LARGE_BOUNDS = 12
 PIPELINE_ONE_WORKGROUP, PIPELINE_PHASES = 0, 1
 REFINE_OFF, REFINE_AUTO, REFINE_ALWAYS = 0, 1, 2
 PATH_AUTO, PATH_COLD, PATH_WARM = 0, 1, 2
@@ -40,7 +41,7 @@ EXPORTS = (
     "ddmpc_get_solution", "ddmpc_hankel", "ddmpc_cost_model", "ddmpc_kernel_name", "ddmpc_debug_stamps",
     "ddmpc_closed_loop", "ddmpc_prepare", "ddmpc_step", "ddmpc_get_gain", "ddmpc_set_option",
     "ddmpc_pe_guard", "ddmpc_solve_from_host", "ddmpc_debug_workspace", "ddmpc_debug_poison_allocations",
-    "ddmpc_closed_loop_kernel_name", "ddmpc_set_input_bounds", "ddmpc_set_output_bounds",
+    "ddmpc_closed_loop_kernel_name", "ddmpc_set_input_bounds", "ddmpc_set_output_bounds", "ddmpc_debug_large_box_order",
 )
 
 c_double_p = C.POINTER(C.c_double)
@@ -120,6 +121,8 @@ def load() -> C.CDLL:
     lib.ddmpc_solve_from_host.restype = C.c_int
     lib.ddmpc_debug_workspace.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp]
     lib.ddmpc_debug_workspace.restype = C.c_int
+    lib.ddmpc_debug_large_box_order.argtypes = [C.c_int32] * 6 + [vp] * 7 + [C.c_int64, vp]
+    lib.ddmpc_debug_large_box_order.restype = C.c_int
     for name in ("ddmpc_prepare", "ddmpc_step", "ddmpc_get_gain", "ddmpc_set_option", "ddmpc_pe_guard"):
         getattr(lib, name).restype = C.c_int
     for name in ("ddmpc_create", "ddmpc_destroy", "ddmpc_set_stream", "ddmpc_synchronize", "ddmpc_set_data",

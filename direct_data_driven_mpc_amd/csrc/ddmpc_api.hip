@@ -1,8 +1,9 @@
-// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp).
+// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp, ddmpc_rr3_box.hpp).
 // Host-side responsibilities: parameter validation with the reference's error
 // conditions (direct_data_driven_mpc_controller.py:165-168,211-222,298-343,664-670),
 // device buffer ownership, kernel-instance selection, launch.
 #include "ddmpc_rr3_law.hpp"
+#include "ddmpc_rr3_box.hpp"
 #include "ddmpc_box_law.hpp"
 #include "../../include/ddmpc.h"
 
@@ -247,7 +248,12 @@ struct ddmpc_handle {
   DevBuf d_rr2mt;                          // ... Minv of every 64 x 64 diagonal block of the two factors (ddmpc_rr2.hpp)
   DevBuf d_rr3w, d_rr3k, d_rr_fb, d_rrmeta_fb;   // ROBUST beyond 271 rows on the phase kernels (ddmpc_rr3.hpp): W + the k x k factor, the per-instance
                                           // ints; workspace / record of the fall-back (ddmpc_large_solve_kernel on instances marked 5)
-  int nA3 = 0;                            // ... first position of the slack-box components in the "boxed last" order
+  int nA3 = 0;                            // ... first position of the boxed components (slack box, bounded inputs / outputs) in the "boxed last" order
+  int nbox3 = 0;                          // ... bounded handles: components of the box table (Rr3Box)
+  int large_bounds = 0;                   // DDMPC_OPT_LARGE_BOUNDS: ddmpc_set_input_bounds / ddmpc_set_output_bounds are accepted beyond 271 rows
+  DevBuf d_r3bi, d_r3bd;                  // ... [position | output?] and [a | c | lo | hi | 1/d | shlo | shhi | bounds per channel] of that table
+  std::vector<int> ti_h;                  // the parameter tables of upload_params on the host (the order and the box table are
+  std::vector<double> td_h;               //   rebuilt from them when the bounds change)
   DevBuf d_r3y, d_r3res, d_r3zp, d_r3flag; // ... DDMPC_OPT_LARGE_AFFINE_LAW (ddmpc_rr3_law.hpp; the law itself in d_gz): substitution
                                           //   vectors, residuals and Hankel sums of a chunk of instances; [no law | re-solve | refine] flags,
                                           //   then the re-solve flags again as Rr2Solve::si (2 ints per instance)
@@ -384,6 +390,85 @@ static bool spd_inverse(std::vector<double>& a, int n) {
 static const double DDMPC_UNWEIGHTED = 1e25;
 static inline double inv_weight(double w) { return w > 0.0 ? 1.0 / w : DDMPC_UNWEIGHTED; }
 
+// ROBUST beyond the register-resident kernels on the phase kernels (ddmpc_rr3.hpp): the component order "boxed LAST" (time
+// order inside both classes), so that every active-set iteration works on the trailing block of the factor, and -- with input
+// or output bounds -- the table of boxed components the kernels test (Rr3Box).  The boxed class is the union of
+// the slack rows (CONVEX: K_WPRED, K_WTERM), the free input rows of the channels with a finite input bound and the free output
+// rows of the channels with a finite output bound.  Host arithmetic on the parameter tables (ti: 3 rows, td: 4 rows of RP
+// entries), no handle; umin / umax [m], ymin / ymax [p], null = no bounds of that kind (then no table is formed).
+struct LargeBox {
+  std::vector<int> pm;          // [position -> component (rv) | component -> position (rv)]
+  int nA = 0;                   // first boxed position
+  int nbox = 0;                 // components of the table: ascending by position, the slack before the output on a shared row
+  std::vector<int> ip;          // [position (nbox) | output component? (nbox)]
+  std::vector<double> bd;       // [a | c | lo | hi | 1/d | shlo | shhi], nbox each, then [u_min (m) | u_max (m) | y_min (p) | y_max (p)]
+};
+static LargeBox build_large_box(const KParams& k, int RP, const std::vector<int>& ti, const std::vector<double>& td,
+                                const double* umin, const double* umax, const double* ymin, const double* ymax) {
+  LargeBox lb;
+  const size_t rv = ((size_t)k.r + 1) & ~(size_t)1;
+  lb.pm.assign(2 * rv, 0);
+  auto slack = [&](int rho) { return k.convex && (ti[rho] == K_WPRED || ti[rho] == K_WTERM); };
+  auto input = [&](int rho) {
+    const int ch = rho % k.nch;
+    return umin != nullptr && ti[rho] == K_UFREE && ch < k.m && (std::isfinite(umin[ch]) || std::isfinite(umax[ch]));
+  };
+  auto output = [&](int rho) {
+    const int cy = rho % k.nch - k.m;
+    return ymin != nullptr && ti[rho] == K_WPRED && cy >= 0 && (std::isfinite(ymin[cy]) || std::isfinite(ymax[cy]));
+  };
+  int pos = 0;
+  for (int cls = 0; cls < 2; ++cls) {
+    for (int rho = 0; rho < k.r; ++rho) {
+      const bool boxed = slack(rho) || input(rho) || output(rho);
+      if ((boxed ? 1 : 0) == cls) { lb.pm[pos] = rho; lb.pm[rv + rho] = pos; ++pos; }
+    }
+    if (cls == 0) lb.nA = pos;
+  }
+  if (umin == nullptr && ymin == nullptr) return lb;
+  std::vector<int> cpos, cy;
+  std::vector<double> cols[R3B_NV];
+  auto add = [&](int i, int isy, double a, double c, double lo, double hi, double d) {
+    cpos.push_back(i); cy.push_back(isy);
+    const double v[R3B_NV] = {a, c, lo, hi, 1.0 / d, lo - a, hi - a};
+    for (int q = 0; q < R3B_NV; ++q) cols[q].push_back(v[q]);
+  };
+  for (int i = lb.nA; i < k.r; ++i) {
+    const int rho = lb.pm[i], ch = rho % k.nch;
+    const double D0 = td[rho], D1 = td[(size_t)RP + rho], tb = td[2 * (size_t)RP + rho];
+    if (slack(rho)) add(i, 0, 0.0, k.sig_scale, -k.bound, k.bound, k.lam * (D0 - D1));        // sigma = -lam beta / lamb_sigma
+    if (input(rho)) add(i, 0, tb, -k.lam * D0, umin[ch], umax[ch], k.lam * D0);               // u = u_s - lam beta / r
+    if (output(rho)) add(i, 1, tb, -k.lam * D1, ymin[ch - k.m], ymax[ch - k.m], k.lam * D1);  // ybar = y_s - lam beta / q
+  }
+  lb.nbox = (int)cpos.size();
+  lb.ip = cpos;
+  lb.ip.insert(lb.ip.end(), cy.begin(), cy.end());
+  for (int q = 0; q < R3B_NV; ++q) lb.bd.insert(lb.bd.end(), cols[q].begin(), cols[q].end());
+  const double inf = std::numeric_limits<double>::infinity();          // [u_min | u_max | y_min | y_max] for the output stage
+  for (int side = 0; side < 2; ++side)
+    for (int ch = 0; ch < k.m; ++ch) lb.bd.push_back(umin ? (side ? umax[ch] : umin[ch]) : (side ? inf : -inf));
+  for (int side = 0; side < 2; ++side)
+    for (int ch = 0; ch < k.p; ++ch) lb.bd.push_back(ymin ? (side ? ymax[ch] : ymin[ch]) : (side ? inf : -inf));
+  return lb;
+}
+
+// The order and the box table of a ROBUST handle beyond 271 rows, from the tables upload_params kept and the handle's bounds.
+static int upload_large_box(ddmpc_handle* h) {
+  const LargeBox lb = build_large_box(h->kp, 16 * h->kc.NT, h->ti_h, h->td_h, h->umin_h.empty() ? nullptr : h->umin_h.data(),
+                                      h->umin_h.empty() ? nullptr : h->umax_h.data(), h->ymin_h.empty() ? nullptr : h->ymin_h.data(),
+                                      h->ymin_h.empty() ? nullptr : h->ymax_h.data());
+  int rc;
+  h->nA3 = lb.nA;
+  h->nbox3 = lb.nbox;
+  if ((rc = h->d_perm.ensure(lb.pm.size() * sizeof(int)))) return rc;
+  HIP_TRY(hipMemcpy(h->d_perm.p, lb.pm.data(), lb.pm.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (lb.nbox == 0) return DDMPC_OK;
+  if ((rc = h->d_r3bi.ensure(lb.ip.size() * sizeof(int))) || (rc = h->d_r3bd.ensure(lb.bd.size() * sizeof(double)))) return rc;
+  HIP_TRY(hipMemcpy(h->d_r3bi.p, lb.ip.data(), lb.ip.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->d_r3bd.p, lb.bd.data(), lb.bd.size() * sizeof(double), hipMemcpyHostToDevice));
+  return DDMPC_OK;
+}
+
 static int upload_params(ddmpc_handle* h) {
   const ddmpc_params& p = h->prm;
   const KParams& k = h->kp;
@@ -483,21 +568,10 @@ static int upload_params(ddmpc_handle* h) {
     }
   }
   if (h->large && !h->large_nominal) {
-    // ROBUST beyond the register-resident kernels on the phase kernels (ddmpc_rr3.hpp): the components the slack box acts on
-    // go LAST (time order inside both classes), so that every active-set iteration works on the trailing block of the factor
-    const size_t rv = ((size_t)k.r + 1) & ~(size_t)1;
-    std::vector<int> pm(2 * rv, 0);
-    int pos = 0;
-    for (int cls = 0; cls < 2; ++cls) {
-      for (int rho = 0; rho < k.r; ++rho) {
-        const int kd = ti[0 * RP + rho];
-        const bool boxed = k.convex && (kd == K_WPRED || kd == K_WTERM);
-        if ((boxed ? 1 : 0) == cls) { pm[pos] = rho; pm[rv + rho] = pos; ++pos; }
-      }
-      if (cls == 0) h->nA3 = pos;
-    }
-    if ((rc = h->d_perm.ensure(pm.size() * sizeof(int)))) return rc;
-    HIP_TRY(hipMemcpy(h->d_perm.p, pm.data(), pm.size() * sizeof(int), hipMemcpyHostToDevice));
+    // ROBUST beyond the register-resident kernels on the phase kernels (ddmpc_rr3.hpp): the boxed components go LAST
+    h->ti_h = ti;
+    h->td_h = td;
+    if ((rc = upload_large_box(h))) return rc;
   }
   h->kp.dense_w = 0;
   h->kp.dmat = nullptr;
@@ -810,7 +884,7 @@ int ddmpc_destroy(ddmpc_handle* h) {
                     &h->d_pl, &h->d_x, &h->d_w, &h->d_usys, &h->d_ysys, &h->d_stacc,
                     &h->d_lfac, &h->d_lfacT, &h->d_gain, &h->d_prep_status, &h->d_zero, &h->d_dmat, &h->d_need, &h->d_io, &h->d_rr, &h->d_alpha, &h->d_zws, &h->d_resc, &h->d_xws, &h->d_rflag, &h->d_rrmeta, &h->d_gpre, &h->d_perm, &h->d_rr2d, &h->d_rr2res, &h->d_rr2mt, &h->d_rr2v, &h->d_rr2zp, &h->d_rr2sc, &h->d_wz, &h->d_gz, &h->d_gres, &h->d_zvirt, &h->d_rr3w, &h->d_rr3k, &h->d_rr_fb, &h->d_rrmeta_fb, &h->d_rr2cand, &h->d_rr2tol, &h->d_rr2rank, &h->d_wd, &h->d_rr2y,
                     &h->d_mcol, &h->d_cwl_tab, &h->d_cwl_sg, &h->d_cwl_ref, &h->d_r3y, &h->d_r3res, &h->d_r3zp, &h->d_r3flag,
-                    &h->d_box_bd, &h->d_ubnd, &h->d_ybnd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp};
+                    &h->d_box_bd, &h->d_ubnd, &h->d_ybnd, &h->d_r3bi, &h->d_r3bd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp};
   for (DevBuf* b : bufs) b->release();
   h->h_io.release();
   h->h_flag.release();
@@ -1019,7 +1093,7 @@ static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
   const int r = kq.r, n16 = (r + 15) & ~15, rv = (r + 1) & ~1, VL = (r + 63) & ~63;
   const size_t B = (size_t)h->batch;
   const long long m64G = rr2_m64(n16);
-  const int nA = kq.convex ? h->nA3 : r, n0 = nA & ~63;
+  const int nA = (kq.convex || h->bounded) ? h->nA3 : r, n0 = nA & ~63;
   const int ldw = ((r - n0) + 63) & ~63;
   const long long wstride = (long long)RR3_KMAX * ldw + (long long)RR3_KMAX * (RR3_KMAX + 1), kstride = 4 + RR3_KMAX + rv + 4;
   int rc;
@@ -1059,6 +1133,21 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     HIP_TRY(raise_lds_limit((const void*)rr3_solve_kernel<false>, lds));
     HIP_TRY(raise_lds_limit((const void*)rr3_solve_kernel<true>, lds));
   }
+  Rr3Box X{};
+  size_t blds = lds;
+  if (h->bounded) {
+    // input / output bounds: the instantiations that test the component table.  No law step filters their instances, and no
+    // fall-back kernel knows the bounds (an instance beyond RR3_KMAX active components ends in status 4 inside the kernel).
+    if (only != nullptr) return fail(DDMPC_ERR_UNSUPPORTED, "a bounded handle has no affine law beyond 271 rows");
+    X.nbox = h->nbox3; X.ip = (const int*)h->d_r3bi.p; X.bd = (const double*)h->d_r3bd.p;
+    blds = lds + (size_t)RR3_BOX_LDS * sizeof(double);
+    if (blds > 64 * 1024) {
+      HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<false>, blds));
+      HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<true>, blds));
+    }
+    hipLaunchKernelGGL(rr3_solve_box_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
+                       (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X);
+  } else
   hipLaunchKernelGGL(rr3_solve_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), lds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
                      (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, only);
   if (refine) {
@@ -1069,11 +1158,15 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     HankelLaunch hk;
     if ((rc = pick_hankel_launch(kq, &hk))) return rc;
     launch_hankel(hk, h->stream, (unsigned)B, H, kq, h->ud, h->yd, (int)R3_X, only_si != nullptr ? 1 : 0);
+    if (h->bounded)
+      hipLaunchKernelGGL(rr3_solve_box_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
+                         (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X);
+    else
     hipLaunchKernelGGL(rr3_solve_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), lds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
                        (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, only);
   }
   HIP_TRY(hipGetLastError());
-  {
+  if (!h->bounded) {
     // instances the phase solve marked 5 (more switched components than W holds, a failed pivot of the k x k system): the
     // one-workgroup kernel of rounds 1-4 solves them from scratch in a workspace of its own; every other workgroup leaves at once
     const size_t rr = (size_t)r, rvv = (rr + 1) & ~(size_t)1, stride = large_robust_stride(kq, h->prm);
@@ -2266,9 +2359,9 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
     case DDMPC_OPT_REFINE:
       if (value != DDMPC_REFINE_OFF && value != DDMPC_REFINE_AUTO && value != DDMPC_REFINE_ALWAYS)
         return fail(DDMPC_ERR_INVALID, "refinement mode must be DDMPC_REFINE_OFF, _AUTO or _ALWAYS");
-      if (value == DDMPC_REFINE_ALWAYS && h->bounded && h->umin_h.empty())
+      if (value == DDMPC_REFINE_ALWAYS && h->bounded && !h->large && h->umin_h.empty())
         return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_REFINE_ALWAYS is not available on a handle with output bounds (ddmpc_set_output_bounds)");
-      if (value == DDMPC_REFINE_ALWAYS && h->bounded)       // (M comes from the unrefined factor: no refined iteration on it)
+      if (value == DDMPC_REFINE_ALWAYS && h->bounded && !h->large)       // (M comes from the unrefined factor: no refined iteration on it)
         return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_REFINE_ALWAYS is not available on a handle with input bounds (ddmpc_set_input_bounds)");
       h->kp.refine = value;
       forget_prep(h);                   // the affine law is formed from a refined solve of the offset column
@@ -2293,6 +2386,9 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
           (h->prm.weight_kind == DDMPC_WEIGHT_DENSE || h->kp.r > 1024 || h->prm.n * h->kp.nch > WARM_MAX_NF))
         return fail(DDMPC_ERR_UNSUPPORTED, "the affine law of ROBUST controllers beyond 271 rows takes scalar / diagonal weights, at most 1024 rows "
                     "and n*(m+p) <= %d", WARM_MAX_NF);
+      if (value != 0 && h->large && h->bounded)
+        return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_LARGE_AFFINE_LAW is not available on a handle with input or output bounds beyond 271 rows "
+                    "(the law step knows no bounds)");
       h->large_affine = value != 0;
       forget_prep(h);
       return DDMPC_OK;
@@ -2321,6 +2417,13 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       h->convex_warm = value;
       forget_prep(h);
       return DDMPC_OK;
+    case DDMPC_OPT_LARGE_BOUNDS:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOUNDS must be 0 or 1");
+      if (value == 0 && h->large && h->bounded)
+        return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_LARGE_BOUNDS = 0 on a handle with input or output bounds beyond 271 rows: remove the "
+                    "bounds first");
+      h->large_bounds = value;            // (which calls are accepted: nothing prepared depends on it)
+      return DDMPC_OK;
     case DDMPC_OPT_BOX_SAFEGUARD:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_BOX_SAFEGUARD must be 0 or 1");
       h->box_safeguard = value;           // (which instantiation of the box kernels is launched: nothing prepared depends on it)
@@ -2338,10 +2441,35 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
         return fail(DDMPC_ERR_INVALID, "pipeline must be DDMPC_PIPELINE_ONE_WORKGROUP or DDMPC_PIPELINE_PHASES");
       if (value == DDMPC_PIPELINE_ONE_WORKGROUP && h->large_nominal && h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
         return fail(DDMPC_ERR_UNSUPPORTED, "dense weighting matrices of a NOMINAL controller beyond 271 rows run on the phase kernels only");
+      if (value == DDMPC_PIPELINE_ONE_WORKGROUP && h->large && h->bounded)
+        return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_PIPELINE_ONE_WORKGROUP is not available on a handle with input or output bounds: beyond 271 rows "
+                    "the phase kernels serve them only");
       h->large_pipeline = value;
       return DDMPC_OK;
     default: return fail(DDMPC_ERR_INVALID, "unknown option %d", option);
   }
+}
+
+// Bounds beyond 271 rows are served by the bounded instantiations of the phase kernels (ddmpc_rr3.hpp) only: why this handle
+// cannot have them, or null.  `what`: "input bounds" / "output bounds".
+static int large_bounds_refusal(const ddmpc_handle* h, const char* what) {
+  if (!h->large_bounds)     // (opt-in: without the option a handle beyond 271 rows refuses bounds as it always did)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels) unless "
+                "DDMPC_OPT_LARGE_BOUNDS = 1 (the phase kernels, 272 .. 1024 rows)", what, h->kp.r);
+  if (h->kp.r > 1024)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 1024 (the phase kernels)", what, h->kp.r);
+  if (h->large_pipeline != DDMPC_PIPELINE_PHASES)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: beyond 271 rows the phase kernels serve them only, and DDMPC_OPT_LARGE_PIPELINE selects the "
+                "one-workgroup kernel", what);
+  if (h->stamps_on)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: beyond 271 rows the phase kernels serve them only, and ddmpc_debug_stamps selects the "
+                "one-workgroup kernel", what);
+  if (h->batch > 65535)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: beyond 271 rows the phase kernels serve them only: batch %lld, the limit is 65535", what,
+                (long long)h->batch);
+  if (h->large_affine)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: not with DDMPC_OPT_LARGE_AFFINE_LAW = 1 (the law step knows no bounds)", what);
+  return DDMPC_OK;
 }
 
 // With the terminal constraint the last n predicted inputs are fixed to u_s: outside the input bounds the QP is infeasible.
@@ -2370,14 +2498,16 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
     if (const char* msg = setpoint_outside_bounds(h, h->us_h.data(), u_min, u_max)) return fail(DDMPC_ERR_INVALID, "u_min / u_max: %s", msg);
     if (p.controller_type != DDMPC_ROBUST)
       return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: ROBUST controllers only (a NOMINAL one has no regularised reduced system to iterate on)");
-    if (h->large)
-      return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels)", h->kp.r);
     if (p.weight_kind == DDMPC_WEIGHT_DENSE)
       return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)");
-    if (p.n * h->kp.nch > WARM_MAX_NF)
-      return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: n*(m+p) = %d, the affine law of ddmpc_prepare holds %d", p.n * h->kp.nch, WARM_MAX_NF);
-    if (h->kp.refine == DDMPC_REFINE_ALWAYS)
-      return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: not with DDMPC_REFINE_ALWAYS (DDMPC_OPT_REFINE must be OFF or AUTO)");
+    if (h->large) {           // (the kept factor plus one refinement pass is the normal solve there: every refinement mode)
+      if (int rc = large_bounds_refusal(h, "input bounds")) return rc;
+    } else {
+      if (p.n * h->kp.nch > WARM_MAX_NF)
+        return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: n*(m+p) = %d, the affine law of ddmpc_prepare holds %d", p.n * h->kp.nch, WARM_MAX_NF);
+      if (h->kp.refine == DDMPC_REFINE_ALWAYS)
+        return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: not with DDMPC_REFINE_ALWAYS (DDMPC_OPT_REFINE must be OFF or AUTO)");
+    }
     const int nfree = p.use_terminal_constraint ? p.L - p.n : p.L;
     const bool diag = p.weight_kind == DDMPC_WEIGHT_DIAG;
     for (int ch = 0; ch < p.m; ++ch) {
@@ -2396,7 +2526,8 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
   h->last.valid = false;
   forget_prep(h);
   h->bounded = any || !h->ymin_h.empty();
-  if (!any) { h->umin_h.clear(); h->umax_h.clear(); return DDMPC_OK; }
+  const bool order = h->large && !h->large_nominal;          // (beyond 271 rows the bounded rows join the "boxed last" class)
+  if (!any) { h->umin_h.clear(); h->umax_h.clear(); return order ? upload_large_box(h) : DDMPC_OK; }
   h->umin_h.assign(u_min, u_min + p.m);
   h->umax_h.assign(u_max, u_max + p.m);
   std::vector<double> ub(h->umin_h);
@@ -2404,7 +2535,7 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
   int rc;
   if ((rc = h->d_ubnd.ensure(ub.size() * sizeof(double)))) { h->umin_h.clear(); h->umax_h.clear(); h->bounded = !h->ymin_h.empty(); return rc; }
   HIP_TRY(hipMemcpy(h->d_ubnd.p, ub.data(), ub.size() * sizeof(double), hipMemcpyHostToDevice));
-  return DDMPC_OK;
+  return order ? upload_large_box(h) : DDMPC_OK;
 }
 
 // With the terminal constraint the last n predicted outputs are fixed to y_s (the bounds act on the free steps, but a setpoint
@@ -2434,14 +2565,16 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
     if (const char* msg = output_setpoint_outside_bounds(h, h->ys_h.data(), y_min, y_max)) return fail(DDMPC_ERR_INVALID, "y_min / y_max: %s", msg);
     if (p.controller_type != DDMPC_ROBUST)
       return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: ROBUST controllers only (a NOMINAL one has no regularised reduced system to iterate on)");
-    if (h->large)
-      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels)", h->kp.r);
     if (p.weight_kind == DDMPC_WEIGHT_DENSE)
       return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)");
-    if (p.n * h->kp.nch > WARM_MAX_NF)
-      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: n*(m+p) = %d, the affine law of ddmpc_prepare holds %d", p.n * h->kp.nch, WARM_MAX_NF);
-    if (h->kp.refine == DDMPC_REFINE_ALWAYS)
-      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: not with DDMPC_REFINE_ALWAYS (DDMPC_OPT_REFINE must be OFF or AUTO)");
+    if (h->large) {
+      if (int rc = large_bounds_refusal(h, "output bounds")) return rc;
+    } else {
+      if (p.n * h->kp.nch > WARM_MAX_NF)
+        return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: n*(m+p) = %d, the affine law of ddmpc_prepare holds %d", p.n * h->kp.nch, WARM_MAX_NF);
+      if (h->kp.refine == DDMPC_REFINE_ALWAYS)
+        return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: not with DDMPC_REFINE_ALWAYS (DDMPC_OPT_REFINE must be OFF or AUTO)");
+    }
     const int nfree = p.use_terminal_constraint ? p.L - p.n : p.L;
     const bool diag = p.weight_kind == DDMPC_WEIGHT_DIAG;
     int nout = 0;
@@ -2461,7 +2594,7 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
     for (int ch = 0; ch < p.m && !h->umin_h.empty(); ++ch)
       if (std::isfinite(h->umin_h[ch]) || std::isfinite(h->umax_h[ch])) nin += nfree;
     const int nlist = (h->kp.convex ? p.L * p.p : 0) + nin + nout;
-    if (nlist > WARM_MAX_R)
+    if (!h->large && nlist > WARM_MAX_R)      // (beyond 271 rows nothing is indexed by component in LDS but the RR3_KMAX active ones)
       return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: the box list has %d components (slack, input and output), the kernels hold %d", nlist,
                   WARM_MAX_R);
   }
@@ -2470,7 +2603,8 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
   h->last.valid = false;
   forget_prep(h);
   h->bounded = any || !h->umin_h.empty();
-  if (!any) { h->ymin_h.clear(); h->ymax_h.clear(); return DDMPC_OK; }
+  const bool order = h->large && !h->large_nominal;
+  if (!any) { h->ymin_h.clear(); h->ymax_h.clear(); return order ? upload_large_box(h) : DDMPC_OK; }
   h->ymin_h.assign(y_min, y_min + p.p);
   h->ymax_h.assign(y_max, y_max + p.p);
   std::vector<double> yb(h->ymin_h);
@@ -2478,7 +2612,7 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
   int rc;
   if ((rc = h->d_ybnd.ensure(yb.size() * sizeof(double)))) { h->ymin_h.clear(); h->ymax_h.clear(); h->bounded = !h->umin_h.empty(); return rc; }
   HIP_TRY(hipMemcpy(h->d_ybnd.p, yb.data(), yb.size() * sizeof(double), hipMemcpyHostToDevice));
-  return DDMPC_OK;
+  return order ? upload_large_box(h) : DDMPC_OK;
 }
 
 int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s) {
@@ -2898,6 +3032,9 @@ const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h) { return h ? h->loop_
 
 int ddmpc_debug_stamps(ddmpc_handle* h, int enable, uint64_t* out) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
+  if (enable && h->large && h->bounded)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_debug_stamps is not available on a handle with input or output bounds beyond 271 rows: stamps "
+                "select the one-workgroup kernel, and the phase kernels serve the bounds only");
   HIP_TRY(hipSetDevice(h->device));
   const size_t bytes = (size_t)h->batch * 16 * sizeof(uint64_t);
   if (out) {
@@ -2962,6 +3099,32 @@ int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws
   if (meta_out && meta_count > 0)
     HIP_TRY(hipMemcpy(meta_out, (const int*)h->d_rrmeta.p + (size_t)b * nmeta, sizeof(int) * (size_t)(meta_count < (int64_t)nmeta ? meta_count : (int64_t)nmeta),
                       hipMemcpyDeviceToHost));
+  return DDMPC_OK;
+}
+
+int ddmpc_debug_large_box_order(int32_t m, int32_t p, int32_t n, int32_t L, int32_t use_terminal_constraint, int32_t convex,
+                                const double* u_min, const double* u_max, const double* y_min, const double* y_max,
+                                int32_t* perm_out, int32_t* n_a, int32_t* comp_out, int64_t comp_count, int32_t* nbox) {
+  if (m <= 0 || p <= 0 || n <= 0 || L <= 0) return fail(DDMPC_ERR_INVALID, "sizes must be positive");
+  if ((u_min == nullptr) != (u_max == nullptr) || (y_min == nullptr) != (y_max == nullptr))
+    return fail(DDMPC_ERR_INVALID, "pass both arrays of a kind of bounds, or neither");
+  // the kinds of a ROBUST controller's rows as upload_params sets them; weights of 1 (the order does not depend on them)
+  KParams k{};
+  k.m = m; k.p = p; k.nch = m + p; k.r = k.nch * (L + n); k.convex = convex != 0; k.lam = 1.0; k.sig_scale = -1.0; k.bound = 1.0;
+  const int RP = (k.r + 15) & ~15;
+  std::vector<int> ti(3 * (size_t)RP, -1);
+  std::vector<double> td(4 * (size_t)RP, 0.0);
+  for (int rho = 0; rho < k.r; ++rho) {
+    const int kk = rho / k.nch, ch = rho % k.nch, kp = kk - n;
+    const bool is_int = kp < 0, is_term = use_terminal_constraint != 0 && kp >= L - n;
+    ti[rho] = ch < m ? ((is_int || is_term) ? K_UFIX : K_UFREE) : (is_int ? K_WINT : is_term ? K_WTERM : K_WPRED);
+    td[rho] = 2.0; td[(size_t)RP + rho] = 1.0;
+  }
+  const LargeBox lb = build_large_box(k, RP, ti, td, u_min, u_max, y_min, y_max);
+  if (perm_out) for (int i = 0; i < k.r; ++i) perm_out[i] = lb.pm[i];
+  if (n_a) *n_a = lb.nA;
+  if (nbox) *nbox = lb.nbox;
+  for (int64_t s = 0; comp_out && s < comp_count && s < lb.nbox; ++s) { comp_out[s] = lb.ip[s]; comp_out[comp_count + s] = lb.ip[lb.nbox + s]; }
   return DDMPC_OK;
 }
 

@@ -236,6 +236,7 @@ class DirectDataDrivenMPCController:
                 use_terminal_constraint=self.use_terminal_constraint, device=self._device)
             self._engine.set_data(np.asarray(self.u_d, dtype=np.float64)[None],
                                   np.asarray(self.y_d, dtype=np.float64)[None])
+            self._engine.set_large_bounds(True)          # (bounds of a long horizon: the phase kernels, DDMPC_OPT_LARGE_BOUNDS)
             if getattr(self, "_input_bounds", None) is not None:
                 self._engine.set_input_bounds(*self._input_bounds)
             if getattr(self, "_output_bounds", None) is not None:

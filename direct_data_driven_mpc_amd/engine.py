@@ -347,8 +347,10 @@ class BatchedDDMPC:
     def set_input_bounds(self, u_min, u_max) -> None:
         """Box on the predicted inputs of the free prediction steps, u_min[ch] <= ubar[k][ch] <= u_max[ch]
         (`ddmpc_set_input_bounds`): arrays of m entries (a scalar is broadcast), -inf / +inf = no bound on that side; both
-        None removes the bounds.  ROBUST controllers up to 271 rows with scalar / diagonal weights; takes effect at the next
-        solve and drops the prepared law and the last solution."""
+        None removes the bounds.  ROBUST controllers up to 1024 rows with scalar / diagonal weights; takes effect at the next
+        solve and drops what `prepare` kept and the last solution.  Beyond 271 rows: after `set_large_bounds(True)` only (phase
+        kernels), and at most 64 boxed components
+        -- slack, input, output -- may be active at once: an instance beyond that reports solver_error with NaN outputs."""
         lo = None if u_min is None else np.ascontiguousarray(np.broadcast_to(np.asarray(u_min, dtype=np.float64), (self.m,)))
         hi = None if u_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(u_max, dtype=np.float64), (self.m,)))
         L.check(self._lib.ddmpc_set_input_bounds(self._h, C.c_void_p(lo.ctypes.data) if lo is not None else C.c_void_p(),
@@ -364,6 +366,13 @@ class BatchedDDMPC:
         hi = None if y_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(y_max, dtype=np.float64), (self.p,)))
         L.check(self._lib.ddmpc_set_output_bounds(self._h, C.c_void_p(lo.ctypes.data) if lo is not None else C.c_void_p(),
                                                   C.c_void_p(hi.ctypes.data) if hi is not None else C.c_void_p()))
+
+    def set_large_bounds(self, on: bool) -> None:
+        """ROBUST controllers beyond 271 rows: True = `set_input_bounds` / `set_output_bounds` are accepted on a handle of
+        272 .. 1024 rows (phase kernels; at most 64 boxed components active at once, an instance beyond that reports
+        solver_error with NaN outputs), False (default) = both refuse finite bounds at that size (DDMPC_OPT_LARGE_BOUNDS).
+        No effect up to 271 rows."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_BOUNDS, 1 if on else 0))
 
     def set_box_safeguard(self, on: bool) -> None:
         """Input / output bounds: True = an instance whose active-set iteration reaches `max_iter` without a stable set is finished by a

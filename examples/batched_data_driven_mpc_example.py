@@ -91,6 +91,7 @@ def main():
                          f"(instance {bad}: rank {int(rank[bad])}).")
     if (a.u_min is None) != (a.u_max is None):
         raise ValueError("--u_min and --u_max go together (use inf / -inf for a side without a bound)")
+    eng.set_large_bounds(True)                   # (bounds with a long horizon, beyond 271 rows: the phase kernels)
     if a.u_min is not None:
         eng.set_input_bounds(a.u_min if len(a.u_min) > 1 else a.u_min[0], a.u_max if len(a.u_max) > 1 else a.u_max[0])
     if (a.y_min is None) != (a.y_max is None):

@@ -162,7 +162,7 @@ extern "C" {
                                          takes the per-step path when there is any.  0 (default) = the filtered cold re-solve.  Setting
                                          it invalidates the prepared law.  DDMPC_ERR_UNSUPPORTED with dense weights, beyond 271 rows and
                                          for a boxed output component without weight (Q entry 0); no effect without the slack box */
-#define DDMPC_OPT_BOX_SAFEGUARD 11      /* handles with input bounds (ddmpc_set_input_bounds): 1 = an instance whose primal-dual active-set
+#define DDMPC_OPT_BOX_SAFEGUARD 11      /* (no effect beyond 271 rows) handles with input bounds (ddmpc_set_input_bounds): 1 = an instance whose primal-dual active-set
                                          iteration reaches max_iter without a stable set is not reported DDMPC_STATUS_SOLVER_ERROR but
                                          solved again, in the same launch, by a primal active-set method on the same law, M and box
                                          table (one component enters or leaves the working set per solve, the cost falls with every
@@ -175,6 +175,14 @@ extern "C" {
                                          any handle, no effect without finite bounds; keeps what ddmpc_prepare kept.  A CONVEX handle
                                          without bounds keeps the slack-only kernels and is not covered: one finite bound puts it on
                                          this route */
+#define DDMPC_OPT_LARGE_BOUNDS 12       /* ROBUST controllers beyond 271 rows: 1 = ddmpc_set_input_bounds / ddmpc_set_output_bounds are accepted
+                                         on a handle of 272 .. 1024 rows that the phase kernels serve ("Bounds beyond 271 rows" at
+                                         ddmpc_set_input_bounds: at most 64 components active at once).  0 (default) = both calls
+                                         refuse finite bounds beyond 271 rows with DDMPC_ERR_UNSUPPORTED, as they did before the
+                                         option existed; the message names the option.  Opt-in because the limits of that route
+                                         (the 64-component cap, no safeguard) are not those of the register-resident one.  Accepted
+                                         on any handle, no effect up to 271 rows; 0 on a bounded handle beyond 271 rows is
+                                         DDMPC_ERR_UNSUPPORTED (remove the bounds first).  Values other than 0 / 1: DDMPC_ERR_INVALID */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -304,11 +312,11 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
  * every result bit-equal to a handle that never had the call.
  *   DDMPC_ERR_INVALID: NaN in either array; u_min[ch] >= u_max[ch]; only one pointer NULL; with the terminal constraint, u_s
  *     outside [u_min, u_max] (the QP is infeasible by construction; ddmpc_set_setpoints checks the same on a bounded handle).
- *   DDMPC_ERR_UNSUPPORTED: NOMINAL controllers; (m+p)(L+n) > 271; DDMPC_WEIGHT_DENSE; a bounded channel with an R entry of 0 on
- *     a free prediction step; with the CONVEX slack box a Q entry of 0 on one; DDMPC_REFINE_ALWAYS (refused by ddmpc_set_option
- *     too once bounds are set); n(m+p) > 256, the one shape for which ddmpc_prepare forms no law at that size (trajectories
- *     beyond the LDS are served: their law comes from the streamed Gram).  ddmpc_solve_from_host on a bounded handle is
- *     DDMPC_ERR_UNSUPPORTED.
+ *   DDMPC_ERR_UNSUPPORTED: NOMINAL controllers; DDMPC_WEIGHT_DENSE; a bounded channel with an R entry of 0 on
+ *     a free prediction step; with the CONVEX slack box a Q entry of 0 on one.  Up to 271 rows also: DDMPC_REFINE_ALWAYS (refused
+ *     by ddmpc_set_option too once bounds are set); n(m+p) > 256, the one shape for which ddmpc_prepare forms no law at that
+ *     size (trajectories beyond the LDS are served: their law comes from the streamed Gram).  Beyond 271 rows: see "Bounds
+ *     beyond 271 rows" below.  ddmpc_solve_from_host on a bounded handle is DDMPC_ERR_UNSUPPORTED at every size.
  * How a bounded handle is served.  A bound that is active makes its input row hard, a diagonal rank-k change of the system of
  * the empty active set, exactly what the slack box does.  Every call runs the primal-dual active-set iteration
  * over the whole box list -- the slack components (CONVEX) and the free input rows of the bounded channels, from the empty set; an
@@ -326,7 +334,25 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
  *     and the unrefined M like the others and report DDMPC_STATUS_OPTIMAL_INACCURATE when their final active set is not empty.
  *   ddmpc_solve / DDMPC_PATH_COLD: the cold contract -- the trajectories are read anew, into a preparation of the call's own
  *     (a second set of the buffers above) that is dropped afterwards; a kept ddmpc_prepare stays valid.
- *     DDMPC_OPT_CLOSED_LOOP_GRAPH is ignored. */
+ *     DDMPC_OPT_CLOSED_LOOP_GRAPH is ignored.
+ * Bounds beyond 271 rows ((m+p)(L+n) = 272 .. 1024; both calls, same arguments and meaning), with DDMPC_OPT_LARGE_BOUNDS = 1;
+ * without the option finite bounds are DDMPC_ERR_UNSUPPORTED at this size.  There is no affine law and no M
+ * at this size: the phase kernels (DDMPC_PIPELINE_PHASES) keep the factor of the EMPTY active set and treat every active
+ * component -- slack, input or output -- as one column of a Woodbury update on the trailing block of the factor, the bounded rows
+ * joining the slack rows in the "boxed last" order; one exact-Hankel refinement pass on the system of the final active set
+ * follows unless DDMPC_REFINE_OFF (all three refinement modes are accepted: the kept factor plus that pass is the normal solve
+ * here).  Same iteration rule, max_iter cap and status 4 at the cap; an active input or output equals its bound exactly.
+ * Served by ddmpc_solve, ddmpc_prepare (the factors only) + ddmpc_step (bit-equal to ddmpc_solve), the per-step
+ * ddmpc_closed_loop ("ddmpc_plant_kernel": there is no fused loop at this size) and ddmpc_get_solution.
+ *   LIMIT: at most 64 components (slack + input + output) may be active at once in any iteration.  No fall-back kernel knows the
+ *     bounds: an instance that exceeds 64, or whose k x k pivot is not positive, reports DDMPC_STATUS_SOLVER_ERROR with `iters`
+ *     the iteration at which it happened and NaN in u_opt / cost; the other instances of the batch are not affected.
+ *   DDMPC_ERR_UNSUPPORTED, each with a message that names the reason: DDMPC_OPT_LARGE_BOUNDS = 0; more than 1024 rows; a handle that is not on the phase
+ *     kernels (DDMPC_OPT_LARGE_PIPELINE = DDMPC_PIPELINE_ONE_WORKGROUP, ddmpc_debug_stamps enabled, batch > 65535);
+ *     DDMPC_OPT_LARGE_AFFINE_LAW = 1.  In the reverse order the same three are refused on a bounded handle:
+ *     ddmpc_set_option(DDMPC_OPT_LARGE_PIPELINE, DDMPC_PIPELINE_ONE_WORKGROUP), ddmpc_set_option(DDMPC_OPT_LARGE_AFFINE_LAW, 1)
+ *     and ddmpc_debug_stamps(enable).  NOMINAL, DDMPC_WEIGHT_DENSE and zero weights as above.
+ *   DDMPC_OPT_BOX_SAFEGUARD is accepted and has no effect beyond 271 rows; the box list has no length limit there. */
 int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max);
 
 /* Box on the predicted outputs: y_min[ch] <= ybar[k][ch] <= y_max[ch] on every FREE prediction step (the rows that carry Q;
@@ -340,11 +366,12 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
  * bounds: a handle may have either or both, and either call keeps the other's bounds.
  *   DDMPC_ERR_INVALID: NaN in either array; y_min[ch] >= y_max[ch]; only one pointer NULL; with the terminal constraint, y_s
  *     outside [y_min, y_max] (ddmpc_set_setpoints checks the same on a bounded handle).
- *   DDMPC_ERR_UNSUPPORTED: NOMINAL controllers; (m+p)(L+n) > 271; DDMPC_WEIGHT_DENSE; a bounded channel with a Q entry of 0 on
- *     a free prediction step; with the CONVEX slack box a Q entry of 0 on any; DDMPC_REFINE_ALWAYS (refused by ddmpc_set_option
- *     too once bounds are set); n(m+p) > 256; a box list of more than 288 components (slack + bounded inputs + bounded
- *     outputs; the count is named, also by ddmpc_prepare when input bounds set later make the list too long).
- *     ddmpc_solve_from_host on such a handle is DDMPC_ERR_UNSUPPORTED.
+ *   DDMPC_ERR_UNSUPPORTED: NOMINAL controllers; DDMPC_WEIGHT_DENSE; a bounded channel with a Q entry of 0 on
+ *     a free prediction step; with the CONVEX slack box a Q entry of 0 on any.  Up to 271 rows also: DDMPC_REFINE_ALWAYS (refused
+ *     by ddmpc_set_option too once bounds are set); n(m+p) > 256; a box list of more than 288 components (slack + bounded
+ *     inputs + bounded outputs; the count is named, also by ddmpc_prepare when input bounds set later make the list too long).
+ *     Beyond 271 rows: "Bounds beyond 271 rows" at ddmpc_set_input_bounds -- 272 .. 1024 rows on the phase kernels, at most 64
+ *     components active at once.  ddmpc_solve_from_host on such a handle is DDMPC_ERR_UNSUPPORTED.
  * How it is served: as an input-bounded handle (above), by ddmpc_solve, ddmpc_step, ddmpc_closed_loop (fused and per step),
  * ddmpc_get_solution and DDMPC_OPT_BOX_SAFEGUARD.  The output is a third kind of boxed component: hat = y_s - lam beta / q,
  * d = lam / q.  A predicted output row carries ybar and sigma, so a CONVEX handle has two components on such a row and both
@@ -447,7 +474,8 @@ int ddmpc_debug_stamps(ddmpc_handle* h, int enable, uint64_t* out);
  * Round 5: ws_count < 0 (NOMINAL, phase kernels): the pivot candidates of G's factorisation in the order they were decided on
  * (16 ceil(r / 16) doubles: the pivot where a column was accepted, the residue where it was skipped; tools/pivot_gap_study.py).
  * ROBUST controllers beyond 271 rows on the phase kernels: meta_out receives the per-instance record of the last solve
- * [k, state, iterations, k, switched positions (64), active set (r rounded up to 2), start tick, ticks (100 MHz), -, -] and
+ * [k, state, iterations, k, switched positions (64), active set (r rounded up to 2), start tick, ticks (100 MHz), peak k of a
+ * bounded handle, -] and
  * *ws_avail = 0 (tools/rr3_schedule.py).  What is read is what the last solve left, on the implementation that served it:
  * DDMPC_ERR_NOT_READY when that was none of the above (no solve yet, the register-resident kernels, the one-workgroup ROBUST
  * kernel). */
@@ -459,6 +487,17 @@ int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws
  * wrote -- fresh device memory is zero on this stack, which hides such reads in a standalone run.  Returns the previous setting.
  * (tests/test_gpu_round4.py) */
 int ddmpc_debug_poison_allocations(int byte);
+
+/* Diagnostics only, host arithmetic, no device and no handle: the component order of a ROBUST controller beyond 271 rows on
+ * the phase kernels, "boxed LAST" -- the boxed class is the union of the slack rows (convex != 0: every predicted output row),
+ * the free input rows of the channels with a finite input bound and the free output rows of the channels with a finite output
+ * bound; time order inside both classes.  u_min / u_max [m], y_min / y_max [p], both of a kind NULL = no bounds of that kind.
+ * perm_out [(m+p)(L+n)]: position -> row; *n_a: the first boxed position; *nbox: components of the box table (0 without bounds);
+ * comp_out [2 comp_count]: position of component s, then whether it is an output component (ascending by position, the slack
+ * before the output on a shared row), at most comp_count of them.  Any output may be NULL.  (tests/test_large_bounds_reference.py) */
+int ddmpc_debug_large_box_order(int32_t m, int32_t p, int32_t n, int32_t L, int32_t use_terminal_constraint, int32_t convex,
+                                const double* u_min, const double* u_max, const double* y_min, const double* y_max,
+                                int32_t* perm_out, int32_t* n_a, int32_t* comp_out, int64_t comp_count, int32_t* nbox);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,5 @@
-// Host check of build_box_list (ddmpc_api.hip) under the address and undefined-behaviour sanitizers: no device is used.
+// Host check of build_box_list and build_large_box (ddmpc_api.hip) under the address and undefined-behaviour sanitizers: no
+// device is used.
 //
 //   python -m direct_data_driven_mpc_amd.build
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Xarch_host -fsanitize=address,undefined -Idirect_data_driven_mpc_amd/csrc \
@@ -9,7 +10,9 @@
 // A 22-row (m = p = 1, L = 10, n = 1) and a 136-row (m = p = 2, L = 30, n = 4) table with the terminal constraint, with and
 // without the CONVEX slack box, without input bounds, with one channel bounded and with all of them, each without output bounds
 // and with every output channel bounded (two components on a predicted output row under the slack box, one column of M per
-// boxed row).  The vectors have exactly the sizes ddmpc_prepare passes, so a read or write past them is reported.
+// boxed row).  The vectors have exactly the sizes ddmpc_prepare passes, so a read or write past them is reported.  Every case
+// also goes through build_large_box (the "boxed last" order and the component table of the phase kernels beyond 271 rows):
+// a permutation with its inverse, nA and the component count, positions ascending with the slack before the output on a row.
 #include "../direct_data_driven_mpc_amd/csrc/ddmpc_api.hip"
 
 int main() {
@@ -58,6 +61,31 @@ int main() {
         printf("%3d rows  convex %d  bounded channels %d  outputs %d: nbox %3d (want %3d) columns %3d (want %3d) %s\n", k.r, convex, bounded,
                ybounded, bl.nbox, want, bl.ncol, wcol, ok ? "ok" : "BAD");
         bad += !ok;
+        // the same tables through build_large_box: the order "boxed last" and the component table of the phase kernels
+        // beyond 271 rows (the builder does not look at the row count)
+        k.p = m;
+        const LargeBox lb = build_large_box(k, RP, ti, td, ul, uh, ybounded ? ylo.data() : nullptr, ybounded ? yhi.data() : nullptr);
+        const int rv = (k.r + 1) & ~1;
+        int rows = 0;
+        for (int rho = 0; rho < k.r; ++rho)
+          rows += (convex && (ti[rho] == K_WPRED || ti[rho] == K_WTERM)) || (ti[rho] == K_UFREE && rho % nch < bounded) ||
+                  (ybounded && ti[rho] == K_WPRED);
+        const int lwant = bd ? want : 0;
+        bool lok = lb.nA == k.r - rows && lb.nbox == lwant && lb.pm.size() == 2 * (size_t)rv && lb.ip.size() == 2 * (size_t)lwant &&
+                   lb.bd.size() == (bd ? (size_t)R3B_NV * lwant + 4 * (size_t)m : 0);
+        std::vector<int> seen((size_t)k.r, 0);
+        for (int i = 0; lok && i < k.r; ++i) {
+          const int rho = lb.pm[i];
+          lok = rho >= 0 && rho < k.r && !seen[rho]++ && lb.pm[rv + rho] == i;
+        }
+        for (int s = 0; lok && s < lb.nbox; ++s) {
+          const int i = lb.ip[s], isy = lb.ip[lb.nbox + s];
+          lok = i >= lb.nA && i < k.r && (s == 0 || i > lb.ip[s - 1] || (i == lb.ip[s - 1] && isy && !lb.ip[lb.nbox + s - 1])) &&
+                std::isfinite(lb.bd[(size_t)R3B_INVD * lb.nbox + s]) && lb.bd[(size_t)R3B_INVD * lb.nbox + s] > 0.0 &&
+                (!isy || ti[lb.pm[i]] == K_WPRED);
+        }
+        printf("          boxed last: nA %3d (want %3d) components %3d (want %3d) %s\n", lb.nA, k.r - rows, lb.nbox, lwant, lok ? "ok" : "BAD");
+        bad += !lok;
       }
   return bad != 0;
 }

@@ -1,0 +1,125 @@
+"""Dev timing (GPU): input and output bounds on ROBUST controllers beyond 271 rows (ddmpc_rr3_box.hpp) -- an
+unbounded handle against a mild input box and a mild output box, same process, same data, batch 512 at the data tail:
+
+  cfg5    m = p = 8, n = 8, L = 30, N = 2000: 608 rows (the cfg5size_robust problem of bench.py).  The boxes are taken from the
+          unbounded solution: per channel the 0.5 % / 99.5 % quantiles of its free inputs (outputs) over the batch, widened to
+          contain the setpoint -- about one boxed value in a hundred starts outside.
+  tank70  four-tank, L = 70, N = 700: 296 rows.  Inputs in [-4, 6]; outputs y <= (0.66, 0.775).
+
+Per case and slack type: ddmpc_prepare, ddmpc_solve and ddmpc_step in ms by HIP events (median of --reps repeats after a warm-up
+call), solves per step (min / median / max of `iters`), the peak number of active components per instance (min / median / max,
+from ddmpc_debug_workspace), the position n0 where the trailing block starts, and the instances that are not optimal.
+
+    python tools/large_bounds_time.py [--batch 512] [--reps 5] [--json out.json]
+"""
+import argparse, ctypes as C, json, sys
+import numpy as np
+import torch                                   # (before the library: torch initialises the HIP runtime itself)
+sys.path.insert(0, ".")
+from direct_data_driven_mpc_amd import _lib as L
+from direct_data_driven_mpc_amd.engine import BatchedDDMPC
+from direct_data_driven_mpc_amd.harness import controller_params, generate_batch
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=512)
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--json", default="")
+a = ap.parse_args()
+
+lib = L.load()
+if lib.ddmpc_device_count() <= 0:
+    raise SystemExit("large_bounds_time: no HIP device visible -- the engine has no CPU fallback, nothing to time")
+
+B = a.batch
+INF = np.inf
+dev = torch.device("cuda", 0)
+t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+
+def ev_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()                                        # warm-up: allocations, LDS attributes
+    out = []
+    for _ in range(a.reps):
+        e0.record(); fn(); e1.record(); e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return float(np.median(out))
+
+
+def record(eng, r):
+    """[k, state, iterations, peak k] of every instance of the last solve."""
+    rv = (r + 1) & ~1
+    n = 4 + 64 + rv + 4
+    meta = np.zeros(n, np.int32)
+    out = np.zeros((B, 4), np.int64)
+    for b in range(B):
+        L.check(lib.ddmpc_debug_workspace(eng._h, b, C.c_void_p(), 0, C.c_void_p(meta.ctypes.data), n, C.c_void_p(), C.c_void_p()))
+        out[b] = (meta[0], meta[1], meta[2], meta[4 + 64 + rv + 2])
+    return out
+
+
+def problem(name):
+    if name == "cfg5":
+        rng = np.random.default_rng(0)
+        ns = n = 8; m = p = 8; Lh = 30; N = 2000
+        A = rng.normal(size=(ns, ns)); A *= 0.9 / max(abs(np.linalg.eigvals(A)))
+        plant = dict(A=A, B=rng.normal(size=(ns, m)), C=rng.normal(size=(p, ns)), D=np.zeros((p, m)), eps_max=0.002)
+        u_s = 0.1 * np.ones(m)
+        y_s = (plant["C"] @ np.linalg.inv(np.eye(ns) - A) @ plant["B"]) @ u_s
+        d = generate_batch(range(B), N=N, plant=plant)
+        return dict(n=n, m=m, p=p, L=Lh, N=N, u_s=u_s, y_s=y_s, d=d, boxes=None)
+    cfg = controller_params()
+    d = generate_batch(range(B), N=700)
+    return dict(n=4, m=2, p=2, L=70, N=700, u_s=cfg["u_s"].reshape(-1), y_s=cfg["y_s"].reshape(-1), d=d,
+                boxes=dict(input=([-4.0, -4.0], [6.0, 6.0]), output=([-INF, -INF], [0.66, 0.775])))
+
+
+res = {"batch": B, "reps": a.reps, "cases": []}
+for name in ("cfg5", "tank70"):
+    pb = problem(name)
+    n, m, p, Lh, N = pb["n"], pb["m"], pb["p"], pb["L"], pb["N"]
+    r = (m + p) * (Lh + n)
+    ud, yd = t(pb["d"]["u_d"]), t(pb["d"]["y_d"])
+    up, yp = t(pb["d"]["u_d"][:, -n:, :].reshape(B, -1)), t(pb["d"]["y_d"][:, -n:, :].reshape(B, -1))
+    for slack in ("none", "convex"):
+        eng = BatchedDDMPC(n=n, m=m, p=p, L_=Lh, N=N, Q=3.0, R=1e-4, u_s=pb["u_s"], y_s=pb["y_s"], batch=B, controller_type=L.ROBUST,
+                           slack_type=L.SLACK_CONVEX if slack == "convex" else L.SLACK_NONE, eps_max=0.002, lamb_alpha=50.0,
+                           lamb_sigma=1000.0, c=1.0, device=0)
+        eng.set_large_bounds(True)
+        eng.set_data(ud, yd)
+        boxes = pb["boxes"]
+        if boxes is None:                       # from the unbounded solution (free steps: the terminal ones sit at the setpoint)
+            eng.solve(up, yp)
+            ub = eng.get_solution("ubar").reshape(B, Lh + n, m)[:, n:Lh]
+            yb = eng.get_solution("ybar").reshape(B, Lh + n, p)[:, n:Lh]
+            q = lambda v, s, c: (np.minimum(np.quantile(v, 0.005, axis=(0, 1)), c - s), np.maximum(np.quantile(v, 0.995, axis=(0, 1)), c + s))
+            boxes = dict(input=q(ub, 1e-3, pb["u_s"]), output=q(yb, 1e-3, pb["y_s"]))
+        for kind in ("unbounded", "input", "output"):
+            eng.set_input_bounds(None, None)
+            eng.set_output_bounds(None, None)
+            if kind == "input":
+                eng.set_input_bounds(*boxes["input"])
+            if kind == "output":
+                eng.set_output_bounds(*boxes["output"])
+            o = eng.solve(up, yp)
+            rec = dict(problem=name, rows=r, slack=slack, box=kind)
+            if kind != "unbounded":
+                rec["bounds"] = [np.asarray(v, float).tolist() for v in boxes[kind]]
+            rec["prepare_ms"] = ev_ms(lambda: (eng.set_data(ud, yd), eng.prepare()))
+            rec["solve_ms"] = ev_ms(lambda: eng.solve(up, yp, *o))
+            eng.prepare()
+            o = eng.step(up, yp)
+            rec["step_ms"] = ev_ms(lambda: eng.step(up, yp, *o))
+            st, it = o[2].cpu().numpy(), o[3].cpu().numpy()
+            rec["not_optimal"] = int(np.count_nonzero(st))
+            rec["solves_per_step"] = [int(it.min()), float(np.median(it)), int(it.max())]
+            kq = record(eng, r)
+            peak = kq[:, 3] if kind != "unbounded" else kq[:, 0]
+            rec["active_components"] = [int(peak.min()), float(np.median(peak)), int(peak.max())]
+            res["cases"].append(rec)
+            print(json.dumps(rec), flush=True)
+        eng.close()
+
+if a.json:
+    with open(a.json, "w") as f:
+        json.dump(res, f, indent=1)
