@@ -338,23 +338,39 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
     bool dst_valid = false;  // a finished Delta tile waits in `dst` (workgroup-uniform)
     // -(G + lam*D) of one raw Gram tile; -identity on dummy rows; rhs COLUMN rE := -t (mirrored into the diagonal tile);
     // dense weighting matrices: lam * W^-1 is a full symmetric matrix shared by the batch (L2)
-    auto fix_tile = [&](auto II, auto JJ, const d4& raw) __attribute__((always_inline)) -> d4 {
+    // No LDS read of the fix-up sits behind a lane test: a read under `if (lane owns the entry)` becomes an exec-masked block
+    // with its own wait, one LDS round trip after the other (36 of them for the nine diagonal tiles of the benchmark,
+    // while the other waves stand at the barrier behind the fix-up).  Every read below is unconditional -- its index is
+    // inside the RP doubles of dvec / tvec for every lane -- and only the lanes that own an entry take the value (no
+    // product with zero anywhere: the other lanes keep their bits, -0.0 and NaN cannot leak).
+    //   dd: dvec[16 J + l15], the only diagonal entry lane (l4, l15) of tile (J, J) can own (register (l15 - l4) / 4 when
+    //       that is an integer); read by the caller, all diagonal tiles of the wave in one batch (diagonal tiles only).
+    //   The diagonal entries keep their four exec-masked blocks per tile, now two vector instructions and no wait each
+    //   (the empty asm keeps them blocks): as selects they cost <9,4> 184 B of scratch on the panel wave's path -- the
+    //   lane masks of all tiles then live side by side in SGPRs that spill into VGPR lanes.  The rhs entries are selects.
+    auto fix_tile = [&](auto II, auto JJ, const d4& raw, const double dd) __attribute__((always_inline)) -> d4 {
       constexpr int I = II, J = JJ;
       const int gc = 16 * I + l15;                        // global column (i side)
       d4 v = -raw;
       if constexpr (I == J) {
+        const bool live = gc < r;
+        const int dj = l15 - l4;
         static_for<4>([&](auto j) __attribute__((always_inline)) {
-          const int gr = 16 * J + l4 + 4 * j;
-          if (gr == gc && gr < r) { kmax = fmax(kmax, raw[j()]); v[j()] -= P.lam * dvec[gr]; }
+          const bool hit = live && (dj == 4 * j);         // gr == gc && gr < r
+          if (hit) { asm volatile(""); kmax = fmax(kmax, raw[j()]); v[j()] -= P.lam * dd; }
         });
       }
       if (16 * I + 15 >= r) {                             // wave-uniform: tile columns that touch the padding / rhs column
+        double tg[4];                                     // targets of the tile's rows (the rhs column), of its own column (the mirror)
+        static_for<4>([&](auto j) __attribute__((always_inline)) { tg[j()] = tvec[16 * J + l4 + 4 * j]; });
+        double tc = 0.0;
+        if constexpr (I == J) tc = tvec[gc];
         static_for<4>([&](auto j) __attribute__((always_inline)) {
           const int gr = 16 * J + l4 + 4 * j;
           if (gr >= r || gc >= r) v[j()] = 0.0;
           if (I == J && gr == gc && gr >= r && gr < rE) v[j()] = -1.0;
-          if (gc == rE && gr < r) v[j()] = -tvec[gr];
-          if (I == J && gr == rE && gc < r) v[j()] = -tvec[gc];
+          if (gc == rE && gr < r) v[j()] = -tg[j()];
+          if (I == J && gr == rE && gc < r) v[j()] = -tc;
         });
       }
       if (P.dense_w) {
@@ -694,7 +710,7 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
       if constexpr (WAVE == 0 && W > 1) {
         if (rE >= 16) {                                   // (tiny systems keep the plain order: their rhs row sits in tile 0)
           constexpr int S0 = TM::slot(0, 0);
-          d4 Ad = fix_tile(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, acc[S0]);
+          d4 Ad = fix_tile(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, acc[S0], dvec[l15]);
           d4 Et;
           factor_begin(Ad, Et);
           static_for<4>([&](auto q) __attribute__((always_inline)) { substep(Ad, Et, acc[S0], q, no_pend); });
@@ -706,12 +722,31 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
     }
 
     // ---- accumulators := -(G + lam*D) (fix_tile above)
+    // (dvec and tvec are rewritten at the top of every active-set iteration: read here, behind its barrier, in every pass)
+    const long long tfx0 = now();
+    double dgv[NT];                                       // dvec entries of this wave's diagonal tiles: one batch of reads, one wait
+    static_for<WT::tab.n>([&](auto K) __attribute__((always_inline)) {
+      constexpr int I = WT::tab.I[K], J = WT::tab.J[K];
+      if constexpr (I == J) dgv[J] = dvec[16 * J + l15];
+    });
     static_for<WT::tab.n>([&](auto K) __attribute__((always_inline)) {
       constexpr int I = WT::tab.I[K], J = WT::tab.J[K];
       constexpr int S = TM::slot(I, J);
-      if (!(I == 0 && J == 0 && f0_done)) acc[S] = fix_tile(std::integral_constant<int, I>{}, std::integral_constant<int, J>{}, acc[S]);
+      if (!(I == 0 && J == 0 && f0_done))
+        acc[S] = fix_tile(std::integral_constant<int, I>{}, std::integral_constant<int, J>{}, acc[S], I == J ? dgv[J] : 0.0);
     });
+    const long long tfx1 = now();
     __syncthreads();      // every wave has read tvec (targets) for its rhs entries; LT / PT2 / PB are free
+    if constexpr (!CVX) {
+      // diagnostics: the panel wave's cycles in the fix-up of its tiles and at the barrier behind it -- the part of stamp 3 -> 4
+      // ahead of the first accounted interval -- in the upper halves of slots 10 and 11 (the sums added to the lower halves
+      // behind the factorisation stay far below 2^32).  Stored at once: kept until then they would cost the factorisation SGPRs.
+      if (timing && threadIdx.x == 0) {
+        const long long tfx2 = now();
+        stamps[10] = (unsigned long long)(tfx1 - tfx0) << 32;
+        stamps[11] = (unsigned long long)(tfx2 - tfx1) << 32;
+      }
+    }
 
     // ---- blocked Cholesky, 16-wide panels, software-pipelined over the tile columns --------------------------------
     // Step Jb (M_Jb = L_JJ^-1 of tile column Jb is in LT):
@@ -880,7 +915,7 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
     if (timing && threadIdx.x == 0) {
       stamps[7] = tphF; stamps[8] = tphB;
       if constexpr (CVX) { stamps[9] = 0; stamps[10] = 0; stamps[11] = 0; }         // (the rank-k update's three phases go there)
-      else { stamps[9] = tphT; stamps[10] = tphA; stamps[11] = tphU; }
+      else { stamps[9] = tphT; stamps[10] += tphA; stamps[11] += tphU; }            // (upper halves: the fix-up split, written above)
     }
     stamp();   // 4
 
@@ -1410,6 +1445,17 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
     }
     if (!again) break;
   }
+  // the output stage's three table entries (L2): one batch of unconditional loads (index clamped into the table) ahead of
+  // everything else in the stage, instead of two or three dependent groups behind its branches; consumed under `rho < r`
+  double o_wq[NE], o_tb[NE];
+  int o_idx[NE];
+  static_for<NE>([&](auto e) __attribute__((always_inline)) {
+    const int rho = tid + e * NTHR;
+    const int rc = rho < RP ? rho : RP - 1;
+    o_wq[e()] = P.tabd[3 * RP + rc];
+    o_tb[e()] = P.tabd[2 * RP + rc];
+    o_idx[e()] = P.tabi[2 * RP + rc];
+  });
   if (flags[0] != 0) status = 4;
   const int lane = tid & 63;
 
@@ -1422,8 +1468,10 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
     if (rho < r) {
       const int s_act = act[rho];
       const double b = beta[rho];
-      const double D = s_act ? cD1[rho] : cD0[rho];
-      const double t = cT[rho] + s_act * P.bound;
+      const double d0 = cD0[rho], d1 = cD1[rho];    // (both read, then selected: no LDS read behind a lane test)
+      const double D = s_act ? d1 : d0;
+      const double ct = cT[rho];
+      const double t = ct + s_act * P.bound;
       bmx = fmax(bmx, fabs(b)); tmx = fmax(tmx, fabs(t));
       double z = t - P.lam * D * b;
       if (P.dense_w) {                              // z = t - lam (W^-1 beta): one row of the dense matrix
@@ -1432,9 +1480,9 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
         for (int j = 0; j < r; ++j) sdb += dr[j] * beta[j];
         z = t - P.lam * (D * b + sdb);
       }
-      const double wq = P.tabd[3 * RP + rho];
-      const double tb = P.tabd[2 * RP + rho];
-      const int oidx = P.tabi[2 * RP + rho];
+      const double wq = o_wq[e()];
+      const double tb = o_tb[e()];
+      const int oidx = o_idx[e()];
       finite = finite && (fabs(b) < 1e300);
       double contrib = P.lam * b * z;
       const int kind = cK[rho];
@@ -1445,7 +1493,7 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
         if (s_act != 0) contrib += P.box_cost;
       } else
       if (kind == K_UFREE || kind == K_YFREE) { const double dlt = z - tb; contrib += wq * dlt * dlt; }
-      else if (kind == K_WINT) { const double sg = z - cT[rho]; contrib += P.lamb_sigma * sg * sg; }
+      else if (kind == K_WINT) { const double sg = z - ct; contrib += P.lamb_sigma * sg * sg; }
       else if (kind == K_WTERM) { const double sg = z - tb; contrib += P.lamb_sigma * sg * sg; }
       else if (kind == K_WPRED) {
         const double sg = (s_act != 0) ? s_act * P.bound : -P.lam * b / P.lamb_sigma;

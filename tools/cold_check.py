@@ -65,7 +65,8 @@ def timing(B=4096, slack=0, stamps=True, refine="auto"):
             print("   %-16s median %8.0f cycles" % (nm, np.median(dt[:, i])))
         print("   total %8.0f cycles" % np.median(st[:, 14] - st[:, 0]))
         for i, nm in enumerate(["F factor (wave 0, incl. U)", "wait B", "T trsm", "wait A1+A2", "U diag updates (in F)"]):
-            print("   chol %-30s median %8.0f cycles (sum over steps, wave 0)" % (nm, np.median(st[:, 7 + i])))
+            print("   chol %-30s median %8.0f cycles (sum over steps, wave 0)" % (nm, np.median(st[:, 7 + i] & 0xffffffff)))
+        print("   fix-up: own tiles %8.0f, wait at its barrier %8.0f cycles (median, wave 0)" % (np.median(st[:, 10] >> 32), np.median(st[:, 11] >> 32)))
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "ref":         # refinement modes, in-process

@@ -34,7 +34,10 @@ for i, nm in enumerate(names[:5]):
     print("%-38s median %8.0f  p10 %8.0f  p90 %8.0f cycles" % (nm, np.median(col), np.percentile(col, 10), np.percentile(col, 90)))
 print("%-38s median %8.0f cycles" % ("outputs + AUTO refinement trigger", np.median(st[:, 14] - st[:, 6])))
 print("%-16s median %8.0f cycles; real time median %.1f us; clock %.2f GHz" % ("total", np.median(tot), np.median(real) / 1e3, np.median(tot / np.maximum(real, 1))))
-ph = st[:, 7:12]
+ph = st[:, 7:12] & 0xffffffff          # (upper halves of slots 10, 11: the fix-up split below)
 for i, nm in enumerate(["chol: panel wave in-tile factorisation (+ its diag updates)", "chol: wait at barrier B", "chol: TRSM (panel wave: none)", "chol: wait at barriers A1+A2", "chol: next-diagonal update"]):
     print("%-60s median %8.0f cycles (sum over steps, wave 0)" % (nm, np.median(ph[:, i])))
+fx, fw = st[:, 10] >> 32, st[:, 11] >> 32
+print("%-60s median %8.0f  p10 %8.0f  p90 %8.0f cycles (wave 0)" % ("fix-up: panel wave's own tiles", np.median(fx), np.percentile(fx, 10), np.percentile(fx, 90)))
+print("%-60s median %8.0f  p10 %8.0f  p90 %8.0f cycles (wave 0)" % ("fix-up: wait at the barrier behind it", np.median(fw), np.percentile(fw, 10), np.percentile(fw, 90)))
 print("span first entry -> last exit: %.1f us" % ((st[:, 13].max() - st[:, 15].min()) * 10.0 / 1e3))
