@@ -4,6 +4,7 @@
 // device buffer ownership, kernel-instance selection, launch.
 #include "ddmpc_rr3_law.hpp"
 #include "ddmpc_rr3_box.hpp"
+#include "ddmpc_rr3_box_wide.hpp"
 #include "ddmpc_box_law.hpp"
 #include "../../include/ddmpc.h"
 
@@ -196,6 +197,7 @@ struct LastSolve {
   BetaState beta = BetaState::Written;
   bool rescue = false;                     // z / x / flags of the NOMINAL rescue kernel are current
   XState x = XState::Written;
+  int box_cap = RR3_KMAX;                  // Route::RobustPhases: columns of W of the kernel that wrote the per-instance record (its layout)
 };
 
 // What ddmpc_prepare kept; it serves the route it was formed on only (prep_valid).
@@ -251,6 +253,7 @@ struct ddmpc_handle {
   int nA3 = 0;                            // ... first position of the boxed components (slack box, bounded inputs / outputs) in the "boxed last" order
   int nbox3 = 0;                          // ... bounded handles: components of the box table (Rr3Box)
   int large_bounds = 0;                   // DDMPC_OPT_LARGE_BOUNDS: ddmpc_set_input_bounds / ddmpc_set_output_bounds are accepted beyond 271 rows
+  int large_box_cap = RR3_KMAX;           // DDMPC_OPT_LARGE_BOX_CAPACITY: columns of W per instance of a bounded handle (64: rr3_solve_box_kernel)
   DevBuf d_r3bi, d_r3bd;                  // ... [position | output?] and [a | c | lo | hi | 1/d | shlo | shhi | bounds per channel] of that table
   std::vector<int> ti_h;                  // the parameter tables of upload_params on the host (the order and the box table are
   std::vector<double> td_h;               //   rebuilt from them when the bounds change)
@@ -1088,6 +1091,9 @@ static int launch_rr3_factors(ddmpc_handle* h) {
   return DDMPC_OK;
 }
 
+// A bounded handle with DDMPC_OPT_LARGE_BOX_CAPACITY above 64 is served by rr3_solve_box_wide_kernel (ddmpc_rr3_box_wide.hpp).
+static bool rr3_wide(const ddmpc_handle* h) { return h->bounded && h->large_box_cap > RR3_KMAX; }
+
 // The descriptor of the kept factors and of the solve's workspace (sized here).
 static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
   const int r = kq.r, n16 = (r + 15) & ~15, rv = (r + 1) & ~1, VL = (r + 63) & ~63;
@@ -1095,7 +1101,12 @@ static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
   const long long m64G = rr2_m64(n16);
   const int nA = (kq.convex || h->bounded) ? h->nA3 : r, n0 = nA & ~63;
   const int ldw = ((r - n0) + 63) & ~63;
-  const long long wstride = (long long)RR3_KMAX * ldw + (long long)RR3_KMAX * (RR3_KMAX + 1), kstride = 4 + RR3_KMAX + rv + 4;
+  long long wstride = (long long)RR3_KMAX * ldw + (long long)RR3_KMAX * (RR3_KMAX + 1), kstride = 4 + RR3_KMAX + rv + 4;
+  if (rr3_wide(h)) {    // rr3_solve_box_wide_kernel: W with `capacity` columns, then the 64 x 64 tiles of the k x k system
+    const int cap = h->large_box_cap;
+    wstride = (long long)cap * ldw + rr3w_tiles(cap) * 4096;
+    kstride = 4 + cap + rv + 4;
+  }
   int rc;
   if ((rc = h->d_rr2v.ensure(B * (size_t)R3_NV * VL * sizeof(double))) || (rc = h->d_rr2zp.ensure(B * (size_t)RR2_NG * VL * sizeof(double))) ||
       (rc = h->d_rr3w.ensure(B * (size_t)wstride * sizeof(double))) || (rc = h->d_rr3k.ensure(B * (size_t)kstride * sizeof(int))) ||
@@ -1135,6 +1146,21 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
   }
   Rr3Box X{};
   size_t blds = lds;
+  const bool wide = rr3_wide(h);
+  const int cap = wide ? h->large_box_cap : RR3_KMAX;
+  h->last.box_cap = cap;
+  if (wide) {
+    // DDMPC_OPT_LARGE_BOX_CAPACITY above 64: the twin with `capacity` columns of W and the tiled k x k system
+    if (only != nullptr) return fail(DDMPC_ERR_UNSUPPORTED, "a bounded handle has no affine law beyond 271 rows");
+    X.nbox = h->nbox3; X.ip = (const int*)h->d_r3bi.p; X.bd = (const double*)h->d_r3bd.p;
+    blds = lds + (size_t)rr3w_lds_extra(cap) * sizeof(double);
+    if (blds > 64 * 1024) {
+      HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<false>, blds));
+      HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<true>, blds));
+    }
+    hipLaunchKernelGGL(rr3_solve_box_wide_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
+                       (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap);
+  } else
   if (h->bounded) {
     // input / output bounds: the instantiations that test the component table.  No law step filters their instances, and no
     // fall-back kernel knows the bounds (an instance beyond RR3_KMAX active components ends in status 4 inside the kernel).
@@ -1158,7 +1184,10 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     HankelLaunch hk;
     if ((rc = pick_hankel_launch(kq, &hk))) return rc;
     launch_hankel(hk, h->stream, (unsigned)B, H, kq, h->ud, h->yd, (int)R3_X, only_si != nullptr ? 1 : 0);
-    if (h->bounded)
+    if (wide)
+      hipLaunchKernelGGL(rr3_solve_box_wide_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
+                         (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X, cap);
+    else if (h->bounded)
       hipLaunchKernelGGL(rr3_solve_box_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
                          (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X);
     else
@@ -2428,6 +2457,12 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_BOX_SAFEGUARD must be 0 or 1");
       h->box_safeguard = value;           // (which instantiation of the box kernels is launched: nothing prepared depends on it)
       return DDMPC_OK;
+    case DDMPC_OPT_LARGE_BOX_CAPACITY:
+      if (value != 64 && value != 128 && value != 192 && value != 256)
+        return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_CAPACITY must be 64, 128, 192 or 256");
+      h->large_box_cap = value;           // (which bounded phase kernel is launched and how its workspace is sized: the factors do not depend on it)
+      h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
+      return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
       if (value == 1 && !h->gram_valu_ok) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_gram_tiles_kernel stages the whole trajectory in LDS: not at this shape");
@@ -3063,9 +3098,10 @@ int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws
   // what the last solve left, read on the route that served it
   if (h->last.route == Route::RobustPhases && h->d_rr3k.p) {
     // ROBUST on the phase kernels (ddmpc_rr3.hpp): the per-instance record of the last solve --
-    // [k, state, iterations, k, switched positions (RR3_KMAX), active set (rv), start tick, ticks] -- into meta_out
+    // [k, state, iterations, k, switched positions (capacity: RR3_KMAX, or DDMPC_OPT_LARGE_BOX_CAPACITY of the solve that wrote
+    // it), active set (rv), start tick, ticks, peak k] -- into meta_out
     const int rv = (h->kp.r + 1) & ~1;
-    const long long kstride = 4 + RR3_KMAX + rv + 4;
+    const long long kstride = 4 + h->last.box_cap + rv + 4;
     if (meta_avail) *meta_avail = kstride;
     if (ws_avail) *ws_avail = 0;
     if (b < 0 || b >= h->batch) return fail(DDMPC_ERR_INVALID, "instance out of range");

@@ -243,6 +243,8 @@ class DirectDataDrivenMPCController:
                 self._engine.set_output_bounds(*self._output_bounds)
             if getattr(self, "_box_safeguard", False):
                 self._engine.set_box_safeguard(True)
+            if getattr(self, "_large_box_capacity", None) is not None:
+                self._engine.set_large_box_capacity(self._large_box_capacity)
         if not hasattr(self, "problem") or self.problem is None:
             self.problem = _Problem(self)
 
@@ -347,6 +349,17 @@ class DirectDataDrivenMPCController:
         self._box_safeguard = bool(on)
         if self._engine is not None:
             self._engine.set_box_safeguard(self._box_safeguard)
+            self._cold_solved = False
+            self.problem.solve()
+
+    def set_large_box_capacity(self, k: int) -> None:
+        """With bounds on a long horizon (beyond 271 rows): how many boxed components may be active at once, 64 (default), 128,
+        192 or 256 (`BatchedDDMPC.set_large_box_capacity`).  Remembered for a rebuilt engine handle.  The problem is solved
+        again, as after `set_input_bounds`."""
+        if self._engine is not None:
+            self._engine.set_large_box_capacity(k)
+        self._large_box_capacity = int(k)
+        if self._engine is not None:
             self._cold_solved = False
             self.problem.solve()
 

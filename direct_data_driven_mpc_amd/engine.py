@@ -349,7 +349,7 @@ class BatchedDDMPC:
         (`ddmpc_set_input_bounds`): arrays of m entries (a scalar is broadcast), -inf / +inf = no bound on that side; both
         None removes the bounds.  ROBUST controllers up to 1024 rows with scalar / diagonal weights; takes effect at the next
         solve and drops what `prepare` kept and the last solution.  Beyond 271 rows: after `set_large_bounds(True)` only (phase
-        kernels), and at most 64 boxed components
+        kernels), and at most the capacity, 64 by default (`set_large_box_capacity`), of boxed components
         -- slack, input, output -- may be active at once: an instance beyond that reports solver_error with NaN outputs."""
         lo = None if u_min is None else np.ascontiguousarray(np.broadcast_to(np.asarray(u_min, dtype=np.float64), (self.m,)))
         hi = None if u_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(u_max, dtype=np.float64), (self.m,)))
@@ -369,10 +369,17 @@ class BatchedDDMPC:
 
     def set_large_bounds(self, on: bool) -> None:
         """ROBUST controllers beyond 271 rows: True = `set_input_bounds` / `set_output_bounds` are accepted on a handle of
-        272 .. 1024 rows (phase kernels; at most 64 boxed components active at once, an instance beyond that reports
+        272 .. 1024 rows (phase kernels; at most the capacity, 64 by default, of boxed components active at once, an instance beyond that reports
         solver_error with NaN outputs), False (default) = both refuse finite bounds at that size (DDMPC_OPT_LARGE_BOUNDS).
         No effect up to 271 rows."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_BOUNDS, 1 if on else 0))
+
+    def set_large_box_capacity(self, k: int) -> None:
+        """Bounded handles beyond 271 rows: how many boxed components -- slack, input, output -- may be active at once in an
+        iteration (DDMPC_OPT_LARGE_BOX_CAPACITY): 64 (default), 128, 192 or 256; any other value raises.  Costs ldw x k doubles of
+        W per instance (ldw: the rows of the trailing block, rounded up to 64) and up to ten 32 KB tiles.  A kept `prepare` stays
+        valid; the last solution is forgotten until the next solve.  No effect up to 271 rows or without finite bounds."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_BOX_CAPACITY, int(k)))
 
     def set_box_safeguard(self, on: bool) -> None:
         """Input / output bounds: True = an instance whose active-set iteration reaches `max_iter` without a stable set is finished by a

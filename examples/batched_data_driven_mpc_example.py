@@ -50,6 +50,8 @@ def parse_args():
     ap.add_argument("--y_max", type=float, nargs="+", default=None, help="upper output bounds; give both or neither")
     ap.add_argument("--box_safeguard", action="store_true",
                     help="with input bounds: finish solves on which the active-set iteration cycles by a primal active-set method")
+    ap.add_argument("--large_box_capacity", type=int, choices=[64, 128, 192, 256], default=None,
+                    help="with bounds beyond 271 rows: how many boxed components may be active at once (default 64)")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     return ap.parse_args()
 
@@ -100,6 +102,8 @@ def main():
         eng.set_output_bounds(a.y_min if len(a.y_min) > 1 else a.y_min[0], a.y_max if len(a.y_max) > 1 else a.y_max[0])
     if a.box_safeguard:
         eng.set_box_safeguard(True)
+    if a.large_box_capacity is not None:
+        eng.set_large_box_capacity(a.large_box_capacity)
     eng.set_data(data["u_d"], data["y_d"])
     up = data["u_d"][:, -n:, :].reshape(B, -1)                                   # controller.py:184-185
     yp = data["y_d"][:, -n:, :].reshape(B, -1)

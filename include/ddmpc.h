@@ -177,12 +177,26 @@ extern "C" {
                                          this route */
 #define DDMPC_OPT_LARGE_BOUNDS 12       /* ROBUST controllers beyond 271 rows: 1 = ddmpc_set_input_bounds / ddmpc_set_output_bounds are accepted
                                          on a handle of 272 .. 1024 rows that the phase kernels serve ("Bounds beyond 271 rows" at
-                                         ddmpc_set_input_bounds: at most 64 components active at once).  0 (default) = both calls
+                                         ddmpc_set_input_bounds: at most the capacity, 64 by default, of components active at once;
+                                         DDMPC_OPT_LARGE_BOX_CAPACITY).  0 (default) = both calls
                                          refuse finite bounds beyond 271 rows with DDMPC_ERR_UNSUPPORTED, as they did before the
                                          option existed; the message names the option.  Opt-in because the limits of that route
-                                         (the 64-component cap, no safeguard) are not those of the register-resident one.  Accepted
+                                         (the capacity, no safeguard) are not those of the register-resident one.  Accepted
                                          on any handle, no effect up to 271 rows; 0 on a bounded handle beyond 271 rows is
                                          DDMPC_ERR_UNSUPPORTED (remove the bounds first).  Values other than 0 / 1: DDMPC_ERR_INVALID */
+#define DDMPC_OPT_LARGE_BOX_CAPACITY 13 /* bounded handles beyond 271 rows (DDMPC_OPT_LARGE_BOUNDS): the number of components (slack + input +
+                                         output) that may be active at once in an iteration = the columns of W kept per instance:
+                                         64 (default), 128, 192 or 256; any other value is DDMPC_ERR_INVALID.  64 launches
+                                         rr3_solve_box_kernel as before the option existed; above 64 rr3_solve_box_wide_kernel
+                                         (the same factor, update, iteration rule and refinement pass; the k x k system as 64 x 64
+                                         tiles with a blocked Cholesky) serves ddmpc_solve, ddmpc_step, the per-step
+                                         ddmpc_closed_loop and ddmpc_get_solution.  Memory per instance: W, ldw x capacity doubles
+                                         (ldw = the rows of the trailing block rounded up to 64: 1.3 MB at 608 rows with every input
+                                         channel bounded and capacity 256, 0.67 GB at 512 instances), and up to 10 tiles of 32 KB; an
+                                         allocation failure is DDMPC_ERR_HIP at the next solve.  Accepted on any handle; no effect up
+                                         to 271 rows or without finite bounds.  Keeps what ddmpc_prepare kept (the factors do not
+                                         depend on it) and forgets the last solution: ddmpc_get_solution is DDMPC_ERR_NOT_READY
+                                         until the next solve, as after ddmpc_set_input_bounds */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -344,8 +358,9 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
  * here).  Same iteration rule, max_iter cap and status 4 at the cap; an active input or output equals its bound exactly.
  * Served by ddmpc_solve, ddmpc_prepare (the factors only) + ddmpc_step (bit-equal to ddmpc_solve), the per-step
  * ddmpc_closed_loop ("ddmpc_plant_kernel": there is no fused loop at this size) and ddmpc_get_solution.
- *   LIMIT: at most 64 components (slack + input + output) may be active at once in any iteration.  No fall-back kernel knows the
- *     bounds: an instance that exceeds 64, or whose k x k pivot is not positive, reports DDMPC_STATUS_SOLVER_ERROR with `iters`
+ *   LIMIT: at most the capacity, 64 by default (DDMPC_OPT_LARGE_BOX_CAPACITY: 128, 192 or 256), of components (slack + input +
+ *     output) may be active at once in any iteration; W takes ldw x capacity doubles per instance (see the option).  No fall-back
+ *     kernel knows the bounds: an instance that exceeds the capacity, or whose k x k pivot is not positive, reports DDMPC_STATUS_SOLVER_ERROR with `iters`
  *     the iteration at which it happened and NaN in u_opt / cost; the other instances of the batch are not affected.
  *   DDMPC_ERR_UNSUPPORTED, each with a message that names the reason: DDMPC_OPT_LARGE_BOUNDS = 0; more than 1024 rows; a handle that is not on the phase
  *     kernels (DDMPC_OPT_LARGE_PIPELINE = DDMPC_PIPELINE_ONE_WORKGROUP, ddmpc_debug_stamps enabled, batch > 65535);
@@ -370,8 +385,8 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
  *     a free prediction step; with the CONVEX slack box a Q entry of 0 on any.  Up to 271 rows also: DDMPC_REFINE_ALWAYS (refused
  *     by ddmpc_set_option too once bounds are set); n(m+p) > 256; a box list of more than 288 components (slack + bounded
  *     inputs + bounded outputs; the count is named, also by ddmpc_prepare when input bounds set later make the list too long).
- *     Beyond 271 rows: "Bounds beyond 271 rows" at ddmpc_set_input_bounds -- 272 .. 1024 rows on the phase kernels, at most 64
- *     components active at once.  ddmpc_solve_from_host on such a handle is DDMPC_ERR_UNSUPPORTED.
+ *     Beyond 271 rows: "Bounds beyond 271 rows" at ddmpc_set_input_bounds -- 272 .. 1024 rows on the phase kernels, at most the
+ *     capacity, 64 by default, of components active at once (DDMPC_OPT_LARGE_BOX_CAPACITY; W: ldw x capacity doubles per instance).  ddmpc_solve_from_host on such a handle is DDMPC_ERR_UNSUPPORTED.
  * How it is served: as an input-bounded handle (above), by ddmpc_solve, ddmpc_step, ddmpc_closed_loop (fused and per step),
  * ddmpc_get_solution and DDMPC_OPT_BOX_SAFEGUARD.  The output is a third kind of boxed component: hat = y_s - lam beta / q,
  * d = lam / q.  A predicted output row carries ybar and sigma, so a CONVEX handle has two components on such a row and both
