@@ -5,6 +5,7 @@
 #include "ddmpc_rr3_law.hpp"
 #include "ddmpc_rr3_box.hpp"
 #include "ddmpc_rr3_box_wide.hpp"
+#include "ddmpc_rr3_box_safe.hpp"
 #include "ddmpc_box_law.hpp"
 #include "../../include/ddmpc.h"
 
@@ -254,6 +255,7 @@ struct ddmpc_handle {
   int nbox3 = 0;                          // ... bounded handles: components of the box table (Rr3Box)
   int large_bounds = 0;                   // DDMPC_OPT_LARGE_BOUNDS: ddmpc_set_input_bounds / ddmpc_set_output_bounds are accepted beyond 271 rows
   int large_box_cap = RR3_KMAX;           // DDMPC_OPT_LARGE_BOX_CAPACITY: columns of W per instance of a bounded handle (64: rr3_solve_box_kernel)
+  int large_box_safeguard = 0;            // DDMPC_OPT_LARGE_BOX_SAFEGUARD: rr3_box_safeguard_kernel behind the solve launch of the wide kernels
   DevBuf d_r3bi, d_r3bd;                  // ... [position | output?] and [a | c | lo | hi | 1/d | shlo | shhi | bounds per channel] of that table
   std::vector<int> ti_h;                  // the parameter tables of upload_params on the host (the order and the box table are
   std::vector<double> td_h;               //   rebuilt from them when the bounds change)
@@ -1091,8 +1093,9 @@ static int launch_rr3_factors(ddmpc_handle* h) {
   return DDMPC_OK;
 }
 
-// A bounded handle with DDMPC_OPT_LARGE_BOX_CAPACITY above 64 is served by rr3_solve_box_wide_kernel (ddmpc_rr3_box_wide.hpp).
-static bool rr3_wide(const ddmpc_handle* h) { return h->bounded && h->large_box_cap > RR3_KMAX; }
+// A bounded handle with DDMPC_OPT_LARGE_BOX_CAPACITY above 64 is served by rr3_solve_box_wide_kernel (ddmpc_rr3_box_wide.hpp), and
+// so is one with DDMPC_OPT_LARGE_BOX_SAFEGUARD at every capacity (64 included: the safeguard writes one layout of W, tiles and record).
+static bool rr3_wide(const ddmpc_handle* h) { return h->bounded && (h->large_box_cap > RR3_KMAX || h->large_box_safeguard != 0); }
 
 // The descriptor of the kept factors and of the solve's workspace (sized here).
 static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
@@ -1105,6 +1108,7 @@ static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
   if (rr3_wide(h)) {    // rr3_solve_box_wide_kernel: W with `capacity` columns, then the 64 x 64 tiles of the k x k system
     const int cap = h->large_box_cap;
     wstride = (long long)cap * ldw + rr3w_tiles(cap) * 4096;
+    if (h->large_box_safeguard) wstride += rr3s_extra(cap, h->nbox3, ldw);   // rr3_box_safeguard_kernel: the unfactored tiles, v, the entering column
     kstride = 4 + cap + rv + 4;
   }
   int rc;
@@ -1160,6 +1164,13 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     }
     hipLaunchKernelGGL(rr3_solve_box_wide_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
                        (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap);
+    if (h->large_box_safeguard) {
+      // DDMPC_OPT_LARGE_BOX_SAFEGUARD: the instances that reached max_iter are solved again by the primal method, before the
+      // Hankel products and the refinement launch; every other workgroup leaves at once
+      if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)rr3_box_safeguard_kernel, blds));
+      hipLaunchKernelGGL(rr3_box_safeguard_kernel, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
+                         (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap);
+    }
   } else
   if (h->bounded) {
     // input / output bounds: the instantiations that test the component table.  No law step filters their instances, and no
@@ -2461,6 +2472,11 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value != 64 && value != 128 && value != 192 && value != 256)
         return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_CAPACITY must be 64, 128, 192 or 256");
       h->large_box_cap = value;           // (which bounded phase kernel is launched and how its workspace is sized: the factors do not depend on it)
+      h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
+      return DDMPC_OK;
+    case DDMPC_OPT_LARGE_BOX_SAFEGUARD:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_SAFEGUARD must be 0 or 1");
+      h->large_box_safeguard = value;     // (which kernels serve a bounded handle beyond 271 rows and how their workspace is sized: the factors do not depend on it)
       h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
       return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:

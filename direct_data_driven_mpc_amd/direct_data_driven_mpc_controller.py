@@ -245,6 +245,8 @@ class DirectDataDrivenMPCController:
                 self._engine.set_box_safeguard(True)
             if getattr(self, "_large_box_capacity", None) is not None:
                 self._engine.set_large_box_capacity(self._large_box_capacity)
+            if getattr(self, "_large_box_safeguard", False):
+                self._engine.set_large_box_safeguard(True)
         if not hasattr(self, "problem") or self.problem is None:
             self.problem = _Problem(self)
 
@@ -359,6 +361,17 @@ class DirectDataDrivenMPCController:
         if self._engine is not None:
             self._engine.set_large_box_capacity(k)
         self._large_box_capacity = int(k)
+        if self._engine is not None:
+            self._cold_solved = False
+            self.problem.solve()
+
+    def set_large_box_safeguard(self, on: bool) -> None:
+        """With bounds on a long horizon (beyond 271 rows): finish a solve whose active-set iteration ends at the cap by the primal
+        active-set method (`BatchedDDMPC.set_large_box_safeguard`).  Remembered for a rebuilt engine handle.  The problem is
+        solved again, as after `set_input_bounds`."""
+        if self._engine is not None:
+            self._engine.set_large_box_safeguard(bool(on))
+        self._large_box_safeguard = bool(on)
         if self._engine is not None:
             self._cold_solved = False
             self.problem.solve()

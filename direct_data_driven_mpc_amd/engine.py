@@ -381,6 +381,14 @@ class BatchedDDMPC:
         valid; the last solution is forgotten until the next solve.  No effect up to 271 rows or without finite bounds."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_BOX_CAPACITY, int(k)))
 
+    def set_large_box_safeguard(self, on: bool) -> None:
+        """Bounded handles beyond 271 rows: True = an instance whose active-set iteration reaches `max_iter` without a stable set is
+        solved again inside the same solve / step by the primal active-set method (DDMPC_OPT_LARGE_BOX_SAFEGUARD; `iters` =
+        max_iter + its solves; its working sets must fit the capacity, `set_large_box_capacity`), False (default) = solver_error at
+        the cap.  With True the wide kernels serve the handle at every capacity.  A kept `prepare` stays valid; the last solution is
+        forgotten until the next solve.  No effect up to 271 rows or without finite bounds."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_BOX_SAFEGUARD, 1 if on else 0))
+
     def set_box_safeguard(self, on: bool) -> None:
         """Input / output bounds: True = an instance whose active-set iteration reaches `max_iter` without a stable set is finished by a
         primal active-set method instead of reporting solver_error (DDMPC_OPT_BOX_SAFEGUARD; `iters` = max_iter + its solves),

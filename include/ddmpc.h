@@ -197,6 +197,24 @@ extern "C" {
                                          to 271 rows or without finite bounds.  Keeps what ddmpc_prepare kept (the factors do not
                                          depend on it) and forgets the last solution: ddmpc_get_solution is DDMPC_ERR_NOT_READY
                                          until the next solve, as after ddmpc_set_input_bounds */
+#define DDMPC_OPT_LARGE_BOX_SAFEGUARD 14 /* bounded handles beyond 271 rows (DDMPC_OPT_LARGE_BOUNDS): 1 = an instance whose primal-dual
+                                         iteration reaches max_iter without a stable set is solved again inside the same ddmpc_solve /
+                                         ddmpc_step call by the primal active-set method of DDMPC_OPT_BOX_SAFEGUARD, stated on the
+                                         reduced system of this route (rr3_box_safeguard_kernel): from the empty
+                                         set's solution, so the result does not depend on max_iter; one component joins or leaves
+                                         the working set per solve; `iters` = max_iter + its solves.  An instance that failed on a
+                                         pivot or outgrew the capacity is not solved again.  Status 4 with NaN in u_opt / cost and
+                                         `iters` = max_iter + the number (from 1) of the solve that could not be made: more than
+                                         4 nbox + 16 solves, a non-positive pivot of the k x k system, a working set larger than
+                                         DDMPC_OPT_LARGE_BOX_CAPACITY (the set of the first solve holds every component the empty
+                                         set's solution violates).  With 1 the wide kernels serve the handle at every capacity: above
+                                         64 an instance that converges below max_iter is bit-equal to 0 in inputs, cost, status and
+                                         iters; at capacity 64 it agrees to rounding only (4e-15 measured: the wide kernel forms the
+                                         right-hand side of the k x k system differently).  Memory per instance on top of the
+                                         capacity's: a second set of tiles, nbox + 16 ldw doubles.  0 (default) = status 4 at the cap.
+                                         Values other than 0 / 1: DDMPC_ERR_INVALID.  Accepted on any handle; no effect up to 271
+                                         rows, without finite bounds or off the phase kernels; keeps what ddmpc_prepare kept and
+                                         forgets the last solution.  A slack-only CONVEX handle is not covered */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -367,7 +385,9 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
  *     DDMPC_OPT_LARGE_AFFINE_LAW = 1.  In the reverse order the same three are refused on a bounded handle:
  *     ddmpc_set_option(DDMPC_OPT_LARGE_PIPELINE, DDMPC_PIPELINE_ONE_WORKGROUP), ddmpc_set_option(DDMPC_OPT_LARGE_AFFINE_LAW, 1)
  *     and ddmpc_debug_stamps(enable).  NOMINAL, DDMPC_WEIGHT_DENSE and zero weights as above.
- *   DDMPC_OPT_BOX_SAFEGUARD is accepted and has no effect beyond 271 rows; the box list has no length limit there. */
+ *   DDMPC_OPT_BOX_SAFEGUARD is accepted and has no effect beyond 271 rows; the safeguard of this size is an option of its own,
+ *     DDMPC_OPT_LARGE_BOX_SAFEGUARD = 1: an instance at the max_iter cap is solved again by the primal active-set method
+ *     (`iters` = max_iter + its solves, working sets up to the capacity; see the option).  The box list has no length limit there. */
 int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max);
 
 /* Box on the predicted outputs: y_min[ch] <= ybar[k][ch] <= y_max[ch] on every FREE prediction step (the rows that carry Q;
