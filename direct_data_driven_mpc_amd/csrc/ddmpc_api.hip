@@ -199,6 +199,7 @@ struct LastSolve {
   bool rescue = false;                     // z / x / flags of the NOMINAL rescue kernel are current
   XState x = XState::Written;
   int box_cap = RR3_KMAX;                  // Route::RobustPhases: columns of W of the kernel that wrote the per-instance record (its layout)
+  bool box_seed = false;                   // Route::BoxLaw, DDMPC_OPT_BOX_WARM_START: d_box_seed holds the signed set that solve ended with
 };
 
 // What ddmpc_prepare kept; it serves the route it was formed on only (prep_valid).
@@ -281,6 +282,8 @@ struct ddmpc_handle {
   int convex_warm = 0;                     // DDMPC_OPT_CONVEX_WARM_LAW: warm steps under the slack box run the active-set iteration on the law
   DevBuf d_mcol, d_cwl_tab, d_cwl_sg, d_cwl_ref;   // ... M = K0^-1 E_box [batch][nbox][r]; [box_rho | box_of]; k x k scratch; refined-law flags (+ count)
   int box_safeguard = 0;                   // DDMPC_OPT_BOX_SAFEGUARD: Route::BoxLaw instances at the max_iter cap are finished by box_safeguard
+  int box_warm = 0;                        // DDMPC_OPT_BOX_WARM_START: Route::BoxLaw steps start their iteration from the last solve's set
+  DevBuf d_box_seed;                       // ... that set, [batch][nbox] (written by the WARM instantiations of the box kernels)
   // input bounds (ddmpc_set_input_bounds) and output bounds (ddmpc_set_output_bounds): per channel, +-infinity = none; the
   // vectors are empty without a finite bound of their kind; `bounded` = some bound of either kind is finite (Route::BoxLaw)
   std::vector<double> umin_h, umax_h, ymin_h, ymax_h;
@@ -322,6 +325,13 @@ static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; }
 // A call that writes solve outputs starts the record afresh (nothing of an earlier call survives) and makes it readable at its end.
 static Route begin_solve(ddmpc_handle* h, Route route) { h->last = LastSolve{}; h->last.route = route; return route; }
 static void end_solve(ddmpc_handle* h, const double* up, const double* yp) { h->last.up = up; h->last.yp = yp; h->last.valid = true; }
+
+// DDMPC_OPT_BOX_WARM_START: the last solve of the handle left a seed the next step on Route::BoxLaw may read.  It lives with the
+// record of that solve: whatever makes the record unreadable (new data, setpoints, bounds, a new ddmpc_prepare) drops the seed,
+// so a seed indexed by another box table is never read.  Asked before begin_solve starts the next record.
+static bool box_seed_valid(const ddmpc_handle* h) {
+  return h->box_warm && h->last.valid && h->last.route == Route::BoxLaw && h->last.box_seed;
+}
 
 // A parameter table of upload_params (d_tabi: 3 rows, d_tabd: 4 rows of 16 NT entries) read back to the host.  The blocking copy
 // is also a synchronisation point: ddmpc_prepare without input bounds has no other one before it overwrites d_cwl_tab.
@@ -889,7 +899,8 @@ int ddmpc_destroy(ddmpc_handle* h) {
                     &h->d_pl, &h->d_x, &h->d_w, &h->d_usys, &h->d_ysys, &h->d_stacc,
                     &h->d_lfac, &h->d_lfacT, &h->d_gain, &h->d_prep_status, &h->d_zero, &h->d_dmat, &h->d_need, &h->d_io, &h->d_rr, &h->d_alpha, &h->d_zws, &h->d_resc, &h->d_xws, &h->d_rflag, &h->d_rrmeta, &h->d_gpre, &h->d_perm, &h->d_rr2d, &h->d_rr2res, &h->d_rr2mt, &h->d_rr2v, &h->d_rr2zp, &h->d_rr2sc, &h->d_wz, &h->d_gz, &h->d_gres, &h->d_zvirt, &h->d_rr3w, &h->d_rr3k, &h->d_rr_fb, &h->d_rrmeta_fb, &h->d_rr2cand, &h->d_rr2tol, &h->d_rr2rank, &h->d_wd, &h->d_rr2y,
                     &h->d_mcol, &h->d_cwl_tab, &h->d_cwl_sg, &h->d_cwl_ref, &h->d_r3y, &h->d_r3res, &h->d_r3zp, &h->d_r3flag,
-                    &h->d_box_bd, &h->d_ubnd, &h->d_ybnd, &h->d_r3bi, &h->d_r3bd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp};
+                    &h->d_box_bd, &h->d_ubnd, &h->d_ybnd, &h->d_r3bi, &h->d_r3bd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp,
+                    &h->d_box_seed};
   for (DevBuf* b : bufs) b->release();
   h->h_io.release();
   h->h_flag.release();
@@ -1532,21 +1543,40 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
 }
 
 // Route::BoxLaw (input bounds): a control step on what ddmpc_prepare kept -- the law, M for the whole box list and the table.
+// seeded (DDMPC_OPT_BOX_WARM_START = 1 only): the iteration starts from the set in d_box_seed; with the option 1 every launch
+// leaves its set there.
 static int launch_box_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
-                           int32_t* iters) {
+                           int32_t* iters, bool seeded) {
   if (int rc = reserve_beta(h)) return rc;
+  const bool warm = h->box_warm != 0;
+  if (warm)
+    if (int rc = h->d_box_seed.ensure((size_t)h->batch * (size_t)std::max(h->prep.cwl_nbox, 1))) return rc;
   // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard: its registers and LDS are the kernel's own)
   // (output bounds: the instantiations with the output components, block = max(r, nbox) rounded up to 64)
   const bool yb = !h->ymin_h.empty();
-  auto kernel = yb ? (h->box_safeguard ? ddmpc_box_step_kernel<true, true> : ddmpc_box_step_kernel<false, true>)
-                   : (h->box_safeguard ? ddmpc_box_step_kernel<true, false> : ddmpc_box_step_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch),
-                     dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0, h->stream, h->kp,
-                     16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo,
-                     cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox,
-                     (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
-                     h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr);
+  // (DDMPC_OPT_BOX_WARM_START = 0 launches the instantiations without the seed argument: the kernels as they were)
+  auto launch = [&](auto kernel, auto... seed) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch),
+                       dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0, h->stream, h->kp,
+                       16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo,
+                       cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox,
+                       (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                       h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, seed...);
+  };
+  if (warm) {
+    const BoxSeed seed{(signed char*)h->d_box_seed.p, seeded ? 1 : 0};
+    if (yb && h->box_safeguard) launch(ddmpc_box_step_kernel<true, true, BoxSeed>, seed);
+    else if (yb) launch(ddmpc_box_step_kernel<false, true, BoxSeed>, seed);
+    else if (h->box_safeguard) launch(ddmpc_box_step_kernel<true, false, BoxSeed>, seed);
+    else launch(ddmpc_box_step_kernel<false, false, BoxSeed>, seed);
+  } else {
+    if (yb && h->box_safeguard) launch(ddmpc_box_step_kernel<true, true>);
+    else if (yb) launch(ddmpc_box_step_kernel<false, true>);
+    else if (h->box_safeguard) launch(ddmpc_box_step_kernel<true, false>);
+    else launch(ddmpc_box_step_kernel<false, false>);
+  }
   HIP_TRY(hipGetLastError());
+  h->last.box_seed = warm;
   return DDMPC_OK;
 }
 
@@ -1565,7 +1595,7 @@ static int solve_box(ddmpc_handle* h, const double* up, const double* yp, double
   int rc = ddmpc_prepare(h);
   if (!rc) {
     begin_solve(h, Route::BoxLaw);
-    rc = launch_box_step(h, up, yp, uo, cost, status, iters);
+    rc = launch_box_step(h, up, yp, uo, cost, status, iters, false);   // (cold contract: from the empty set; it leaves a seed)
   }
   swap_bufs();
   h->prep = kept;
@@ -1920,8 +1950,9 @@ static int solve_on_route(ddmpc_handle* h, const double* up, const double* yp, d
 // A control step on what ddmpc_prepare kept (ddmpc_step, the per-step closed loop): the callers have prepared on this route.
 static int step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                          int32_t* iters) {
+  const bool seeded = box_seed_valid(h);
   const Route route = begin_solve(h, select_route(h));
-  if (route == Route::BoxLaw) return launch_box_step(h, up, yp, uo, cost, status, iters);
+  if (route == Route::BoxLaw) return launch_box_step(h, up, yp, uo, cost, status, iters, seeded);
   if (route == Route::RobustPhases || route == Route::RobustOneWg)
     return launch_large_robust(h, route, Stage::OnFactors, up, yp, uo, cost, status, iters);
   if (route != Route::Cold) return launch_large_nominal_warm(h, route, up, yp, uo, cost, status, iters);
@@ -2468,6 +2499,11 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_BOX_SAFEGUARD must be 0 or 1");
       h->box_safeguard = value;           // (which instantiation of the box kernels is launched: nothing prepared depends on it)
       return DDMPC_OK;
+    case DDMPC_OPT_BOX_WARM_START:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_BOX_WARM_START must be 0 or 1");
+      h->box_warm = value;                // (which instantiation of the box kernels is launched: nothing prepared depends on it)
+      h->last.box_seed = false;           // (setting it, to either value, drops the seed: the next step starts from the empty set)
+      return DDMPC_OK;
     case DDMPC_OPT_LARGE_BOX_CAPACITY:
       if (value != 64 && value != 128 && value != 192 && value != 256)
         return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_CAPACITY must be 64, 128, 192 or 256");
@@ -2893,6 +2929,10 @@ static int select_loop_path(ddmpc_handle* h, int n_mpc_step, LoopPath* path) {
 static int launch_fused_loop(ddmpc_handle* h, LoopPath path, LoopArgs a) {
   if (int rc = reserve_beta(h)) return rc;
   a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p;
+  const bool warm = path == LoopPath::FusedBox && h->box_warm != 0;       // DDMPC_OPT_BOX_WARM_START, as launch_box_step
+  const int seeded = (warm && box_seed_valid(h)) ? 1 : 0;
+  if (warm)
+    if (int rc = h->d_box_seed.ensure((size_t)h->batch * (size_t)std::max(h->prep.cwl_nbox, 1))) return rc;
   begin_solve(h, path == LoopPath::FusedBox ? Route::BoxLaw : Route::Cold);
   const bool yb = path == LoopPath::FusedBox && !h->ymin_h.empty();
   const unsigned threads = yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r);
@@ -2912,10 +2952,25 @@ static int launch_fused_loop(ddmpc_handle* h, LoopPath path, LoopArgs a) {
   } else {    // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard, as launch_box_step)
     const double* bd = (const double*)h->d_box_bd.p;
     const int* ref = h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr;
-    if (yb && h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true, true>, nbox, tab, bd, mcol, sg, ref);
-    else if (yb) launch(ddmpc_closed_loop_box_kernel<false, true>, nbox, tab, bd, mcol, sg, ref);
-    else if (h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true, false>, nbox, tab, bd, mcol, sg, ref);
-    else launch(ddmpc_closed_loop_box_kernel<false, false>, nbox, tab, bd, mcol, sg, ref);
+    if (warm) {                            // (the seed follows the window of the last solve)
+      const BoxSeed seed{(signed char*)h->d_box_seed.p, seeded};
+      auto launch_warm = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(threads), 0, h->stream, h->kp, 16 * h->kc.NT,
+                           h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps,
+                           a.n_mpc_step, a.x, a.up, a.yp, a.w, a.usys, a.ysys, a.stacc, a.beta, a.act, nbox, tab, bd, mcol, sg, ref,
+                           a.lwup, a.lwyp, seed);
+      };
+      if (yb && h->box_safeguard) launch_warm(ddmpc_closed_loop_box_kernel<true, true, BoxSeed>);
+      else if (yb) launch_warm(ddmpc_closed_loop_box_kernel<false, true, BoxSeed>);
+      else if (h->box_safeguard) launch_warm(ddmpc_closed_loop_box_kernel<true, false, BoxSeed>);
+      else launch_warm(ddmpc_closed_loop_box_kernel<false, false, BoxSeed>);
+    } else {
+      if (yb && h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true, true>, nbox, tab, bd, mcol, sg, ref);
+      else if (yb) launch(ddmpc_closed_loop_box_kernel<false, true>, nbox, tab, bd, mcol, sg, ref);
+      else if (h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true, false>, nbox, tab, bd, mcol, sg, ref);
+      else launch(ddmpc_closed_loop_box_kernel<false, false>, nbox, tab, bd, mcol, sg, ref);
+    }
+    h->last.box_seed = warm;
   }
   HIP_TRY(hipGetLastError());
   return DDMPC_OK;

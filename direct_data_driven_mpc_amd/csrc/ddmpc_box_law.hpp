@@ -370,6 +370,61 @@ __device__ int box_safeguard(const KParams& P, const BoxTabT<YB>& T, const doubl
   return st;
 }
 
+// DDMPC_OPT_BOX_WARM_START: the iteration from the signed set the last solve of the handle ended with, in the
+// WARM instantiations of the box kernels only.  Called like box_iterate, after the law violated the box under the empty set,
+// with the seed in s.act (settled by a barrier).  An empty seed: box_iterate as it is.  Otherwise the seed is solved for --
+// solve number 2 -- and the test / solve loop of box_iterate goes on from there under the same cap (box_solve_set is that
+// loop's body; BoxTab::test releases an active component whose multiplier has the wrong sign).  A seeded run that meets a
+// non-positive pivot (K(A) is positive definite for every set, so that is the seed's doing) or ends at the cap starts again
+// from the empty set with a fresh cap: box_iterate as it is, so the status is never worse than without the seed.  With SAFE a
+// seeded run at the cap returns 4 with s.fail = 0 instead, and the caller goes to box_safeguard (which starts from the empty
+// set's law: its result does not depend on the seed).  *iters = every solve made, the law counted once.
+template <bool SAFE, bool YB>
+__device__ int box_iterate_seeded(const KParams& P, const BoxTabT<YB>& T, const double* __restrict__ Mb, double* __restrict__ Sg,
+                                  const double* b0, CwlLds& s, int* iters) {
+  const int tid = threadIdx.x, nthr = blockDim.x, nbox = T.nbox;
+  int any = 0;
+  for (int j = tid; j < nbox; j += nthr) any |= s.act[j] != 0;
+  int spent = 0;                                                      // solves of a seeded run that is given up
+  if (__syncthreads_or(any)) {
+    for (int j = tid; j < nbox; j += nthr) { s.bc[j] = b0[T.rho[j]]; s.slot[j] = -1; }
+    if (tid == 0) { s.kfin = 0; s.fail = 0; s.nslots = 0; }
+    __syncthreads();
+    int iter = 1;
+    bool done = false;
+    for (;;) {
+      if (iter >= P.max_iter) break;                                  // the cap
+      ++iter;
+      if (box_solve_set<YB>(P, T, Mb, Sg, b0, s)) break;              // a pivot
+      if (tid == 0) s.changed = 0;
+      __syncthreads();
+      for (int j = tid; j < nbox; j += nthr) {
+        const int ns = T.test(j, s.bc[j], s.act[j]);
+        if (ns != s.act[j]) { s.act[j] = (signed char)ns; s.changed = 1; }
+      }
+      __syncthreads();
+      if (!s.changed) { done = true; break; }
+    }
+    if (done) { *iters = iter; return 0; }
+    if (SAFE && !s.fail) { *iters = iter; return 4; }
+    spent = iter - 1;
+    __syncthreads();                                                  // (everyone has read what the seeded run left)
+  }
+  int it;
+  const int st = box_iterate<YB>(P, T, Mb, Sg, b0, s, &it);
+  *iters = spent + it;
+  return st;
+}
+
+// The seed as a kernel argument.  The box kernels take it as a parameter pack: empty in the instantiations launched with the
+// option 0, whose signature, kernel arguments and code are then those of the kernels without the option; one BoxSeed in the WARM ones.
+struct BoxSeed {
+  signed char* ws;            // [batch][nbox]: the signed set every instance's last solve ended with; written by every WARM launch
+  int use;                    // 0: `ws` is not read (nothing valid in it) and every instance starts from the empty set
+};
+__device__ __forceinline__ BoxSeed box_seed_of() { return BoxSeed{nullptr, 0}; }
+__device__ __forceinline__ BoxSeed box_seed_of(BoxSeed s) { return s; }
+
 // Output stage of one component with its active flag (j: its place in the box list, or -1): cwl_component, and an input row
 // held at a bound is that bound exactly (t = bound, D1 = 0); its cost term is the K_UFREE one.
 __device__ __forceinline__ double box_component(const KParams& P, int RPs, const BoxTab& T, int rho, int j, double beta, int sa,
@@ -418,14 +473,19 @@ __device__ __forceinline__ double box_component_y(const KParams& P, int RPs, con
 // its solves.  The host launches <false> when the option is 0: that instantiation is the kernel as it was.
 // YB (ddmpc_set_output_bounds): the table with the output components; block = max(r, nbox) rounded up to 64; the active-set
 // workspace holds sa + 4 say per row (sa: slack or input, say: output).  Without YB the kernel is the one it was.
-template <bool SAFE, bool YB>
+// Seed = BoxSeed (DDMPC_OPT_BOX_WARM_START = 1, "WARM"): box_iterate_seeded from the set in seed.ws when seed.use, and the set this
+// solve ended with goes there (empty when nothing was iterated or the solve failed).  The host launches the empty pack when the
+// option is 0: that instantiation is the kernel as it was.
+template <bool SAFE, bool YB, class... Seed>
 __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                       const int* __restrict__ prep_status, const double* __restrict__ u_past,
                                       const double* __restrict__ y_past, double* __restrict__ u_opt, double* __restrict__ cost,
                                       int* __restrict__ status, int* __restrict__ iters, double* __restrict__ beta_ws,
                                       signed char* __restrict__ act_ws, int nbox, const int* __restrict__ tab,
                                       const double* __restrict__ bd, const double* __restrict__ Mcol, double* __restrict__ sg,
-                                      const int* __restrict__ refined) {
+                                      const int* __restrict__ refined, Seed... seed_arg) {
+  constexpr bool WARM = sizeof...(Seed) != 0;
+  [[maybe_unused]] const BoxSeed seed = box_seed_of(seed_arg...);
   __shared__ double pv[WARM_MAX_NF];
   __shared__ double red[32];
   __shared__ double bsh[WARM_MAX_R];
@@ -469,7 +529,14 @@ __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* 
   const bool iterate = viol && st <= 1;               // (a failed factorisation: nothing to iterate on)
   if (iterate) {
     double* Sg = sg + b * (long long)(nbox * (nbox + 1) / 2);
-    int dst = box_iterate<YB>(P, T, Mb, Sg, bsh, s, &it);
+    int dst;
+    if constexpr (WARM) {
+      for (int j = tid; j < nbox; j += blockDim.x) s.act[j] = seed.use ? seed.ws[b * nbox + j] : (signed char)0;
+      __syncthreads();
+      dst = box_iterate_seeded<SAFE, YB>(P, T, Mb, Sg, bsh, s, &it);
+    } else {
+      dst = box_iterate<YB>(P, T, Mb, Sg, bsh, s, &it);
+    }
     if constexpr (SAFE) {
       __shared__ BoxSafeLds q;
       if (dst == 4 && !s.fail) {                      // at the cap (not a pivot)
@@ -519,14 +586,21 @@ __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* 
     status[b] = st;
     if (iters) iters[b] = it;
   }
+  if constexpr (WARM) {                                // the seed of the handle's next step: the set this solve ended with
+    if (tid == 0) s.changed = iterate && st <= 1;      // (empty without an iteration and behind a failed solve)
+    __syncthreads();
+    const bool keep = s.changed != 0;
+    for (int j = tid; j < nbox; j += blockDim.x) seed.ws[b * nbox + j] = keep ? s.act[j] : (signed char)0;
+  }
 }
 
 // Whole closed loop of one instance of a bounded handle in one workgroup: the twin of ddmpc_closed_loop_convex_warm_kernel
 // (same fixed-size arrays and the same checks of ddmpc_closed_loop behind them).  Per solve the law on the boxed rows and the
 // n_mpc_step * m input rows in use, the iteration of ddmpc_box_step_kernel, the M_A ev correction of those rows, then the
 // plant / FIFO steps of ddmpc_plant_kernel; everything on the last solve.  SAFE: as in ddmpc_box_step_kernel; an instance the
-// safeguard finishes carries on with the loop.  YB: as in ddmpc_box_step_kernel.
-template <bool SAFE, bool YB>
+// safeguard finishes carries on with the loop.  YB: as in ddmpc_box_step_kernel.  Seed = BoxSeed: the set stays in s.act from one
+// solve of the loop to the next; the first solve takes the handle's seed when seed.use, the last one leaves its set in seed.ws.
+template <bool SAFE, bool YB, class... Seed>
 __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                              const int* __restrict__ prep_status, int ns, const double* __restrict__ pl,
                                              int n_steps, int n_mpc_step, double* __restrict__ x, double* __restrict__ u_past,
@@ -534,7 +608,10 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
                                              double* __restrict__ y_sys, int* __restrict__ status_out, double* __restrict__ beta_ws,
                                              signed char* __restrict__ act_ws, int nbox, const int* __restrict__ tab,
                                              const double* __restrict__ bd, const double* __restrict__ Mcol, double* __restrict__ sg,
-                                             const int* __restrict__ refined, double* __restrict__ lw_up, double* __restrict__ lw_yp) {
+                                             const int* __restrict__ refined, double* __restrict__ lw_up, double* __restrict__ lw_yp,
+                                             Seed... seed_arg) {
+  constexpr bool WARM = sizeof...(Seed) != 0;
+  [[maybe_unused]] const BoxSeed seed = box_seed_of(seed_arg...);
   __shared__ double pv[WARM_MAX_NF];
   __shared__ double uo[WARM_MAX_NF];      // the first n_mpc_step*m entries of optimal_u
   __shared__ double xs[16], xn[16];       // (ns <= 16 is checked by ddmpc_closed_loop)
@@ -564,6 +641,8 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
   double* up = pv;
   double* yp = pv + P.npu;
   int stc = 0;                                        // worst status so far (ddmpc_plant_kernel's st_acc)
+  if constexpr (WARM)                                 // the seed stays in s.act from one solve of the loop to the next
+    for (int j = tid; j < nbox; j += blockDim.x) s.act[j] = seed.use ? seed.ws[b * nbox + j] : (signed char)0;
   for (int t0 = 0; t0 < n_steps; t0 += n_mpc_step) {
     __syncthreads();
     const bool last = (t0 + n_mpc_step >= n_steps);
@@ -589,7 +668,9 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
     int st = st0, it = 1;
     const bool iterate = viol && st <= 1;
     if (iterate) {
-      int dst = box_iterate<YB>(P, T, Mb, Sg, bsh, s, &it);
+      int dst;
+      if constexpr (WARM) dst = box_iterate_seeded<SAFE, YB>(P, T, Mb, Sg, bsh, s, &it);
+      else dst = box_iterate<YB>(P, T, Mb, Sg, bsh, s, &it);
       if constexpr (SAFE) {
         __shared__ BoxSafeLds q;
         if (dst == 4 && !s.fail) {
@@ -623,6 +704,9 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
     }
     if (__syncthreads_or(nonfin)) st = 4;
     stc = (st > stc) ? st : stc;
+    if constexpr (WARM)                               // (an empty seed without an iteration and behind a failed solve)
+      if (!iterate || st > 1)
+        for (int j = tid; j < nbox; j += blockDim.x) s.act[j] = 0;
     if (tid == 0) {
       const int nsub = (t0 + n_mpc_step <= n_steps) ? n_mpc_step : n_steps - t0;
       for (int j = 0; j < nsub; ++j) {
@@ -663,6 +747,8 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
   }
   if (tid < ns) x[b * ns + tid] = xs[tid];
   if (tid == 0) status_out[b] = stc;
+  if constexpr (WARM)
+    for (int j = tid; j < nbox; j += blockDim.x) seed.ws[b * nbox + j] = s.act[j];
 }
 
 }  // namespace ddmpc

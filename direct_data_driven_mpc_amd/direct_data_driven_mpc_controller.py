@@ -243,6 +243,8 @@ class DirectDataDrivenMPCController:
                 self._engine.set_output_bounds(*self._output_bounds)
             if getattr(self, "_box_safeguard", False):
                 self._engine.set_box_safeguard(True)
+            if getattr(self, "_box_warm_start", False):
+                self._engine.set_box_warm_start(True)
             if getattr(self, "_large_box_capacity", None) is not None:
                 self._engine.set_large_box_capacity(self._large_box_capacity)
             if getattr(self, "_large_box_safeguard", False):
@@ -353,6 +355,14 @@ class DirectDataDrivenMPCController:
             self._engine.set_box_safeguard(self._box_safeguard)
             self._cold_solved = False
             self.problem.solve()
+
+    def set_box_warm_start(self, on: bool) -> None:
+        """With input or output bounds (up to 271 rows): start the active-set iteration of every later control step from the set
+        the previous solve ended with instead of the empty set (`BatchedDDMPC.set_box_warm_start`).  Remembered for a rebuilt
+        engine handle.  The solution in hand stays as it is: the optimum does not depend on where the iteration starts."""
+        self._box_warm_start = bool(on)
+        if self._engine is not None:
+            self._engine.set_box_warm_start(self._box_warm_start)
 
     def set_large_box_capacity(self, k: int) -> None:
         """With bounds on a long horizon (beyond 271 rows): how many boxed components may be active at once, 64 (default), 128,

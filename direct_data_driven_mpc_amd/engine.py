@@ -396,6 +396,17 @@ class BatchedDDMPC:
         a kept `prepare` stays valid."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_BOX_SAFEGUARD, 1 if on else 0))
 
+    def set_box_warm_start(self, on: bool) -> None:
+        """Input / output bounds up to 271 rows: True = `step` (`solve(..., warm=True)`) and the fused `closed_loop` start the
+        active-set iteration from the signed set the last solve of the handle ended with instead of the empty set
+        (DDMPC_OPT_BOX_WARM_START); a seeded run that fails starts again from the empty set, so the status is never worse.
+        Results agree with False to rounding, `iters` is what the seeded run took.  The first solve after `prepare` and every
+        cold `solve` start from the empty set and are bit-equal to False.  Setting it (either value) drops the seed, as do
+        `set_data`, `set_setpoints`, `set_input_bounds`, `set_output_bounds` and a new `prepare`.  False (default) = every solve
+        from the empty set.  A kept `prepare` stays valid; no effect beyond 271 rows, without finite bounds or on a slack-only
+        CONVEX handle."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_BOX_WARM_START, 1 if on else 0))
+
     def get_solution(self, what: str) -> np.ndarray:
         """`.value` of alpha / ubar / ybar / sigma after the last solve (host array)."""
         sel = {"alpha": L.SOL_ALPHA, "ubar": L.SOL_UBAR, "ybar": L.SOL_YBAR, "sigma": L.SOL_SIGMA}[what]

@@ -50,6 +50,8 @@ def parse_args():
     ap.add_argument("--y_max", type=float, nargs="+", default=None, help="upper output bounds; give both or neither")
     ap.add_argument("--box_safeguard", action="store_true",
                     help="with input bounds: finish solves on which the active-set iteration cycles by a primal active-set method")
+    ap.add_argument("--box_warm_start", action="store_true",
+                    help="with bounds up to 271 rows: start each solve's active-set iteration from the previous solve's set")
     ap.add_argument("--large_box_capacity", type=int, choices=[64, 128, 192, 256], default=None,
                     help="with bounds beyond 271 rows: how many boxed components may be active at once (default 64)")
     ap.add_argument("--large_box_safeguard", action="store_true",
@@ -104,6 +106,8 @@ def main():
         eng.set_output_bounds(a.y_min if len(a.y_min) > 1 else a.y_min[0], a.y_max if len(a.y_max) > 1 else a.y_max[0])
     if a.box_safeguard:
         eng.set_box_safeguard(True)
+    if a.box_warm_start:
+        eng.set_box_warm_start(True)
     if a.large_box_capacity is not None:
         eng.set_large_box_capacity(a.large_box_capacity)
     if a.large_box_safeguard:

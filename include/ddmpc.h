@@ -215,6 +215,28 @@ extern "C" {
                                          Values other than 0 / 1: DDMPC_ERR_INVALID.  Accepted on any handle; no effect up to 271
                                          rows, without finite bounds or off the phase kernels; keeps what ddmpc_prepare kept and
                                          forgets the last solution.  A slack-only CONVEX handle is not covered */
+#define DDMPC_OPT_BOX_WARM_START 15     /* bounded handles up to 271 rows (ddmpc_set_input_bounds / ddmpc_set_output_bounds): 1 = ddmpc_step and
+                                         the fused ddmpc_closed_loop start the primal-dual active-set iteration from the signed set
+                                         the last solve of the handle ended with (ddmpc_step, ddmpc_solve or ddmpc_closed_loop; in the
+                                         fused loop the set also passes from one solve of the loop to the next), not from the empty
+                                         set.  The law is still tested under the empty set first: no violation is `iters` = 1 and an
+                                         empty seed.  With a violation and a non-empty seed the seed is solved for (solve number 2)
+                                         and the usual test / solve loop goes on under the max_iter cap.  A seeded run that meets a
+                                         non-positive pivot, or ends at the cap, starts again from the empty set with a fresh cap --
+                                         the status is never worse than with 0 -- except that at the cap with
+                                         DDMPC_OPT_BOX_SAFEGUARD = 1 it goes straight to the safeguard; `iters` counts every solve
+                                         made, the law once.  The optimum does not depend on the seed: results agree with 0 to
+                                         rounding, `iters` differs.  The first solve after ddmpc_prepare has no seed and is bit-equal
+                                         to 0; so are ddmpc_solve and DDMPC_PATH_COLD (always from the empty set; they leave a
+                                         seed for a following ddmpc_step).  The seed is dropped by everything that makes
+                                         ddmpc_get_solution report DDMPC_ERR_NOT_READY on this route (ddmpc_set_data,
+                                         ddmpc_set_setpoints, ddmpc_set_input_bounds, ddmpc_set_output_bounds, a new ddmpc_prepare) and
+                                         by setting this option to either value; an instance whose solve ended with status > 1
+                                         leaves an empty seed.  One byte per boxed component and instance.  0 (default) = every solve
+                                         from the empty set, the kernels as they were.  Values other than 0 / 1: DDMPC_ERR_INVALID.
+                                         Accepted on any handle; keeps what ddmpc_prepare kept and the last solution.  No effect
+                                         beyond 271 rows, without finite bounds, and on a slack-only CONVEX handle (it keeps the
+                                         slack-only kernels, as for DDMPC_OPT_BOX_SAFEGUARD) */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -358,6 +380,7 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
  * Same solve count, max_iter cap and status 4 (solver_error) at the cap or on a non-positive pivot as under the slack box; a box
  * tight enough to make the rule cycle (width 0.2 around u_s at the data tail) ends there unless DDMPC_OPT_BOX_SAFEGUARD = 1, which
  * finishes such an instance by a primal active-set method.  In the solution an active input equals its bound exactly.
+ * DDMPC_OPT_BOX_WARM_START = 1 starts the iteration of ddmpc_step and of the fused loop from the last solve's set instead.
  *   ddmpc_prepare: law + M, nbox r doubles per instance with nbox = [p L or p (L - n) when CONVEX] + [free steps x bounded
  *     channels] -- 122 KB at L = 30, n = 4, m = p = 2, CONVEX, both channels bounded: 0.5 GB at 4096 instances -- plus
  *     nbox (nbox + 1) / 2 doubles of k x k scratch when nbox > 16.  An allocation failure is DDMPC_ERR_HIP.
