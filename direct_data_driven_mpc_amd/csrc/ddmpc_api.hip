@@ -200,6 +200,7 @@ struct LastSolve {
   XState x = XState::Written;
   int box_cap = RR3_KMAX;                  // Route::RobustPhases: columns of W of the kernel that wrote the per-instance record (its layout)
   bool box_seed = false;                   // Route::BoxLaw, DDMPC_OPT_BOX_WARM_START: d_box_seed holds the signed set that solve ended with
+  bool large_seed = false;                 // Route::RobustPhases, DDMPC_OPT_LARGE_BOX_WARM_START: d_large_seed holds the set that solve ended with
 };
 
 // What ddmpc_prepare kept; it serves the route it was formed on only (prep_valid).
@@ -284,6 +285,8 @@ struct ddmpc_handle {
   int box_safeguard = 0;                   // DDMPC_OPT_BOX_SAFEGUARD: Route::BoxLaw instances at the max_iter cap are finished by box_safeguard
   int box_warm = 0;                        // DDMPC_OPT_BOX_WARM_START: Route::BoxLaw steps start their iteration from the last solve's set
   DevBuf d_box_seed;                       // ... that set, [batch][nbox] (written by the WARM instantiations of the box kernels)
+  int large_box_warm = 0;                  // DDMPC_OPT_LARGE_BOX_WARM_START: steps of a bounded handle beyond 271 rows start from the last solve's set
+  DevBuf d_large_seed;                     // ... that set, sa + 4 say per row, [batch][rE] (rr3_box_keep_seed_kernel)
   // input bounds (ddmpc_set_input_bounds) and output bounds (ddmpc_set_output_bounds): per channel, +-infinity = none; the
   // vectors are empty without a finite bound of their kind; `bounded` = some bound of either kind is finite (Route::BoxLaw)
   std::vector<double> umin_h, umax_h, ymin_h, ymax_h;
@@ -319,8 +322,10 @@ static bool nominal_route(Route r) { return r == Route::NominalPhases || r == Ro
 // What ddmpc_prepare kept is the input of the route it was formed on only (the routes keep different things next to the factors).
 static bool prep_valid(const ddmpc_handle* h) { return h->prep.valid && h->prep.route == select_route(h); }
 
-// Forget what ddmpc_prepare kept (the data, the weights or an option it was formed with changed).
-static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; }
+// Forget what ddmpc_prepare kept (the data, the weights or an option it was formed with changed) -- and with it the seed of
+// DDMPC_OPT_LARGE_BOX_WARM_START, which belongs to the kept factors, the order and the box table (every call that changes one
+// of them comes through here: ddmpc_set_data, ddmpc_set_setpoints, both bounds calls, a new ddmpc_prepare).
+static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; h->last.large_seed = false; }
 
 // A call that writes solve outputs starts the record afresh (nothing of an earlier call survives) and makes it readable at its end.
 static Route begin_solve(ddmpc_handle* h, Route route) { h->last = LastSolve{}; h->last.route = route; return route; }
@@ -331,6 +336,13 @@ static void end_solve(ddmpc_handle* h, const double* up, const double* yp) { h->
 // so a seed indexed by another box table is never read.  Asked before begin_solve starts the next record.
 static bool box_seed_valid(const ddmpc_handle* h) {
   return h->box_warm && h->last.valid && h->last.route == Route::BoxLaw && h->last.box_seed;
+}
+
+// DDMPC_OPT_LARGE_BOX_WARM_START: the last solve of the handle left a seed the next step on Route::RobustPhases may read.  Unlike
+// box_seed_valid it does not ask for a finished record: the steps of the per-step closed loop follow each other inside one
+// call.  What drops it clears the flag itself (forget_prep, options 12, 13, 14 and 16).  Asked before begin_solve.
+static bool large_seed_valid(const ddmpc_handle* h) {
+  return h->large_box_warm && h->last.route == Route::RobustPhases && h->last.large_seed;
 }
 
 // A parameter table of upload_params (d_tabi: 3 rows, d_tabd: 4 rows of 16 NT entries) read back to the host.  The blocking copy
@@ -897,7 +909,7 @@ int ddmpc_destroy(ddmpc_handle* h) {
   DevBuf* bufs[] = {&h->d_tabd, &h->d_tabi, &h->d_ud, &h->d_yd, &h->d_up, &h->d_yp, &h->d_uopt,
                     &h->d_cost, &h->d_status, &h->d_iters, &h->d_beta, &h->d_act, &h->d_out, &h->d_stamps,
                     &h->d_pl, &h->d_x, &h->d_w, &h->d_usys, &h->d_ysys, &h->d_stacc,
-                    &h->d_lfac, &h->d_lfacT, &h->d_gain, &h->d_prep_status, &h->d_zero, &h->d_dmat, &h->d_need, &h->d_io, &h->d_rr, &h->d_alpha, &h->d_zws, &h->d_resc, &h->d_xws, &h->d_rflag, &h->d_rrmeta, &h->d_gpre, &h->d_perm, &h->d_rr2d, &h->d_rr2res, &h->d_rr2mt, &h->d_rr2v, &h->d_rr2zp, &h->d_rr2sc, &h->d_wz, &h->d_gz, &h->d_gres, &h->d_zvirt, &h->d_rr3w, &h->d_rr3k, &h->d_rr_fb, &h->d_rrmeta_fb, &h->d_rr2cand, &h->d_rr2tol, &h->d_rr2rank, &h->d_wd, &h->d_rr2y,
+                    &h->d_lfac, &h->d_lfacT, &h->d_gain, &h->d_prep_status, &h->d_zero, &h->d_dmat, &h->d_need, &h->d_io, &h->d_rr, &h->d_alpha, &h->d_zws, &h->d_resc, &h->d_xws, &h->d_rflag, &h->d_rrmeta, &h->d_gpre, &h->d_perm, &h->d_rr2d, &h->d_rr2res, &h->d_rr2mt, &h->d_rr2v, &h->d_rr2zp, &h->d_rr2sc, &h->d_wz, &h->d_gz, &h->d_gres, &h->d_zvirt, &h->d_rr3w, &h->d_rr3k, &h->d_large_seed, &h->d_rr_fb, &h->d_rrmeta_fb, &h->d_rr2cand, &h->d_rr2tol, &h->d_rr2rank, &h->d_wd, &h->d_rr2y,
                     &h->d_mcol, &h->d_cwl_tab, &h->d_cwl_sg, &h->d_cwl_ref, &h->d_r3y, &h->d_r3res, &h->d_r3zp, &h->d_r3flag,
                     &h->d_box_bd, &h->d_ubnd, &h->d_ybnd, &h->d_r3bi, &h->d_r3bd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp,
                     &h->d_box_seed};
@@ -1105,8 +1117,11 @@ static int launch_rr3_factors(ddmpc_handle* h) {
 }
 
 // A bounded handle with DDMPC_OPT_LARGE_BOX_CAPACITY above 64 is served by rr3_solve_box_wide_kernel (ddmpc_rr3_box_wide.hpp), and
-// so is one with DDMPC_OPT_LARGE_BOX_SAFEGUARD at every capacity (64 included: the safeguard writes one layout of W, tiles and record).
-static bool rr3_wide(const ddmpc_handle* h) { return h->bounded && (h->large_box_cap > RR3_KMAX || h->large_box_safeguard != 0); }
+// so is one with DDMPC_OPT_LARGE_BOX_SAFEGUARD at every capacity (64 included: the safeguard writes one layout of W, tiles and record)
+// and one with DDMPC_OPT_LARGE_BOX_WARM_START (the seeded instantiation is that kernel's).
+static bool rr3_wide(const ddmpc_handle* h) {
+  return h->bounded && (h->large_box_cap > RR3_KMAX || h->large_box_safeguard != 0 || h->large_box_warm != 0);
+}
 
 // The descriptor of the kept factors and of the solve's workspace (sized here).
 static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
@@ -1123,6 +1138,7 @@ static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
     kstride = 4 + cap + rv + 4;
   }
   int rc;
+  if (rr3_wide(h) && h->large_box_warm && (rc = h->d_large_seed.ensure(B * (size_t)kq.rE))) return rc;   // DDMPC_OPT_LARGE_BOX_WARM_START
   if ((rc = h->d_rr2v.ensure(B * (size_t)R3_NV * VL * sizeof(double))) || (rc = h->d_rr2zp.ensure(B * (size_t)RR2_NG * VL * sizeof(double))) ||
       (rc = h->d_rr3w.ensure(B * (size_t)wstride * sizeof(double))) || (rc = h->d_rr3k.ensure(B * (size_t)kstride * sizeof(int))) ||
       (rc = h->d_beta.ensure(B * (size_t)kq.rE * sizeof(double))) || (rc = h->d_act.ensure(B * (size_t)kq.rE)))
@@ -1143,9 +1159,10 @@ static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
 }
 
 // The solve on those factors (what a control step repeats, controller.py:389-407).  only (nullptr: the whole batch): per-instance
-// flags of the law step, the solve launches leave every other instance alone.
+// flags of the law step, the solve launches leave every other instance alone.  seeded (DDMPC_OPT_LARGE_BOX_WARM_START = 1 on a
+// bounded handle only): the iteration starts from the set in d_large_seed; with the option 1 every call leaves its set there.
 static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up, const double* yp, double* uo, double* cost,
-                            int32_t* status, int32_t* iters, const int* only = nullptr, int* only_si = nullptr) {
+                            int32_t* status, int32_t* iters, const int* only = nullptr, int* only_si = nullptr, bool seeded = false) {
   const int r = kq.r, VL = (r + 63) & ~63;
   const size_t B = (size_t)h->batch;
   const Rr3Lds LD = Rr3Lds::make(r);
@@ -1173,6 +1190,14 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
       HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<false>, blds));
       HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<true>, blds));
     }
+    if (h->large_box_warm && seeded) {
+      // DDMPC_OPT_LARGE_BOX_WARM_START with a valid seed: the seeded instantiation (without one, the kernel of the option 0)
+      const auto kern = rr3_solve_box_wide_kernel<false, Rr3Seed>;
+      const Rr3Seed seed{(const signed char*)h->d_large_seed.p, h->large_box_safeguard ? 1 : 0};
+      if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)kern, blds));
+      hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status, (int*)iters,
+                         (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap, seed);
+    } else
     hipLaunchKernelGGL(rr3_solve_box_wide_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
                        (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap);
     if (h->large_box_safeguard) {
@@ -1215,6 +1240,12 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     else
     hipLaunchKernelGGL(rr3_solve_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), lds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
                        (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, only);
+  }
+  if (wide && h->large_box_warm) {
+    // the signed set the call finally reported (the solve, safeguard or refinement launch wrote it last) becomes the next step's seed
+    hipLaunchKernelGGL(rr3_box_keep_seed_kernel, dim3((unsigned)B), dim3(256), 0, h->stream, r, kq.rE, (const int*)status,
+                       (const signed char*)h->d_act.p, (signed char*)h->d_large_seed.p);
+    h->last.large_seed = true;
   }
   HIP_TRY(hipGetLastError());
   if (!h->bounded) {
@@ -1324,14 +1355,14 @@ static int launch_rr3_law_step(ddmpc_handle* h, const double* up, const double* 
 
 // ROBUST controllers beyond the register-resident kernels (Route::RobustPhases, Route::RobustOneWg).
 static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const double* up, const double* yp, double* uo,
-                               double* cost, int32_t* status, int32_t* iters) {
+                               double* cost, int32_t* status, int32_t* iters, bool seeded = false) {
   int rc;
   if (route == Route::RobustPhases) {
     // lock-step factorisation of the whole batch, then one workgroup per instance that streams the factor twice and runs the
     // active-set iterations on its trailing block
     if (stage != Stage::OnFactors && (rc = launch_rr3_factors(h))) return rc;
     if (stage == Stage::OnFactors && h->large_affine && h->prep.law) return launch_rr3_law_step(h, up, yp, uo, cost, status, iters);
-    if (stage != Stage::Factors && (rc = launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters))) return rc;
+    if (stage != Stage::Factors && (rc = launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters, nullptr, nullptr, seeded))) return rc;
     return DDMPC_OK;
   }
   // the one-workgroup kernel: matrices in a per-instance slice of a global workspace
@@ -1950,11 +1981,11 @@ static int solve_on_route(ddmpc_handle* h, const double* up, const double* yp, d
 // A control step on what ddmpc_prepare kept (ddmpc_step, the per-step closed loop): the callers have prepared on this route.
 static int step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                          int32_t* iters) {
-  const bool seeded = box_seed_valid(h);
+  const bool seeded = box_seed_valid(h), large_seeded = large_seed_valid(h);
   const Route route = begin_solve(h, select_route(h));
   if (route == Route::BoxLaw) return launch_box_step(h, up, yp, uo, cost, status, iters, seeded);
   if (route == Route::RobustPhases || route == Route::RobustOneWg)
-    return launch_large_robust(h, route, Stage::OnFactors, up, yp, uo, cost, status, iters);
+    return launch_large_robust(h, route, Stage::OnFactors, up, yp, uo, cost, status, iters, large_seeded);
   if (route != Route::Cold) return launch_large_nominal_warm(h, route, up, yp, uo, cost, status, iters);
   const int rc = launch_warm(h, up, yp, uo, cost, status, iters);
   return rc ? rc : launch_nominal_rescue(h, route, up, yp, uo, cost, status, iters);
@@ -2494,6 +2525,7 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
         return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_LARGE_BOUNDS = 0 on a handle with input or output bounds beyond 271 rows: remove the "
                     "bounds first");
       h->large_bounds = value;            // (which calls are accepted: nothing prepared depends on it)
+      h->last.large_seed = false;         // (DDMPC_OPT_LARGE_BOX_WARM_START: the next step starts from the empty set)
       return DDMPC_OK;
     case DDMPC_OPT_BOX_SAFEGUARD:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_BOX_SAFEGUARD must be 0 or 1");
@@ -2509,11 +2541,19 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
         return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_CAPACITY must be 64, 128, 192 or 256");
       h->large_box_cap = value;           // (which bounded phase kernel is launched and how its workspace is sized: the factors do not depend on it)
       h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
+      h->last.large_seed = false;
       return DDMPC_OK;
     case DDMPC_OPT_LARGE_BOX_SAFEGUARD:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_SAFEGUARD must be 0 or 1");
       h->large_box_safeguard = value;     // (which kernels serve a bounded handle beyond 271 rows and how their workspace is sized: the factors do not depend on it)
       h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
+      h->last.large_seed = false;
+      return DDMPC_OK;
+    case DDMPC_OPT_LARGE_BOX_WARM_START:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_WARM_START must be 0 or 1");
+      h->large_box_warm = value;          // (with 1 the wide kernels serve a bounded handle beyond 271 rows at every capacity: the factors do not depend on it)
+      h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
+      h->last.large_seed = false;         // (setting it, to either value, drops the seed)
       return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");

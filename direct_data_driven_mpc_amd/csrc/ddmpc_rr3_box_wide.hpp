@@ -229,17 +229,35 @@ __device__ __forceinline__ double rr3w_tile_bwd(const double* Sm, int kb, int x,
   return h;
 }
 
+// DDMPC_OPT_LARGE_BOX_WARM_START: the signed set the handle's last solve ended with, sa + 4 say per row in COMPONENT order
+// ([batch][rE] bytes, the layout of the act_ws workspace; written by rr3_box_keep_seed_kernel behind the last launch of a solve),
+// and whether rr3_box_safeguard_kernel follows the launch (a seeded run at the cap is then left to it).
+struct Rr3Seed {
+  const signed char* set;
+  int safeguard;
+};
+
 // ---------------------------------------------------------------------------------------------------------------
 // The solve on the kept factor with the table-driven box and up to `cap` active components (the twin of rr3_solve_box_kernel;
 // same launch geometry, LDS of Rr3Lds::total + rr3w_lds_extra(cap) doubles).  More than cap active components in an iteration,
 // or a non-positive pivot in any diagonal tile of S: status 4 at that iteration.
+// Seed...: empty (the kernel as it is launched without a seed) or one Rr3Seed ("Warm start"): when the empty
+// set's solution violates a bound and the seed holds an active component, the iteration goes on from the seed instead of from
+// what the test asked for.  A seeded run that ends at the cap, beyond the capacity or on a non-positive pivot starts again from
+// the empty set (act = 0, y' = y, beta of the trailing block by one backward substitution) with a fresh cap; run0 is the count
+// before the run in progress, so iter - run0 is that run's own count and iter every solve attempted, the empty set's once.
+// The record of a failed instance holds the count of its LAST run (kq[2] >= max_iter: that run ended at its own cap, what
+// rr3_box_safeguard_kernel asks), that of a finished one the whole count.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool REFINE_PASS>
+template <bool REFINE_PASS, class... Seed>
 __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KParams P, int RPs, const double* __restrict__ u_past,
                                                                     const double* __restrict__ y_past, double* __restrict__ u_opt,
                                                                     double* __restrict__ cost, int* __restrict__ status,
                                                                     int* __restrict__ iters, double* __restrict__ beta_ws,
-                                                                    signed char* __restrict__ act_ws, int defer_outputs, Rr3Box X, int cap) {
+                                                                    signed char* __restrict__ act_ws, int defer_outputs, Rr3Box X, int cap,
+                                                                    Seed... seed) {
+  static_assert(sizeof...(Seed) <= 1 && !(REFINE_PASS && sizeof...(Seed) != 0), "one seed, and for the solve launch only");
+  constexpr bool SEEDED = sizeof...(Seed) != 0;
   extern __shared__ __attribute__((aligned(16))) double r3_lds[];
   const long long b = blockIdx.x;
   const int tid = threadIdx.x, nthr = blockDim.x;
@@ -268,6 +286,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
   const double* up = u_past + b * (long long)P.npu;
   const double* yp = y_past + b * (long long)(n * p);
   int st = 0, iter = 0, k = 0;
+  [[maybe_unused]] int run0 = 0, phase = 0;                  // (seeded) the count before the run in progress; 0 no seed yet, 1 the seeded run, 2 started again
   const long long t_begin = (long long)__builtin_amdgcn_s_memrealtime();   // diagnostics (kq[.. + rv ..]): when this workgroup ran
   // h = W'v on the trailing block (v: LDS, absolute rows), into hv[0 .. k): a column per thread of each of the 8 row parts
   auto w_times = [&](const double* v) {
@@ -377,6 +396,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
       tv[i] = t; act[i] = 0; y2[i] = 0.0; bv[i] = 0.0;
     }
     if (tid == 0) flagw[3] = 0;
+    if constexpr (SEEDED) { if (tid == 0) flagw[5] = 0; }      // [5] the seed holds an active component
     if (block_sum(nbad, tmp) != 0.0) st = 4;                 // (uniform) a pivot of K0 failed: not positive definite numerically
     __syncthreads();
     if (st == 0) {
@@ -388,6 +408,15 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
         for (int i = tid; i < LD.VL; i += nthr) y2[i] = yv[i];
         __syncthreads();
         rr3_trsv_bwd(G, m64, r, live, nb, b0, y2, bv, red, tmp);         // beta on the trailing block: the empty active set
+        // (seeded) give the run in progress up: the empty set again, its beta on the trailing block (yv is kept), a fresh cap
+        [[maybe_unused]] auto restart = [&]() {
+          int ot = threadIdx.x;
+          asm volatile("" : "+v"(ot));
+          for (int i = ot; i < LD.VL; i += nthr) { act[i] = 0; y2[i] = yv[i]; }
+          __syncthreads();
+          rr3_trsv_bwd(G, m64, r, live, nb, b0, y2, bv, red, tmp);
+          run0 = iter; phase = 2; k = 0;
+        };
         for (;;) {
           ++iter;
           if (tid == 0) flagw[0] = 0;
@@ -406,7 +435,42 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
           }
           __syncthreads();
           if (flagw[0] == 0) break;
-          if (iter >= P.max_iter) { st = 4; break; }
+          if constexpr (SEEDED) {
+            const Rr3Seed sd = (seed, ...);
+            if (iter - run0 >= P.max_iter) {
+              if (phase != 1 || sd.safeguard) { st = 4; break; }       // (a seeded run at the cap with the safeguard on: left to it)
+              --iter;                                                  // (the test that found the cap followed a solve already counted)
+              restart();
+              continue;
+            }
+            if (phase == 0) {
+              // the empty set's solution violates a bound: the seed, read component by component (a code outside the table's
+              // components or outside -1 .. 1 is no seed), takes the place of what the test asked for -- unless it is empty
+              phase = 2;
+              const signed char* sset = sd.set + b * (long long)P.rE;
+              for (int s = ot; s < X.nbox; s += nthr) {
+                const int code = sset[perm[X.ip[s]]];
+                const int a = X.ip[X.nbox + s] ? rr3_say(code) : rr3_sa(code);
+                if (a == 1 || a == -1) flagw[5] = 1;
+              }
+              __syncthreads();
+              if (flagw[5] != 0) {                                     // (uniform)
+                phase = 1;
+                for (int i = ot; i < LD.VL; i += nthr) act[i] = 0;
+                __syncthreads();
+                for (int s = ot; s < X.nbox; s += nthr) {
+                  const int i = X.ip[s], isy = X.ip[X.nbox + s];
+                  const int code = sset[perm[i]];
+                  const int a = isy ? rr3_say(code) : rr3_sa(code);
+                  if (a == 1 || a == -1) atomicAdd(&act[i], a * (isy ? 4 : 1));
+                }
+                __syncthreads();
+              }
+            }
+          } else if (iter >= P.max_iter) {
+            st = 4;
+            break;
+          }
           // the active components, ascending (deterministic column order)
           if (ot < 64) {
             int base = 0;
@@ -426,6 +490,9 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
           }
           __syncthreads();
           k = flagw[1];
+          if constexpr (SEEDED) {
+            if (k > cap && phase == 1) { restart(); continue; }
+          }
           if (k > cap) { st = 4; k = 0; break; }                          // more columns than W holds
           const int nblk = (k + 63) >> 6;
           for (int cb = 0; cb < nblk; ++cb)                               // W = L_TT^-1 E_T, 64 columns per pass
@@ -453,6 +520,9 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
             if (oj < k - 64 * (J + 1)) rr3w_chol_rows(rr3w_tile(Sg, J + 1 + (oj >> 6), J) + (size_t)(oj & 63) * 64, Sm);
             __syncthreads();
           }
+          if constexpr (SEEDED) {
+            if (bad && phase == 1) { restart(); continue; }
+          }
           if (bad) { st = 4; k = 0; break; }
           s_solve();
           if (ot < k) ev[ot] += lsh[ot];                                  // y' = y + W (shift + cv) on the trailing block
@@ -474,6 +544,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
     }
     if (tid == 0) {
       kq[0] = (st == 0) ? k : 0; kq[1] = st; kq[2] = iter; kq[3] = k;
+      if constexpr (SEEDED) { if (st != 0) kq[2] = iter - run0; }        // (a failed instance: the count of its last run)
       const long long t_end = (long long)__builtin_amdgcn_s_memrealtime();
       kq[4 + cap + S.rv] = (int)(t_begin & 0x7fffffff); kq[4 + cap + S.rv + 1] = (int)(t_end - t_begin);   // (100 MHz ticks)
       kq[4 + cap + S.rv + 2] = flagw[3];                                  // the most components active in any iteration
@@ -516,6 +587,18 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
     __syncthreads();
     rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, 0, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws);
   }
+}
+
+// DDMPC_OPT_LARGE_BOX_WARM_START: behind the last launch of a solve, what the call finally reported becomes the seed of the next
+// step -- the codes rr3_box_outputs left in act_ws (component order) for an instance with status 0 or 1, the empty set for any
+// other (its codes were not written).  A buffer of its own: act_ws is the workspace ddmpc_get_solution reads, shared by every
+// route of the handle.
+__global__ void rr3_box_keep_seed_kernel(int r, int rE, const int* __restrict__ status, const signed char* __restrict__ act_ws,
+                                         signed char* __restrict__ seed) {
+  const long long b = blockIdx.x;
+  const int st = status[b];
+  for (int i = threadIdx.x; i < rE; i += blockDim.x)
+    seed[b * (long long)rE + i] = (i < r && (st == 0 || st == 1)) ? act_ws[b * (long long)rE + i] : (signed char)0;
 }
 
 }  // namespace ddmpc

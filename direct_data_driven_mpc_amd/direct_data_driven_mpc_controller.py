@@ -249,6 +249,8 @@ class DirectDataDrivenMPCController:
                 self._engine.set_large_box_capacity(self._large_box_capacity)
             if getattr(self, "_large_box_safeguard", False):
                 self._engine.set_large_box_safeguard(True)
+            if getattr(self, "_large_box_warm_start", False):
+                self._engine.set_large_box_warm_start(True)
         if not hasattr(self, "problem") or self.problem is None:
             self.problem = _Problem(self)
 
@@ -382,6 +384,17 @@ class DirectDataDrivenMPCController:
         if self._engine is not None:
             self._engine.set_large_box_safeguard(bool(on))
         self._large_box_safeguard = bool(on)
+        if self._engine is not None:
+            self._cold_solved = False
+            self.problem.solve()
+
+    def set_large_box_warm_start(self, on: bool) -> None:
+        """With bounds on a long horizon (beyond 271 rows): start the active-set iteration of every later control step from the
+        set the previous solve ended with instead of the empty set (`BatchedDDMPC.set_large_box_warm_start`).  Remembered for a
+        rebuilt engine handle.  The problem is solved again, as after `set_input_bounds`."""
+        if self._engine is not None:
+            self._engine.set_large_box_warm_start(bool(on))
+        self._large_box_warm_start = bool(on)
         if self._engine is not None:
             self._cold_solved = False
             self.problem.solve()

@@ -407,6 +407,18 @@ class BatchedDDMPC:
         CONVEX handle."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_BOX_WARM_START, 1 if on else 0))
 
+    def set_large_box_warm_start(self, on: bool) -> None:
+        """Bounded handles beyond 271 rows: True = `step` (`solve(..., warm=True)`) and the per-step `closed_loop` start the
+        active-set iteration from the signed set the last solve of the handle ended with instead of the empty set
+        (DDMPC_OPT_LARGE_BOX_WARM_START); a seeded run that fails starts again from the empty set, so the status is never worse.
+        Results agree with False to rounding, `iters` is every solve attempted.  The first step after `prepare` and every cold
+        `solve` start from the empty set.  Setting it (either value) drops the seed, as do `set_data`, `set_setpoints`,
+        `set_input_bounds`, `set_output_bounds`, a new `prepare`, `set_large_bounds`, `set_large_box_capacity` and
+        `set_large_box_safeguard`.  With True the wide kernels serve the handle at every capacity.  A kept `prepare` stays valid;
+        the last solution is forgotten until the next solve.  No effect up to 271 rows, without finite bounds or on a slack-only
+        CONVEX handle."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_BOX_WARM_START, 1 if on else 0))
+
     def get_solution(self, what: str) -> np.ndarray:
         """`.value` of alpha / ubar / ybar / sigma after the last solve (host array)."""
         sel = {"alpha": L.SOL_ALPHA, "ubar": L.SOL_UBAR, "ybar": L.SOL_YBAR, "sigma": L.SOL_SIGMA}[what]

@@ -237,6 +237,34 @@ extern "C" {
                                          Accepted on any handle; keeps what ddmpc_prepare kept and the last solution.  No effect
                                          beyond 271 rows, without finite bounds, and on a slack-only CONVEX handle (it keeps the
                                          slack-only kernels, as for DDMPC_OPT_BOX_SAFEGUARD) */
+#define DDMPC_OPT_LARGE_BOX_WARM_START 16 /* bounded handles beyond 271 rows (DDMPC_OPT_LARGE_BOUNDS): 1 = ddmpc_step and the per-step
+                                         ddmpc_closed_loop (DDMPC_PATH_AUTO / _WARM) start the primal-dual iteration from the signed
+                                         set the last solve of the handle ended with (ddmpc_step, ddmpc_solve or a step of the loop),
+                                         not from the empty set: the rule of DDMPC_OPT_BOX_WARM_START on the reduced system of this
+                                         route.  The empty set is still solved and tested first: no violation is
+                                         `iters` = 1 and an empty seed.  With a violation and a non-empty seed the seed is solved for
+                                         (solve number 2) and the usual test / solve loop goes on under the max_iter cap.  A seeded
+                                         run that meets a non-positive pivot, more active components than the capacity, or the cap
+                                         starts again from the empty set with a fresh cap -- the status is never worse than with 0 --
+                                         except that at the cap with DDMPC_OPT_LARGE_BOX_SAFEGUARD = 1 it goes straight to the
+                                         safeguard (`iters` = max_iter + its solves, bit-equal to 0); `iters` counts every solve
+                                         attempted, the empty set's once.  The optimum does not depend on the seed: results agree
+                                         with 0 to rounding, `iters` differs.  The first step after ddmpc_prepare has no seed;
+                                         ddmpc_solve and DDMPC_PATH_COLD always start from the empty set and leave a seed for a
+                                         following ddmpc_step.  Without a seed a call is bit-equal to 0 above capacity 64; with 1
+                                         the wide kernels serve the handle at every capacity, so at capacity 64 it agrees with 0
+                                         to rounding only (as DDMPC_OPT_LARGE_BOX_SAFEGUARD).  The seed is dropped by ddmpc_set_data,
+                                         ddmpc_set_setpoints, ddmpc_set_input_bounds, ddmpc_set_output_bounds, a new ddmpc_prepare
+                                         (the factors are new) and by setting DDMPC_OPT_LARGE_BOUNDS, _LARGE_BOX_CAPACITY,
+                                         _LARGE_BOX_SAFEGUARD or this option to any value; an instance whose call ended with
+                                         status > 1 leaves an empty seed, one finished by the safeguard the safeguard's final set.
+                                         A stale seed may cost solves and never changes a result.  One byte per row and instance.
+                                         0 (default) = every solve from the empty set, the kernels as they were.  Values other than
+                                         0 / 1: DDMPC_ERR_INVALID.  Accepted on any handle; keeps what ddmpc_prepare kept and forgets
+                                         the last solution (the record layout may change), as DDMPC_OPT_LARGE_BOX_CAPACITY.  No
+                                         effect up to 271 rows (DDMPC_OPT_BOX_WARM_START is the option of that size and has no
+                                         effect here), without finite bounds, off the phase kernels, and on a slack-only CONVEX
+                                         handle (it keeps rr3_solve_kernel) */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -410,7 +438,11 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
  *     and ddmpc_debug_stamps(enable).  NOMINAL, DDMPC_WEIGHT_DENSE and zero weights as above.
  *   DDMPC_OPT_BOX_SAFEGUARD is accepted and has no effect beyond 271 rows; the safeguard of this size is an option of its own,
  *     DDMPC_OPT_LARGE_BOX_SAFEGUARD = 1: an instance at the max_iter cap is solved again by the primal active-set method
- *     (`iters` = max_iter + its solves, working sets up to the capacity; see the option).  The box list has no length limit there. */
+ *     (`iters` = max_iter + its solves, working sets up to the capacity; see the option).  The box list has no length limit there.
+ *   DDMPC_OPT_BOX_WARM_START is accepted and has no effect beyond 271 rows; the warm start of this size is an option of its own,
+ *     DDMPC_OPT_LARGE_BOX_WARM_START = 1: ddmpc_step and the per-step ddmpc_closed_loop start the iteration from the signed set
+ *     the last solve ended with; a seeded run that fails starts again from the empty set, ddmpc_solve keeps the cold contract
+ *     and leaves a seed (see the option for what drops the seed and how `iters` counts). */
 int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max);
 
 /* Box on the predicted outputs: y_min[ch] <= ybar[k][ch] <= y_max[ch] on every FREE prediction step (the rows that carry Q;
