@@ -34,6 +34,7 @@ OPT_LARGE_BOX_CAPACITY = 13
 OPT_LARGE_BOX_SAFEGUARD = 14
 OPT_BOX_WARM_START = 15
 OPT_LARGE_BOX_WARM_START = 16
+OPT_LARGE_BOX_LAW = 17
 PIPELINE_ONE_WORKGROUP, PIPELINE_PHASES = 0, 1
 REFINE_OFF, REFINE_AUTO, REFINE_ALWAYS = 0, 1, 2
 PATH_AUTO, PATH_COLD, PATH_WARM = 0, 1, 2

@@ -3,6 +3,7 @@
 // conditions (direct_data_driven_mpc_controller.py:165-168,211-222,298-343,664-670),
 // device buffer ownership, kernel-instance selection, launch.
 #include "ddmpc_rr3_law.hpp"
+#include "ddmpc_rr3_box_law.hpp"
 #include "ddmpc_rr3_box.hpp"
 #include "ddmpc_rr3_box_wide.hpp"
 #include "ddmpc_rr3_box_safe.hpp"
@@ -207,7 +208,7 @@ struct LastSolve {
 struct Prep {
   bool valid = false;
   Route route = Route::Cold;
-  bool law = false;                        // beyond 271 rows: the affine law was formed (DDMPC_OPT_LARGE_AFFINE_LAW)
+  bool law = false;                        // beyond 271 rows: the affine law was formed (DDMPC_OPT_LARGE_AFFINE_LAW, DDMPC_OPT_LARGE_BOX_LAW)
   int r3_nolaw = 0;                        // ... ROBUST: instances whose law missed the refinement threshold (their steps take the filtered re-solve)
   int cwl_nbox = 0;                        // DDMPC_OPT_CONVEX_WARM_LAW, Route::BoxLaw: boxed components
   int box_threads = 0;                     // Route::BoxLaw: block of the box kernels (max(r, nbox) rounded up to 64)
@@ -287,6 +288,7 @@ struct ddmpc_handle {
   DevBuf d_box_seed;                       // ... that set, [batch][nbox] (written by the WARM instantiations of the box kernels)
   int large_box_warm = 0;                  // DDMPC_OPT_LARGE_BOX_WARM_START: steps of a bounded handle beyond 271 rows start from the last solve's set
   DevBuf d_large_seed;                     // ... that set, sa + 4 say per row, [batch][rE] (rr3_box_keep_seed_kernel)
+  int large_box_law = 0;                   // DDMPC_OPT_LARGE_BOX_LAW: steps of a bounded handle beyond 271 rows on the affine law while inside the box
   // input bounds (ddmpc_set_input_bounds) and output bounds (ddmpc_set_output_bounds): per channel, +-infinity = none; the
   // vectors are empty without a finite bound of their kind; `bounded` = some bound of either kind is finite (Route::BoxLaw)
   std::vector<double> umin_h, umax_h, ymin_h, ymax_h;
@@ -1181,15 +1183,30 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
   const bool wide = rr3_wide(h);
   const int cap = wide ? h->large_box_cap : RR3_KMAX;
   h->last.box_cap = cap;
+  const Rr3Only flt{only};                                  // (bounded handles, DDMPC_OPT_LARGE_BOX_LAW: the filtered instantiations)
   if (wide) {
     // DDMPC_OPT_LARGE_BOX_CAPACITY above 64: the twin with `capacity` columns of W and the tiled k x k system
-    if (only != nullptr) return fail(DDMPC_ERR_UNSUPPORTED, "a bounded handle has no affine law beyond 271 rows");
     X.nbox = h->nbox3; X.ip = (const int*)h->d_r3bi.p; X.bd = (const double*)h->d_r3bd.p;
     blds = lds + (size_t)rr3w_lds_extra(cap) * sizeof(double);
     if (blds > 64 * 1024) {
       HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<false>, blds));
       HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<true>, blds));
+      if (only != nullptr) {
+        HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<false, Rr3Only>, blds));
+        HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<true, Rr3Only>, blds));
+      }
     }
+    if (only != nullptr && h->large_box_warm && seeded) {
+      // DDMPC_OPT_LARGE_BOX_LAW: the same launches for the instances the law step flagged, every other workgroup leaves at once
+      const auto kern = rr3_solve_box_wide_kernel<false, Rr3Seed, Rr3Only>;
+      const Rr3Seed seed{(const signed char*)h->d_large_seed.p, h->large_box_safeguard ? 1 : 0};
+      if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)kern, blds));
+      hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status, (int*)iters,
+                         (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap, seed, flt);
+    } else if (only != nullptr) {
+      hipLaunchKernelGGL((rr3_solve_box_wide_kernel<false, Rr3Only>), dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo,
+                         cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap, flt);
+    } else
     if (h->large_box_warm && seeded) {
       // DDMPC_OPT_LARGE_BOX_WARM_START with a valid seed: the seeded instantiation (without one, the kernel of the option 0)
       const auto kern = rr3_solve_box_wide_kernel<false, Rr3Seed>;
@@ -1203,21 +1220,35 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     if (h->large_box_safeguard) {
       // DDMPC_OPT_LARGE_BOX_SAFEGUARD: the instances that reached max_iter are solved again by the primal method, before the
       // Hankel products and the refinement launch; every other workgroup leaves at once
-      if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)rr3_box_safeguard_kernel, blds));
-      hipLaunchKernelGGL(rr3_box_safeguard_kernel, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
+      if (only != nullptr) {
+        if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)rr3_box_safeguard_kernel<Rr3Only>, blds));
+        hipLaunchKernelGGL(rr3_box_safeguard_kernel<Rr3Only>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
+                           (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap, flt);
+      } else {
+      if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)rr3_box_safeguard_kernel<>, blds));
+      hipLaunchKernelGGL(rr3_box_safeguard_kernel<>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
                          (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap);
+      }
     }
   } else
   if (h->bounded) {
-    // input / output bounds: the instantiations that test the component table.  No law step filters their instances, and no
-    // fall-back kernel knows the bounds (an instance beyond RR3_KMAX active components ends in status 4 inside the kernel).
-    if (only != nullptr) return fail(DDMPC_ERR_UNSUPPORTED, "a bounded handle has no affine law beyond 271 rows");
+    // input / output bounds: the instantiations that test the component table.  No fall-back kernel knows the bounds (an
+    // instance beyond RR3_KMAX active components ends in status 4 inside the kernel).  DDMPC_OPT_LARGE_BOX_LAW: the filtered
+    // instantiations serve the instances the law step flagged.
     X.nbox = h->nbox3; X.ip = (const int*)h->d_r3bi.p; X.bd = (const double*)h->d_r3bd.p;
     blds = lds + (size_t)RR3_BOX_LDS * sizeof(double);
     if (blds > 64 * 1024) {
       HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<false>, blds));
       HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<true>, blds));
+      if (only != nullptr) {
+        HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<false, Rr3Only>, blds));
+        HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<true, Rr3Only>, blds));
+      }
     }
+    if (only != nullptr)
+      hipLaunchKernelGGL((rr3_solve_box_kernel<false, Rr3Only>), dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
+                         (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, flt);
+    else
     hipLaunchKernelGGL(rr3_solve_box_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
                        (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X);
   } else
@@ -1231,9 +1262,15 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     HankelLaunch hk;
     if ((rc = pick_hankel_launch(kq, &hk))) return rc;
     launch_hankel(hk, h->stream, (unsigned)B, H, kq, h->ud, h->yd, (int)R3_X, only_si != nullptr ? 1 : 0);
-    if (wide)
+    if (wide && only != nullptr)
+      hipLaunchKernelGGL((rr3_solve_box_wide_kernel<true, Rr3Only>), dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo,
+                         cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X, cap, flt);
+    else if (wide)
       hipLaunchKernelGGL(rr3_solve_box_wide_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
                          (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X, cap);
+    else if (h->bounded && only != nullptr)
+      hipLaunchKernelGGL((rr3_solve_box_kernel<true, Rr3Only>), dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
+                         (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X, flt);
     else if (h->bounded)
       hipLaunchKernelGGL(rr3_solve_box_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
                          (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X);
@@ -1352,6 +1389,31 @@ static int launch_rr3_law_step(ddmpc_handle* h, const double* up, const double* 
   return DDMPC_OK;
 }
 
+// DDMPC_OPT_LARGE_BOX_LAW (ddmpc_rr3_box_law.hpp): a control step of a bounded handle on that law -- one launch over the batch that
+// serves the instances whose beta violates no component of the box table, then the bounded solve on the kept factor (the launches
+// of the option 0) restricted to the instances the step left to it.  The solve launches are queued whatever the step found (no
+// read-back between them): their workgroups leave at once for a served instance, and rr3_box_keep_seed_kernel behind them reads
+// the empty set of a served instance like any other.
+static bool rr3_box_law(const ddmpc_handle* h) { return h->large_box_law != 0 && h->large && !h->large_nominal && h->bounded; }
+
+static int launch_rr3_law_box_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
+                                   int32_t* iters, bool seeded) {
+  const KParams& k = h->kp;
+  const size_t B = (size_t)h->batch;
+  Rr3 S;
+  int rc;
+  if ((rc = rr3_desc(h, k, &S))) return rc;
+  const int* nolaw = (const int*)h->d_r3flag.p;
+  int* need = (int*)h->d_r3flag.p + B;
+  int* si = (int*)h->d_r3flag.p + 3 * B;                   // [2 B]: need in the layout of Rr2Solve::si
+  Rr3Box X{};
+  X.nbox = h->nbox3; X.ip = (const int*)h->d_r3bi.p; X.bd = (const double*)h->d_r3bd.p;
+  hipLaunchKernelGGL(rr3_law_box_step_kernel, dim3((unsigned)B), dim3(RR2_TS), 0, h->stream, S, k, 16 * h->kc.NT, h->prm.n * k.nch,
+                     (const double*)h->d_gz.p, nolaw, up, yp, uo, cost, (int*)status, (int*)iters, (double*)h->d_beta.p,
+                     (signed char*)h->d_act.p, need, si, X, rr3_wide(h) ? h->large_box_cap : RR3_KMAX);
+  HIP_TRY(hipGetLastError());
+  return launch_rr3_solve(h, k, up, yp, uo, cost, status, iters, need, si, seeded);
+}
 
 // ROBUST controllers beyond the register-resident kernels (Route::RobustPhases, Route::RobustOneWg).
 static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const double* up, const double* yp, double* uo,
@@ -1362,6 +1424,7 @@ static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const 
     // active-set iterations on its trailing block
     if (stage != Stage::OnFactors && (rc = launch_rr3_factors(h))) return rc;
     if (stage == Stage::OnFactors && h->large_affine && h->prep.law) return launch_rr3_law_step(h, up, yp, uo, cost, status, iters);
+    if (stage == Stage::OnFactors && rr3_box_law(h) && h->prep.law) return launch_rr3_law_box_step(h, up, yp, uo, cost, status, iters, seeded);
     if (stage != Stage::Factors && (rc = launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters, nullptr, nullptr, seeded))) return rc;
     return DDMPC_OK;
   }
@@ -2414,7 +2477,7 @@ int ddmpc_prepare(ddmpc_handle* h) {
   if (route != Route::Cold && !box) {     // ROBUST at this size: Gram + lam D, the factor of the columns outside the slack box and
                                           // the Schur complement of the boxed block are formed once and kept
     int rc = launch_large_robust(h, route, Stage::Factors, h->ud, h->yd, nullptr, nullptr, nullptr, nullptr);
-    if (!rc && h->large_affine && route == Route::RobustPhases) rc = launch_rr3_law_build(h);   // ... and the affine law on that factor
+    if (!rc && (h->large_affine || rr3_box_law(h)) && route == Route::RobustPhases) rc = launch_rr3_law_build(h);   // ... and the affine law on that factor
     h->prep.valid = rc == DDMPC_OK;
     return rc;
   }
@@ -2434,7 +2497,7 @@ int ddmpc_step(ddmpc_handle* h, const double* u_past, const double* y_past, doub
 
 int ddmpc_get_gain(ddmpc_handle* h, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
-  if (h->large && !h->large_affine)
+  if (h->large && !h->large_affine && !(rr3_box_law(h) && select_route(h) == Route::RobustPhases))
     return fail(DDMPC_ERR_UNSUPPORTED, "no affine law at this problem size without DDMPC_OPT_LARGE_AFFINE_LAW");
   if (!prep_valid(h) || (h->large && !h->prep.law)) return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare must be called before ddmpc_get_gain");
   HIP_TRY(hipSetDevice(h->device));
@@ -2471,7 +2534,7 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
     case DDMPC_OPT_REFINE_MAX:
       if (value < 1 || value > 10) return fail(DDMPC_ERR_INVALID, "refinement passes must be within [1, 10]");
       h->kp.refine_max = value;
-      if (h->large_affine) forget_prep(h);        // the ROBUST law beyond 271 rows marks "no law" after refine_max passes
+      if (h->large_affine || h->large_box_law) forget_prep(h);   // the ROBUST law beyond 271 rows marks "no law" after refine_max passes
       return DDMPC_OK;
     case DDMPC_OPT_REFINE_RES_LOG10:
       if (value < 0 || value > 3000)
@@ -2554,6 +2617,17 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       h->large_box_warm = value;          // (with 1 the wide kernels serve a bounded handle beyond 271 rows at every capacity: the factors do not depend on it)
       h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
       h->last.large_seed = false;         // (setting it, to either value, drops the seed)
+      return DDMPC_OK;
+    case DDMPC_OPT_LARGE_BOX_LAW:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_LAW must be 0 or 1");
+      // (the law is built on the phase kernels and its step stages the window in LDS: a shape check, whatever the bounds)
+      if (value == 1 && h->large && h->prm.n * h->kp.nch > WARM_MAX_NF)
+        return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_LARGE_BOX_LAW: n*(m+p) = %d, the affine law beyond 271 rows supports n*(m+p) <= %d",
+                    h->prm.n * h->kp.nch, WARM_MAX_NF);
+      h->large_box_law = value;           // (ddmpc_prepare forms the law next to the factors: it is part of what is kept)
+      forget_prep(h);
+      h->last.valid = false;
+      h->last.large_seed = false;
       return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");

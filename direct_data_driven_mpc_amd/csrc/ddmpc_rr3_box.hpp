@@ -5,6 +5,7 @@
 // Everything else -- the factor of the empty active set, rr3_w_forward, rr3_w_gram, the k x k Cholesky, the substitutions, Rr3Lds --
 // is shared.
 #pragma once
+#include <type_traits>
 #include "ddmpc_rr3.hpp"
 
 namespace ddmpc {
@@ -24,6 +25,20 @@ struct Rr3Box {
   const double* bd;                                   // [a | c | lo | hi | 1/d | shlo | shhi] (nbox each), then the bounds per channel
 };
 enum : int { R3B_A = 0, R3B_C, R3B_LO, R3B_HI, R3B_INVD, R3B_SHLO, R3B_SHHI, R3B_NV };
+// DDMPC_OPT_LARGE_BOX_LAW: the instance filter of the bounded kernels (rr3_solve_box_kernel, rr3_solve_box_wide_kernel,
+// rr3_box_safeguard_kernel), a trailing argument of their filtered instantiations: a workgroup whose instance has only[b] == 0
+// leaves at once (the step on the law served it, ddmpc_rr3_box_law.hpp).  Without the argument a kernel is what it was.
+struct Rr3Only {
+  const int* only;
+};
+// A trailing argument pack of those kernels: does it hold a T, and that T.
+template <class T, class... A>
+inline constexpr bool rr3_has_arg = (std::is_same_v<T, A> || ...);
+template <class T, class A0, class... A>
+__device__ __forceinline__ T rr3_get_arg(A0 a0, A... a) {
+  if constexpr (std::is_same_v<T, A0>) return a0;
+  else return rr3_get_arg<T>(a...);
+}
 // What the bounded kernels keep in LDS behind Rr3Lds::total (doubles): the table indices of the active components (RR3_KMAX
 // ints) and their shifts (RR3_KMAX doubles).  Nothing else is indexed by component in LDS.
 constexpr int RR3_BOX_LDS = RR3_KMAX / 2 + RR3_KMAX;
@@ -102,15 +117,20 @@ __device__ __forceinline__ void rr3_box_outputs(const KParams& P, int RPs, const
 // shifts of the active components, ascending (two components of one row give two equal columns of W); the k x k system is
 // diag(1 / d_s) - W'W with each component's own d_s, its right-hand side takes the component's own shift.  More than RR3_KMAX
 // active components in an iteration, or a non-positive pivot of the k x k system: status 4 at that iteration.
+// Only...: empty (the kernel as it is launched without a filter) or one Rr3Only.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool REFINE_PASS>
+template <bool REFINE_PASS, class... Only>
 __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_kernel(Rr3 S, KParams P, int RPs, const double* __restrict__ u_past,
                                                                const double* __restrict__ y_past, double* __restrict__ u_opt,
                                                                double* __restrict__ cost, int* __restrict__ status, int* __restrict__ iters,
                                                                double* __restrict__ beta_ws, signed char* __restrict__ act_ws, int defer_outputs,
-                                                               Rr3Box X) {
+                                                               Rr3Box X, Only... only) {
+  static_assert(sizeof...(Only) == 0 || (sizeof...(Only) == 1 && rr3_has_arg<Rr3Only, Only...>), "one filter at most");
   extern __shared__ __attribute__((aligned(16))) double r3_lds[];
   const long long b = blockIdx.x;
+  if constexpr (sizeof...(Only) != 0) {
+    if (rr3_get_arg<Rr3Only>(only...).only[b] == 0) return;                 // (workgroup-uniform)
+  }
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int r = S.r, nA = S.nA, n0 = S.n0, m = P.m, p = P.p;
   const int n = P.npu / m;

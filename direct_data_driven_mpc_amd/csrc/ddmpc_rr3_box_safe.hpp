@@ -31,13 +31,20 @@ __host__ __device__ constexpr long long rr3s_extra(int cap, int nbox, int ldw) {
   return rr3w_tiles(cap) * 4096 + ((nbox + 15) & ~15) + 16ll * ldw;
 }
 
+// Only...: empty (the kernel as it is launched without a filter) or one Rr3Only (DDMPC_OPT_LARGE_BOX_LAW).
+template <class... Only>
 __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KParams P, int RPs, const double* __restrict__ u_past,
                                                                    const double* __restrict__ y_past, double* __restrict__ u_opt,
                                                                    double* __restrict__ cost, int* __restrict__ status,
                                                                    int* __restrict__ iters, double* __restrict__ beta_ws,
-                                                                   signed char* __restrict__ act_ws, int defer_outputs, Rr3Box X, int cap) {
+                                                                   signed char* __restrict__ act_ws, int defer_outputs, Rr3Box X, int cap,
+                                                                   Only... only) {
+  static_assert(sizeof...(Only) == 0 || (sizeof...(Only) == 1 && rr3_has_arg<Rr3Only, Only...>), "one filter at most");
   extern __shared__ __attribute__((aligned(16))) double r3_lds[];
   const long long b = blockIdx.x;
+  if constexpr (sizeof...(Only) != 0) {
+    if (rr3_get_arg<Rr3Only>(only...).only[b] == 0) return;                 // (workgroup-uniform)
+  }
   int* kq = S.kq + b * S.kstride;
   // (uniform) only an instance whose iteration reached max_iter without a stable set: a capacity or pivot failure ends below
   // max_iter (the cap test precedes the list build in the bounded kernels), a failed pivot of K0 has 0 iterations

@@ -248,6 +248,7 @@ struct Rr3Seed {
 // before the run in progress, so iter - run0 is that run's own count and iter every solve attempted, the empty set's once.
 // The record of a failed instance holds the count of its LAST run (kq[2] >= max_iter: that run ended at its own cap, what
 // rr3_box_safeguard_kernel asks), that of a finished one the whole count.
+// Behind the seed, or alone: one Rr3Only (DDMPC_OPT_LARGE_BOX_LAW, the instance filter; both launches).
 // ---------------------------------------------------------------------------------------------------------------
 template <bool REFINE_PASS, class... Seed>
 __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KParams P, int RPs, const double* __restrict__ u_past,
@@ -256,10 +257,14 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
                                                                     int* __restrict__ iters, double* __restrict__ beta_ws,
                                                                     signed char* __restrict__ act_ws, int defer_outputs, Rr3Box X, int cap,
                                                                     Seed... seed) {
-  static_assert(sizeof...(Seed) <= 1 && !(REFINE_PASS && sizeof...(Seed) != 0), "one seed, and for the solve launch only");
-  constexpr bool SEEDED = sizeof...(Seed) != 0;
+  constexpr bool SEEDED = rr3_has_arg<Rr3Seed, Seed...>, ONLY = rr3_has_arg<Rr3Only, Seed...>;
+  static_assert(sizeof...(Seed) == (SEEDED ? 1 : 0) + (ONLY ? 1 : 0) && !(REFINE_PASS && SEEDED),
+                "one seed (for the solve launch only) and one filter at most");
   extern __shared__ __attribute__((aligned(16))) double r3_lds[];
   const long long b = blockIdx.x;
+  if constexpr (ONLY) {
+    if (rr3_get_arg<Rr3Only>(seed...).only[b] == 0) return;                 // (workgroup-uniform)
+  }
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int r = S.r, nA = S.nA, n0 = S.n0, m = P.m, p = P.p;
   const int n = P.npu / m;
@@ -436,7 +441,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
           __syncthreads();
           if (flagw[0] == 0) break;
           if constexpr (SEEDED) {
-            const Rr3Seed sd = (seed, ...);
+            const Rr3Seed sd = rr3_get_arg<Rr3Seed>(seed...);
             if (iter - run0 >= P.max_iter) {
               if (phase != 1 || sd.safeguard) { st = 4; break; }       // (a seeded run at the cap with the safeguard on: left to it)
               --iter;                                                  // (the test that found the cap followed a solve already counted)

@@ -251,6 +251,8 @@ class DirectDataDrivenMPCController:
                 self._engine.set_large_box_safeguard(True)
             if getattr(self, "_large_box_warm_start", False):
                 self._engine.set_large_box_warm_start(True)
+            if getattr(self, "_large_box_law", False):
+                self._engine.set_large_box_law(True)
         if not hasattr(self, "problem") or self.problem is None:
             self.problem = _Problem(self)
 
@@ -395,6 +397,17 @@ class DirectDataDrivenMPCController:
         if self._engine is not None:
             self._engine.set_large_box_warm_start(bool(on))
         self._large_box_warm_start = bool(on)
+        if self._engine is not None:
+            self._cold_solved = False
+            self.problem.solve()
+
+    def set_large_box_law(self, on: bool) -> None:
+        """With bounds on a long horizon (beyond 271 rows): serve every later control step that stays inside the box from the
+        affine law of the empty active set, and solve only the others (`BatchedDDMPC.set_large_box_law`).  Remembered for a
+        rebuilt engine handle.  The problem is solved again, as after `set_input_bounds`."""
+        if self._engine is not None:
+            self._engine.set_large_box_law(bool(on))
+        self._large_box_law = bool(on)
         if self._engine is not None:
             self._cold_solved = False
             self.problem.solve()

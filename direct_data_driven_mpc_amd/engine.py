@@ -419,6 +419,17 @@ class BatchedDDMPC:
         CONVEX handle."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_BOX_WARM_START, 1 if on else 0))
 
+    def set_large_box_law(self, on: bool) -> None:
+        """Bounded handles beyond 271 rows: True = `prepare` also forms the affine law of the empty active set on the kept factor
+        ((n(m+p) + 1) r doubles per instance) and `step` (`solve(..., warm=True)`) and the per-step `closed_loop` serve every
+        instance whose law violates no component of the box from it in one launch (`iters` = 1; agrees with the solve to
+        rounding); every other instance of the batch is solved in the same call by the launches of False restricted to it and is
+        bit-equal to False (DDMPC_OPT_LARGE_BOX_LAW).  `gain()` returns the law after `prepare`.  Cold `solve`s never use the law.
+        Setting it (either value) forgets what `prepare` kept, the last solution and the seed of `set_large_box_warm_start`.
+        Raises beyond 271 rows when n(m+p) > 256.  False (default) = every step is the whole solve.  No effect up to 271 rows,
+        without finite bounds or on a slack-only CONVEX handle."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_BOX_LAW, 1 if on else 0))
+
     def get_solution(self, what: str) -> np.ndarray:
         """`.value` of alpha / ubar / ybar / sigma after the last solve (host array)."""
         sel = {"alpha": L.SOL_ALPHA, "ubar": L.SOL_UBAR, "ybar": L.SOL_YBAR, "sigma": L.SOL_SIGMA}[what]

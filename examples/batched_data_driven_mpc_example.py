@@ -58,6 +58,8 @@ def parse_args():
                     help="with bounds beyond 271 rows: finish solves that end at the iteration cap by a primal active-set method")
     ap.add_argument("--large_box_warm_start", action="store_true",
                     help="with bounds beyond 271 rows: start each step's active-set iteration from the previous solve's set")
+    ap.add_argument("--large_box_law", action="store_true",
+                    help="with bounds beyond 271 rows: serve the steps that stay inside the box from the affine law, solve only the others")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     return ap.parse_args()
 
@@ -116,6 +118,8 @@ def main():
         eng.set_large_box_safeguard(True)
     if a.large_box_warm_start:
         eng.set_large_box_warm_start(True)
+    if a.large_box_law:
+        eng.set_large_box_law(True)
     eng.set_data(data["u_d"], data["y_d"])
     up = data["u_d"][:, -n:, :].reshape(B, -1)                                   # controller.py:184-185
     yp = data["y_d"][:, -n:, :].reshape(B, -1)

@@ -265,6 +265,32 @@ extern "C" {
                                          effect up to 271 rows (DDMPC_OPT_BOX_WARM_START is the option of that size and has no
                                          effect here), without finite bounds, off the phase kernels, and on a slack-only CONVEX
                                          handle (it keeps rr3_solve_kernel) */
+#define DDMPC_OPT_LARGE_BOX_LAW 17       /* bounded handles beyond 271 rows (DDMPC_OPT_LARGE_BOUNDS): 1 = ddmpc_prepare also forms the
+                                         affine law of the EMPTY active set on the kept factor (beta = g0 + G' w; the kernels,
+                                         refinement under DDMPC_OPT_REFINE and "no law" marking after DDMPC_OPT_REFINE_MAX passes of
+                                         DDMPC_OPT_LARGE_AFFINE_LAW; (n(m+p) + 1) r doubles per instance, an allocation failure is
+                                         DDMPC_ERR_HIP), and ddmpc_step and the per-step ddmpc_closed_loop (DDMPC_PATH_AUTO / _WARM)
+                                         run one launch on that law first.  An instance that has a law and whose beta violates no
+                                         component of the box table -- hat = a + c beta strictly above hi or strictly below lo; slack,
+                                         input and output components alike, the first test of the bounded kernels -- is served by
+                                         that launch: status 0, `iters` = 1, u_opt, cost, the empty active set in the workspace
+                                         (ddmpc_get_solution and ddmpc_debug_workspace read it like any other step) and, under
+                                         DDMPC_OPT_LARGE_BOX_WARM_START, an empty seed.  Such a result agrees with the option 0 to
+                                         rounding (1e-9 relative: the law is not the solve).  Every other instance (a violation, or
+                                         no law) is solved in the same call by exactly the launches of the option 0 restricted to
+                                         it -- at the handle's capacity, seeded, with the safeguard and the refinement launch as set
+                                         -- and is bit-equal to the option 0 in u_opt, cost, status, iters, the solution and the
+                                         seed it leaves.  ddmpc_solve and DDMPC_PATH_COLD keep the cold contract and never use the
+                                         law.  ddmpc_get_gain returns the law on such a handle (the layout of a ROBUST gain: beta of
+                                         the empty active set in component order; DDMPC_ERR_NOT_READY before ddmpc_prepare).
+                                         0 (default) = every step is the whole solve, the kernels as they were.  Values other than
+                                         0 / 1: DDMPC_ERR_INVALID; 1 beyond 271 rows with n(m+p) > 256: DDMPC_ERR_UNSUPPORTED.
+                                         Setting it, to either value, forgets what ddmpc_prepare kept (the law is part of it), the
+                                         last solution and the seed; with 1, DDMPC_OPT_REFINE_MAX forgets the preparation too.
+                                         Accepted on any other handle; no effect up to 271 rows (such a handle is always on the
+                                         law), without finite bounds, off the phase kernels, and on a slack-only CONVEX handle (it
+                                         keeps rr3_solve_kernel: DDMPC_OPT_LARGE_AFFINE_LAW is its option, and stays refused with
+                                         bounds) */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -442,7 +468,12 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s);
  *   DDMPC_OPT_BOX_WARM_START is accepted and has no effect beyond 271 rows; the warm start of this size is an option of its own,
  *     DDMPC_OPT_LARGE_BOX_WARM_START = 1: ddmpc_step and the per-step ddmpc_closed_loop start the iteration from the signed set
  *     the last solve ended with; a seeded run that fails starts again from the empty set, ddmpc_solve keeps the cold contract
- *     and leaves a seed (see the option for what drops the seed and how `iters` counts). */
+ *     and leaves a seed (see the option for what drops the seed and how `iters` counts).
+ *   DDMPC_OPT_LARGE_BOX_LAW = 1 gives this size a law after all, for the steps that stay inside the box: ddmpc_prepare forms the
+ *     law of the empty active set next to the factors ((n(m+p) + 1) r doubles per instance: 40 KB at the four-tank L = 70,
+ *     627 KB at 608 rows with n(m+p) = 128), a step whose beta violates no component of the box table is served by one launch
+ *     on it (`iters` = 1, agreeing with the solve to rounding), and every other instance of the batch is solved in the same call
+ *     by the launches above restricted to it, bit-equal to the option 0.  ddmpc_solve keeps the cold contract. */
 int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max);
 
 /* Box on the predicted outputs: y_min[ch] <= ybar[k][ch] <= y_max[ch] on every FREE prediction step (the rows that carry Q;
