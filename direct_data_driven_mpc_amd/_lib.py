@@ -35,6 +35,7 @@ OPT_LARGE_BOX_SAFEGUARD = 14
 OPT_BOX_WARM_START = 15
 OPT_LARGE_BOX_WARM_START = 16
 OPT_LARGE_BOX_LAW = 17
+OPT_SETPOINT_LAW = 18
 PIPELINE_ONE_WORKGROUP, PIPELINE_PHASES = 0, 1
 REFINE_OFF, REFINE_AUTO, REFINE_ALWAYS = 0, 1, 2
 PATH_AUTO, PATH_COLD, PATH_WARM = 0, 1, 2
@@ -47,6 +48,7 @@ EXPORTS = (
     "ddmpc_closed_loop", "ddmpc_prepare", "ddmpc_step", "ddmpc_get_gain", "ddmpc_set_option",
     "ddmpc_pe_guard", "ddmpc_solve_from_host", "ddmpc_debug_workspace", "ddmpc_debug_poison_allocations",
     "ddmpc_closed_loop_kernel_name", "ddmpc_set_input_bounds", "ddmpc_set_output_bounds", "ddmpc_debug_large_box_order",
+    "ddmpc_step_setpoints", "ddmpc_closed_loop_setpoints", "ddmpc_get_setpoint_gain",
 )
 
 c_double_p = C.POINTER(C.c_double)
@@ -117,6 +119,12 @@ def load() -> C.CDLL:
     lib.ddmpc_debug_stamps.restype = C.c_int
     lib.ddmpc_closed_loop.argtypes = [vp, C.POINTER(Plant), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     lib.ddmpc_closed_loop.restype = C.c_int
+    lib.ddmpc_closed_loop_setpoints.argtypes = [vp, C.POINTER(Plant), C.c_int32, C.c_int32] + [vp] * 9 + [C.c_int]
+    lib.ddmpc_closed_loop_setpoints.restype = C.c_int
+    lib.ddmpc_step_setpoints.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32p, i32p, C.c_int]
+    lib.ddmpc_step_setpoints.restype = C.c_int
+    lib.ddmpc_get_setpoint_gain.argtypes = [vp, vp, C.c_int]
+    lib.ddmpc_get_setpoint_gain.restype = C.c_int
     lib.ddmpc_prepare.argtypes = [vp]
     lib.ddmpc_step.argtypes = [vp, vp, vp, vp, vp, i32p, i32p, C.c_int]
     lib.ddmpc_get_gain.argtypes = [vp, vp, C.c_int]

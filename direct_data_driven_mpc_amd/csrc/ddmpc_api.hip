@@ -1,4 +1,4 @@
-// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp, ddmpc_rr3_box.hpp).
+// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_setpoint_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp, ddmpc_rr3_box.hpp).
 // Host-side responsibilities: parameter validation with the reference's error
 // conditions (direct_data_driven_mpc_controller.py:165-168,211-222,298-343,664-670),
 // device buffer ownership, kernel-instance selection, launch.
@@ -8,6 +8,7 @@
 #include "ddmpc_rr3_box_wide.hpp"
 #include "ddmpc_rr3_box_safe.hpp"
 #include "ddmpc_box_law.hpp"
+#include "ddmpc_setpoint_law.hpp"
 #include "../../include/ddmpc.h"
 
 #include <cmath>
@@ -202,6 +203,7 @@ struct LastSolve {
   int box_cap = RR3_KMAX;                  // Route::RobustPhases: columns of W of the kernel that wrote the per-instance record (its layout)
   bool box_seed = false;                   // Route::BoxLaw, DDMPC_OPT_BOX_WARM_START: d_box_seed holds the signed set that solve ended with
   bool large_seed = false;                 // Route::RobustPhases, DDMPC_OPT_LARGE_BOX_WARM_START: d_large_seed holds the set that solve ended with
+  bool setpoint_call = false;              // not valid because ddmpc_step_setpoints / ddmpc_closed_loop_setpoints ran last (the message of ddmpc_get_solution)
 };
 
 // What ddmpc_prepare kept; it serves the route it was formed on only (prep_valid).
@@ -215,6 +217,7 @@ struct Prep {
   int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch;
                                            //     BoxLaw: they iterate like the others and report optimal_inaccurate with a non-empty active set)
   int epoch = 0;                           // stamp of the flags recorded by the factor-export launch (AUTO)
+  bool setpoint = false;                   // DDMPC_OPT_SETPOINT_LAW: S was formed next to the law (d_sgain)
 };
 
 struct ddmpc_handle {
@@ -289,6 +292,10 @@ struct ddmpc_handle {
   int large_box_warm = 0;                  // DDMPC_OPT_LARGE_BOX_WARM_START: steps of a bounded handle beyond 271 rows start from the last solve's set
   DevBuf d_large_seed;                     // ... that set, sa + 4 say per row, [batch][rE] (rr3_box_keep_seed_kernel)
   int large_box_law = 0;                   // DDMPC_OPT_LARGE_BOX_LAW: steps of a bounded handle beyond 271 rows on the affine law while inside the box
+  int setpoint_law = 0;                    // DDMPC_OPT_SETPOINT_LAW: ddmpc_prepare also forms S = K0^-1 [1_c] (ddmpc_setpoint_law.hpp)
+  DevBuf d_sgain, d_sptab;                 // ... S [batch][m+p][r]; the m + p table copies with a unit setpoint (refined columns)
+  DevBuf d_sp, d_uref, d_yref;             // ... staging of host setpoints [u_s | y_s] (ddmpc_step_setpoints) and schedules (ddmpc_closed_loop_setpoints)
+  const double *sp_us = nullptr, *sp_ys = nullptr;   // ... the device setpoints of the ddmpc_step_setpoints call in progress
   // input bounds (ddmpc_set_input_bounds) and output bounds (ddmpc_set_output_bounds): per channel, +-infinity = none; the
   // vectors are empty without a finite bound of their kind; `bounded` = some bound of either kind is finite (Route::BoxLaw)
   std::vector<double> umin_h, umax_h, ymin_h, ymax_h;
@@ -2386,6 +2393,68 @@ static int prep_refine_columns(ddmpc_handle* h, const KParams& k0) {
   return DDMPC_OK;
 }
 
+// DDMPC_OPT_SETPOINT_LAW: S = K0^-1 [1_0 .. 1_{m+p-1}] by substitutions through the exported factor (queued behind enqueue_gain,
+// while d_lfac / d_lfacT are alive).
+static int enqueue_setpoint_gain(ddmpc_handle* h) {
+  const int NT = h->kc.NT;
+  bool launched = false;
+#define DDMPC_INSTANCE(NT_, W_)                                                                              \
+  if (!launched && NT == NT_) {                                                                               \
+    const size_t glds = (size_t)(2 * NT_ * 256 + 32) * sizeof(double);                                        \
+    if (glds > 64 * 1024)                                                                                     \
+      HIP_TRY(raise_lds_limit((const void*)ddmpc_setpoint_gain_kernel<NT_>, glds));                           \
+    hipLaunchKernelGGL(ddmpc_setpoint_gain_kernel<NT_>, dim3((unsigned)h->batch), dim3(256), glds, h->stream, h->kp, 16 * NT, \
+                       (const double*)h->d_lfac.p, (const double*)h->d_lfacT.p, (double*)h->d_sgain.p);      \
+    launched = true;                                                                                          \
+  }
+#include "ddmpc_instances.inc"
+#undef DDMPC_INSTANCE
+  if (!launched) return fail(DDMPC_ERR_UNSUPPORTED, "no setpoint gain kernel for %d tile rows", NT);
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
+// ... and, like the columns of the law (prep_refine_columns: same launches, same flag filter), replaced by refining cold solves:
+// column c is the beta of a solve at the zero past window whose KParams copy points `tabd` at a scratch copy of the tables with
+// the unit setpoint e_c in row 2 -- its right-hand side is 1_c, so there is no offset to subtract.  The handle's tables are
+// only read.  m + p launches of the refining kernel variant, once per data set.
+static int prep_refine_setpoint_columns(ddmpc_handle* h, const KParams& k0) {
+  const ddmpc_params& p = h->prm;
+  const KParams& k = h->kp;
+  const size_t B = (size_t)h->batch;
+  const int RP = 16 * h->kc.NT, nch = k.nch;
+  const bool flagged_only = k.refine == DDMPC_REFINE_AUTO;
+  const int npu = p.n * p.m, npy = p.n * p.p;
+  if (int rc = h->d_sptab.ensure((size_t)nch * 4 * RP * sizeof(double))) return rc;
+  double* pu = (double*)h->d_zero.p;               // (prep_refine_columns left a unit window there)
+  double* py = pu + B * (size_t)npu;
+  const unsigned gp = (unsigned)((B * (size_t)(npu + npy) + 255) / 256), gg = (unsigned)((B * (size_t)k.r + 255) / 256);
+  hipLaunchKernelGGL(ddmpc_unit_past_kernel, dim3(gp), dim3(256), 0, h->stream, (long long)B, npu, npy, -1, pu, py);
+  hipLaunchKernelGGL(ddmpc_setpoint_tables_kernel, dim3((unsigned)((nch * 4 * RP + 255) / 256)), dim3(256), 0, h->stream, RP, nch,
+                     k.tabd, (double*)h->d_sptab.p);
+  KParams kr = k0;
+  kr.refine = DDMPC_REFINE_ALWAYS;
+  ColdSeq sr; sr.kp = &kr;
+  ColdArgs a{h->ud, h->yd, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p};
+  a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p;
+  for (int c = 0; c < nch; ++c) {
+    kr.tabd = (const double*)h->d_sptab.p + (size_t)c * 4 * RP;
+    if (!flagged_only) {
+      if (int rc = launch_cold(h, pu, py, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_prep_status.p, nullptr, sr))
+        return rc;
+    } else {
+      kr.epoch = h->prep.epoch;
+      if (int rc = gram_pre_launch(h, kr, h->ud, h->yd, B, 0, true)) return rc;
+      enqueue_cold(h, ColdPass::Filtered, kr, a, B);
+    }
+    hipLaunchKernelGGL(ddmpc_setpoint_gain_column_kernel, dim3(gg), dim3(256), 0, h->stream, (long long)B, k.r, k.rE, nch, c,
+                       (const double*)h->d_beta.p, (double*)h->d_sgain.p,
+                       flagged_only ? (const int*)h->d_rflag.p : (const int*)nullptr, h->prep.epoch);
+  }
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
 // Factor export, AUTO probe, box list, gain launch, refined columns, refined-instance mark and its count, in this order.
 static int prepare_register_resident(ddmpc_handle* h, bool box) {
   const ddmpc_params& p = h->prm;
@@ -2435,7 +2504,13 @@ static int prepare_register_resident(ddmpc_handle* h, bool box) {
   }
   h->prep.cwl_nbox = nbox;
   if ((rc = enqueue_gain(h, nf, ncol, col_rho ? col_rho : (const int*)h->d_cwl_tab.p))) return rc;
+  const bool setpoint = h->setpoint_law != 0;     // DDMPC_OPT_SETPOINT_LAW (ROBUST, no box: refinable, no box list)
+  if (setpoint && ((rc = h->d_sgain.ensure(B * (size_t)k.nch * k.r * sizeof(double))) || (rc = enqueue_setpoint_gain(h)))) return rc;
   if (refinable && (k.refine == DDMPC_REFINE_ALWAYS || k.refine == DDMPC_REFINE_AUTO) && (rc = prep_refine_columns(h, k0))) return rc;
+  if (setpoint && refinable && (k.refine == DDMPC_REFINE_ALWAYS || k.refine == DDMPC_REFINE_AUTO) &&
+      (rc = prep_refine_setpoint_columns(h, k0)))
+    return rc;
+  h->prep.setpoint = setpoint;
   if (cwl) {
     // M comes from the unrefined factor: instances whose law was refined keep the filtered cold launch for their box
     // (ddmpc_step), and their presence sends ddmpc_closed_loop to the per-step path
@@ -2506,6 +2581,55 @@ int ddmpc_get_gain(ddmpc_handle* h, double* out, int mem) {
   const size_t bytes = (size_t)h->batch * (h->prm.n * h->kp.nch + 1) * h->kp.r * sizeof(double);
   HIP_TRY(hipMemcpyAsync(out, h->large ? h->d_gz.p : h->d_gain.p, bytes, mem == DDMPC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                          h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return DDMPC_OK;
+}
+
+// DDMPC_OPT_SETPOINT_LAW: one evaluation of the law and S with the setpoints of the call in progress (h->sp_us / h->sp_ys).
+static int setpoint_step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
+                                  int32_t* iters) {
+  begin_solve(h, Route::Cold);
+  hipLaunchKernelGGL(ddmpc_setpoint_step_kernel, dim3((unsigned)h->batch), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
+                     16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const double*)h->d_sgain.p,
+                     (const int*)h->d_prep_status.p, up, yp, h->sp_us, h->sp_ys, uo, cost, (int*)status, (int*)iters);
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
+int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_past, const double* u_s, const double* y_s,
+                         double* u_opt, double* cost, int32_t* status, int32_t* iters, int mem) {
+  if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
+  if (!h->setpoint_law) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1");
+  if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_step_setpoints");
+  if (!u_s || !y_s) return fail(DDMPC_ERR_INVALID, "null argument");
+  if (mem != DDMPC_MEM_HOST && mem != DDMPC_MEM_DEVICE) return fail(DDMPC_ERR_INVALID, "mem must be DDMPC_MEM_HOST or DDMPC_MEM_DEVICE");
+  if (!prep_valid(h))
+    if (int rc = ddmpc_prepare(h)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  h->sp_us = u_s; h->sp_ys = y_s;
+  if (mem == DDMPC_MEM_HOST) {
+    const size_t B = (size_t)h->batch, nu = B * h->prm.m, ny = B * h->prm.p;
+    if (int rc = h->d_sp.ensure((nu + ny) * sizeof(double))) return rc;
+    double* d = (double*)h->d_sp.p;
+    HIP_TRY(hipMemcpyAsync(d, u_s, nu * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d + nu, y_s, ny * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h->sp_us = d; h->sp_ys = d + nu;
+  }
+  const int rc = solve_impl(h, u_past, y_past, u_opt, cost, status, iters, mem, &setpoint_step_on_route);
+  h->last = LastSolve{};               // nothing ddmpc_get_solution could reconstruct: its kernel reads the shared setpoint table
+  h->last.setpoint_call = true;
+  h->sp_us = h->sp_ys = nullptr;
+  return rc;
+}
+
+int ddmpc_get_setpoint_gain(ddmpc_handle* h, double* out, int mem) {
+  if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
+  if (!h->setpoint_law) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_get_setpoint_gain needs DDMPC_OPT_SETPOINT_LAW = 1");
+  if (!prep_valid(h) || !h->prep.setpoint)
+    return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare with DDMPC_OPT_SETPOINT_LAW = 1 must be called before ddmpc_get_setpoint_gain");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t bytes = (size_t)h->batch * h->kp.nch * h->kp.r * sizeof(double);
+  HIP_TRY(hipMemcpyAsync(out, h->d_sgain.p, bytes, mem == DDMPC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return DDMPC_OK;
 }
@@ -2629,6 +2753,29 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       h->last.valid = false;
       h->last.large_seed = false;
       return DDMPC_OK;
+    case DDMPC_OPT_SETPOINT_LAW:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_SETPOINT_LAW must be 0 or 1");
+      if (value == 1) {
+        const char* pre = "DDMPC_OPT_SETPOINT_LAW";
+        if (h->prm.controller_type != DDMPC_ROBUST)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: ROBUST controllers only (a NOMINAL one fixes its outputs to the setpoint as hard rows)", pre);
+        if (h->kp.convex)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: not with the CONVEX slack box (slack NONE only: the setpoint step runs no active-set iteration)", pre);
+        if (h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)", pre);
+        if (h->prm.n * h->kp.nch > WARM_MAX_NF)     // (asked before the row count: L >= 2 n puts every such ROBUST handle beyond 271 rows)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: n*(m+p) = %d, the affine law of ddmpc_prepare holds %d", pre, h->prm.n * h->kp.nch, WARM_MAX_NF);
+        if (h->large)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels)", pre, h->kp.r);
+        if (h->long_data)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: N = %d, the trajectory does not fit the LDS of the cold kernel (no refined columns there)", pre,
+                      h->prm.N);
+        if (h->bounded)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s is not available on a handle with input or output bounds (the setpoint step knows no bounds)", pre);
+      }
+      if (h->setpoint_law != value) forget_prep(h);     // (S is part of what ddmpc_prepare keeps)
+      h->setpoint_law = value;
+      return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
       if (value == 1 && !h->gram_valu_ok) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_gram_tiles_kernel stages the whole trajectory in LDS: not at this shape");
@@ -2697,6 +2844,8 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
   }
   if (any) {
     if (const char* msg = setpoint_outside_bounds(h, h->us_h.data(), u_min, u_max)) return fail(DDMPC_ERR_INVALID, "u_min / u_max: %s", msg);
+    if (h->setpoint_law)
+      return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: not with DDMPC_OPT_SETPOINT_LAW = 1 (the setpoint step knows no bounds)");
     if (p.controller_type != DDMPC_ROBUST)
       return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: ROBUST controllers only (a NOMINAL one has no regularised reduced system to iterate on)");
     if (p.weight_kind == DDMPC_WEIGHT_DENSE)
@@ -2764,6 +2913,8 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
   }
   if (any) {
     if (const char* msg = output_setpoint_outside_bounds(h, h->ys_h.data(), y_min, y_max)) return fail(DDMPC_ERR_INVALID, "y_min / y_max: %s", msg);
+    if (h->setpoint_law)
+      return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: not with DDMPC_OPT_SETPOINT_LAW = 1 (the setpoint step knows no bounds)");
     if (p.controller_type != DDMPC_ROBUST)
       return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: ROBUST controllers only (a NOMINAL one has no regularised reduced system to iterate on)");
     if (p.weight_kind == DDMPC_WEIGHT_DENSE)
@@ -2836,6 +2987,9 @@ int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s) {
 int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
   LastSolve& l = h->last;
+  if (!l.valid && l.setpoint_call)      // (ddmpc_reconstruct_kernel reads the shared setpoint table: it cannot rebuild that solve)
+    return fail(DDMPC_ERR_NOT_READY, "no solution to read after ddmpc_step_setpoints / ddmpc_closed_loop_setpoints: the reconstruction knows "
+                "the handle's shared setpoints only (a ddmpc_solve or ddmpc_step makes it readable again)");
   if (!l.valid) return fail(DDMPC_ERR_NOT_READY, "no solve to read a solution from");
   const KParams& k = h->kp;
   size_t per = 0;
@@ -3182,12 +3336,46 @@ static int copy_loop_outputs(ddmpc_handle* h, int mem, const LoopBytes& nb, cons
   return DDMPC_OK;
 }
 
+// DDMPC_OPT_SETPOINT_LAW: the fused loop with a setpoint schedule (a.ns .. a.stacc as for the other fused loops; u_ref / y_ref on
+// the device).  The loop's last solve leaves nothing ddmpc_get_solution could reconstruct.
+static int launch_setpoint_loop(ddmpc_handle* h, const LoopArgs& a, const double* u_ref, const double* y_ref) {
+  begin_solve(h, Route::Cold);
+  hipLaunchKernelGGL(ddmpc_closed_loop_setpoint_kernel, dim3((unsigned)h->batch), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
+                     16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const double*)h->d_sgain.p,
+                     (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps, a.n_mpc_step, a.x, a.up, a.yp, a.w, u_ref, y_ref, a.usys,
+                     a.ysys, a.stacc);
+  HIP_TRY(hipGetLastError());
+  h->last.setpoint_call = true;
+  return DDMPC_OK;
+}
+
+// ddmpc_closed_loop (u_ref = y_ref = null) and ddmpc_closed_loop_setpoints (`what` names the call in messages).
+static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant* plant, int32_t n_steps, int32_t n_mpc_step,
+                            double* x, double* u_past, double* y_past, const double* w, const double* u_ref, const double* y_ref,
+                            double* u_sys, double* y_sys, int32_t* status, int mem);
+
 int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps, int32_t n_mpc_step, double* x,
                       double* u_past, double* y_past, const double* w, double* u_sys, double* y_sys,
                       int32_t* status, int mem) {
+  return closed_loop_impl(h, "ddmpc_closed_loop", plant, n_steps, n_mpc_step, x, u_past, y_past, w, nullptr, nullptr, u_sys, y_sys,
+                          status, mem);
+}
+
+int ddmpc_closed_loop_setpoints(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps, int32_t n_mpc_step, double* x,
+                                double* u_past, double* y_past, const double* w, const double* u_ref, const double* y_ref,
+                                double* u_sys, double* y_sys, int32_t* status, int mem) {
+  if (!h || !u_ref || !y_ref) return fail(DDMPC_ERR_INVALID, "null argument");
+  if (!h->setpoint_law) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1");
+  return closed_loop_impl(h, "ddmpc_closed_loop_setpoints", plant, n_steps, n_mpc_step, x, u_past, y_past, w, u_ref, y_ref, u_sys,
+                          y_sys, status, mem);
+}
+
+static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant* plant, int32_t n_steps, int32_t n_mpc_step,
+                            double* x, double* u_past, double* y_past, const double* w, const double* u_ref, const double* y_ref,
+                            double* u_sys, double* y_sys, int32_t* status, int mem) {
   if (!h || !plant || !x || !u_past || !y_past || !w || !u_sys || !y_sys || !status)
     return fail(DDMPC_ERR_INVALID, "null argument");
-  if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_closed_loop");
+  if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before %s", what);
   if (!prep_valid(h)) h->gpre_valid = false;    // (borrowed device data may have changed since the last solve; a kept law pins it)
   if (n_steps <= 0 || n_mpc_step <= 0) return fail(DDMPC_ERR_INVALID, "n_steps and n_mpc_step must be positive");
   const ddmpc_params& p = h->prm;
@@ -3222,6 +3410,21 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
   // the plant steps that follow it move u_past / y_past on, so that window is kept apart
   if ((rc = h->d_lwup.ensure(nb.up)) || (rc = h->d_lwyp.ensure(nb.yp))) return rc;
   a.lwup = (double*)h->d_lwup.p; a.lwyp = (double*)h->d_lwyp.p;
+  if (u_ref) {
+    // DDMPC_OPT_SETPOINT_LAW: one fused launch, no per-step fall-back (DDMPC_OPT_CLOSED_LOOP_PATH / _GRAPH are not looked at)
+    if ((size_t)n_mpc_step * m > (size_t)WARM_MAX_NF)
+      return fail(DDMPC_ERR_UNSUPPORTED, "%s: n_mpc_step * m = %d, the fused loop holds %d inputs per solve", what, n_mpc_step * m, WARM_MAX_NF);
+    if (mem == DDMPC_MEM_HOST) {     // the schedules are [batch, n_steps, m] and [batch, n_steps, p]: the sizes of u_sys and y_sys
+      if ((rc = h->d_uref.ensure(nb.us)) || (rc = h->d_yref.ensure(nb.w))) return rc;
+      HIP_TRY(hipMemcpyAsync(h->d_uref.p, u_ref, nb.us, hipMemcpyHostToDevice, h->stream));
+      HIP_TRY(hipMemcpyAsync(h->d_yref.p, y_ref, nb.w, hipMemcpyHostToDevice, h->stream));
+      u_ref = (const double*)h->d_uref.p; y_ref = (const double*)h->d_yref.p;
+    }
+    if (!prep_valid(h) && (rc = ddmpc_prepare(h))) return rc;
+    h->loop_kernel = "ddmpc_closed_loop_setpoint_kernel";
+    if ((rc = launch_setpoint_loop(h, a, u_ref, y_ref))) return rc;
+    return copy_loop_outputs(h, mem, nb, a, user, status);
+  }
   LoopPath path;
   if ((rc = select_loop_path(h, n_mpc_step, &path))) return rc;
   h->loop_kernel = kLoopKernel[(int)path];

@@ -161,6 +161,10 @@ class BatchedDDMPC:
         warm=False: cold solve (Hankel -> Gram -> KKT -> Cholesky -> solve), `ddmpc_solve`.
         warm=True : `ddmpc_step`, the affine law prepared once per data set; with slack CONVEX the instances
                     whose affine iterate leaves the slack box are re-solved cold inside the same call."""
+        return self._solve(u_past, y_past, u_opt, cost, status, iters, warm, None)
+
+    def _solve(self, u_past, y_past, u_opt, cost, status, iters, warm, setpoints):
+        """`solve` / `step` (setpoints None) and `step_setpoints` (setpoints = (u_s [batch,m], y_s [batch,p]))."""
         B = self.batch
         dev = _is_torch(u_past)
         if u_opt is None:
@@ -185,10 +189,19 @@ class BatchedDDMPC:
             p6, m6, k6 = self._ptr(iters, (B,), "iters", dtype=np.int32, writable=True)
         else:
             p6, m6, k6 = C.c_void_p(), m1, None
-        if len({m1, m2, m3, m4, m5, m6}) != 1:
+        mems = {m1, m2, m3, m4, m5, m6}
+        if setpoints is not None:
+            p7, m7, k7 = self._ptr(setpoints[0], (B, self.m), "u_s")
+            p8, m8, k8 = self._ptr(setpoints[1], (B, self.p), "y_s")
+            mems |= {m7, m8}
+        if len(mems) != 1:
             raise ValueError("all solve buffers must live in the same memory space")
         if m1 == L.MEM_DEVICE:
             self._use_torch_stream()
+        if setpoints is not None:
+            L.check(self._lib.ddmpc_step_setpoints(self._h, p1, p2, p7, p8, p3, p4, p5, p6, m1))
+            self._keep["solve"] = (k1, k2, k3, k4, k5, k6, k7, k8)
+            return u_opt, cost, status, iters
         fn = self._lib.ddmpc_step if warm else self._lib.ddmpc_solve
         L.check(fn(self._h, p1, p2, p3, p4, p5, p6, m1))
         self._keep["solve"] = (k1, k2, k3, k4, k5, k6)
@@ -278,7 +291,33 @@ class BatchedDDMPC:
         Dense weights, more than 1024 rows or n(m+p) > 256 raise ERR_UNSUPPORTED."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_AFFINE_LAW, 1 if on else 0))
 
-    def closed_loop(self, A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step: int = 1):
+    def set_setpoint_law(self, on: bool) -> None:
+        """ROBUST controllers up to 271 rows, slack NONE, scalar / diagonal weights, no bounds: True = `prepare` also forms
+        S = K0^-1 [1_c], (m+p) r doubles per instance, which makes the setpoint an argument of the step: `step_setpoints`,
+        `closed_loop_setpoints`, `setpoint_gain` (DDMPC_OPT_SETPOINT_LAW).  `solve`, `step`, `closed_loop`, `gain` and
+        `get_solution` stay bit-equal to False (default).  Changing the value forgets what `prepare` kept.  Raises
+        ERR_UNSUPPORTED on NOMINAL controllers, the CONVEX slack box, dense weights, more than 271 rows, a trajectory beyond
+        the LDS, n(m+p) > 256 and a handle with bounds."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_SETPOINT_LAW, 1 if on else 0))
+
+    def step_setpoints(self, u_past, y_past, u_s, y_s, u_opt=None, cost=None, status=None, iters=None):
+        """Warm control step with one setpoint per instance (`ddmpc_step_setpoints`): u_s [batch,m], y_s [batch,p], in the
+        memory space of the windows; same outputs and array / tensor handling as `solve`.  The handle's own setpoints are not
+        read; `get_solution` is not available after it (until the next `solve` / `step`).  Needs `set_setpoint_law(True)`."""
+        return self._solve(u_past, y_past, u_opt, cost, status, iters, True, (u_s, y_s))
+
+    def setpoint_gain(self) -> np.ndarray:
+        """S of the prepared law: [batch, m+p, r], beta = gain[:,1:]^T [u_past; y_past] + S^T [u_s; y_s] (component order)."""
+        out = np.empty((self.batch, self.m + self.p, (self.m + self.p) * (self.L + self.n)))
+        L.check(self._lib.ddmpc_get_setpoint_gain(self._h, C.c_void_p(out.ctypes.data), L.MEM_HOST))
+        return out
+
+    def closed_loop_setpoints(self, A, B, Cm, D, x0, u_past, y_past, w, u_ref, y_ref, n_mpc_step: int = 1):
+        """`closed_loop` with a setpoint schedule per instance (`ddmpc_closed_loop_setpoints`, one fused launch): u_ref
+        [batch,n_steps,m], y_ref [batch,n_steps,p]; the solve made at step t tracks row t.  Needs `set_setpoint_law(True)`."""
+        return self.closed_loop(A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step, _ref=(u_ref, y_ref))
+
+    def closed_loop(self, A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step: int = 1, _ref=None):
         """Batched closed loop on the device (controller_operation.py:259-305 for every instance).
 
         A,B,Cm,D: plant matrices; x0 [batch,ns]; u_past [batch,n*m], y_past [batch,n*p];
@@ -301,6 +340,13 @@ class BatchedDDMPC:
         pl = L.Plant(ns, A.ctypes.data_as(L.c_double_p), Bm.ctypes.data_as(L.c_double_p),
                      Cm.ctypes.data_as(L.c_double_p), D.ctypes.data_as(L.c_double_p))
         vp = lambda a: C.c_void_p(a.ctypes.data)
+        if _ref is not None:
+            ur = np.ascontiguousarray(_ref[0], dtype=np.float64); yr = np.ascontiguousarray(_ref[1], dtype=np.float64)
+            if ur.shape != (self.batch, n_steps, self.m) or yr.shape != (self.batch, n_steps, self.p):
+                raise ValueError("u_ref / y_ref must have shape [batch, n_steps, m] / [batch, n_steps, p]")
+            L.check(self._lib.ddmpc_closed_loop_setpoints(self._h, C.byref(pl), n_steps, int(n_mpc_step), vp(x), vp(up), vp(yp),
+                                                          vp(w), vp(ur), vp(yr), vp(u_sys), vp(y_sys), vp(status), L.MEM_HOST))
+            return u_sys, y_sys, status, x, up, yp
         L.check(self._lib.ddmpc_closed_loop(self._h, C.byref(pl), n_steps, int(n_mpc_step), vp(x), vp(up), vp(yp), vp(w),
                                             vp(u_sys), vp(y_sys), vp(status), L.MEM_HOST))
         return u_sys, y_sys, status, x, up, yp
@@ -458,8 +504,8 @@ class BatchedDDMPC:
         return self._lib.ddmpc_kernel_name(self._h).decode()
 
     def closed_loop_kernel_name(self) -> str:
-        """The kernel that stepped the plant in the last `closed_loop`: one of the two fused loops, or 'ddmpc_plant_kernel'
-        when the loop ran per step."""
+        """The kernel that stepped the plant in the last `closed_loop`: one of the fused loops, or 'ddmpc_plant_kernel'
+        when the loop ran per step; 'ddmpc_closed_loop_setpoint_kernel' after `closed_loop_setpoints`."""
         return self._lib.ddmpc_closed_loop_kernel_name(self._h).decode()
 
 

@@ -60,6 +60,9 @@ def parse_args():
                     help="with bounds beyond 271 rows: start each step's active-set iteration from the previous solve's set")
     ap.add_argument("--large_box_law", action="store_true",
                     help="with bounds beyond 271 rows: serve the steps that stay inside the box from the affine law, solve only the others")
+    ap.add_argument("--setpoint_spread", type=float, default=None,
+                    help="instance b tracks its own equilibrium: u_s + S * uniform(-1, 1) (generator seeded with --seed) and the "
+                         "output the plant settles at under it (robust scheme, slack None, no bounds; closed_loop_setpoints)")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     return ap.parse_args()
 
@@ -120,6 +123,12 @@ def main():
         eng.set_large_box_warm_start(True)
     if a.large_box_law:
         eng.set_large_box_law(True)
+    us_b = ys_b = None                           # --setpoint_spread: the setpoints of every instance, [B, m] and [B, p]
+    if a.setpoint_spread is not None:
+        eng.set_setpoint_law(True)
+        gain_dc = plant["C"] @ np.linalg.inv(np.eye(plant["A"].shape[0]) - plant["A"]) @ plant["B"] + plant["D"]
+        us_b = np.asarray(cfg["u_s"], float) + a.setpoint_spread * np.random.default_rng(a.seed).uniform(-1.0, 1.0, (B, m))
+        ys_b = us_b @ gain_dc.T                  # y_s = (C (I - A)^-1 B + D) u_s: an equilibrium of the plant
     eng.set_data(data["u_d"], data["y_d"])
     up = data["u_d"][:, -n:, :].reshape(B, -1)                                   # controller.py:184-185
     yp = data["y_d"][:, -n:, :].reshape(B, -1)
@@ -128,8 +137,13 @@ def main():
         raise ValueError("Failed to get the optimal control input: the first solve is not optimal for "
                          f"{int(np.count_nonzero(status0 > 1))} instance(s)")
     t1 = time.perf_counter()
-    u_sys, y_sys, status, x_end, up_end, yp_end = eng.closed_loop(plant["A"], plant["B"], plant["C"], plant["D"],
-                                                                  data["x_end"], up, yp, w, n_mpc_step=n_mpc_step)
+    if us_b is not None:                         # every step of an instance tracks that instance's own setpoint
+        u_sys, y_sys, status, x_end, up_end, yp_end = eng.closed_loop_setpoints(
+            plant["A"], plant["B"], plant["C"], plant["D"], data["x_end"], up, yp, w,
+            np.repeat(us_b[:, None, :], n_steps, axis=1), np.repeat(ys_b[:, None, :], n_steps, axis=1), n_mpc_step=n_mpc_step)
+    else:
+        u_sys, y_sys, status, x_end, up_end, yp_end = eng.closed_loop(plant["A"], plant["B"], plant["C"], plant["D"],
+                                                                      data["x_end"], up, yp, w, n_mpc_step=n_mpc_step)
     t_loop = time.perf_counter() - t1
 
     if a.verbose > 1:                                                            # per-step report of instance 0
@@ -138,25 +152,39 @@ def main():
                           slack_type=L.SLACK_CONVEX if cfg["slack"] == "convex" else L.SLACK_NONE,
                           eps_max=cfg["eps_max"], lamb_alpha=cfg["lamb_alpha"], lamb_sigma=cfg["lamb_sigma"],
                           c=cfg["c"], use_terminal_constraint=cfg["tec"], device=a.device) as one:
+            if us_b is not None:
+                one.set_setpoint_law(True)
             one.set_data(data["u_d"][:1], data["y_d"][:1])
             U = np.concatenate([data["u_d"][0, -n:], u_sys[0]]); Y = np.concatenate([data["y_d"][0, -n:], y_sys[0]])
             for t in range(0, n_steps, n_mpc_step):                              # one line per solve, controller_operation.py:310-329
-                _, cst, _, _ = one.step(U[t:t + n].reshape(1, -1), Y[t:t + n].reshape(1, -1))
+                if us_b is not None:
+                    _, cst, _, _ = one.step_setpoints(U[t:t + n].reshape(1, -1), Y[t:t + n].reshape(1, -1), us_b[:1], ys_b[:1])
+                else:
+                    _, cst, _, _ = one.step(U[t:t + n].reshape(1, -1), Y[t:t + n].reshape(1, -1))
                 k = min(t + n_mpc_step, n_steps) - 1                             # errors of the last applied step
-                print(step_report_line(t, float(cst[0]), cfg["u_s"], cfg["y_s"], u_sys[0, k], y_sys[0, k]))
+                print(step_report_line(t, float(cst[0]), cfg["u_s"] if us_b is None else us_b[0],
+                                       cfg["y_s"] if ys_b is None else ys_b[0], u_sys[0, k], y_sys[0, k]))
     if a.verbose:
         n_bad = int(np.count_nonzero(status > 1))
-        err_y = np.abs(y_sys[:, -1, :] - cfg["y_s"]); err_u = np.abs(u_sys[:, -1, :] - cfg["u_s"])
+        err_y = np.abs(y_sys[:, -1, :] - (cfg["y_s"] if ys_b is None else ys_b))
+        err_u = np.abs(u_sys[:, -1, :] - (cfg["u_s"] if us_b is None else us_b))
         solves = B * ((n_steps + n_mpc_step - 1) // n_mpc_step)
         print(f"data generation (host) {t_gen:.2f} s; closed loop of {B} controllers x {n_steps} steps "
               f"({solves} QP solves) in {t_loop * 1e3:.1f} ms incl. host<->device copies")
         print(f"non-optimal instances: {n_bad}; final |y - y_s| mean {err_y.mean(axis=0)}, max {err_y.max(axis=0)}; "
               f"final |u - u_s| mean {err_u.mean(axis=0)}")
         print(f"instance 0: y[-1] = {y_sys[0, -1]}, u[-1] = {u_sys[0, -1]}")
+        if us_b is not None:
+            print(f"per-instance setpoints (spread {a.setpoint_spread}): instance 0 tracks y_s = {ys_b[0]}, u_s = {us_b[0]}; "
+                  f"{eng.closed_loop_kernel_name()}")
     if a.out:
-        np.savez_compressed(a.out, u_sys=u_sys, y_sys=y_sys, status=status, u_s=cfg["u_s"], y_s=cfg["y_s"])
+        np.savez_compressed(a.out, u_sys=u_sys, y_sys=y_sys, status=status, u_s=cfg["u_s"] if us_b is None else us_b,
+                            y_s=cfg["y_s"] if ys_b is None else ys_b)
     if a.plot:
         from _plot import plot_closed_loops
+        if us_b is not None:                     # every instance as its deviation from its own setpoint, around the configured one
+            u_sys = u_sys - us_b[:, None, :] + np.asarray(cfg["u_s"], float)
+            y_sys = y_sys - ys_b[:, None, :] + np.asarray(cfg["y_s"], float)
         plot_closed_loops(a.plot, {"closed loop": (u_sys, y_sys)}, cfg["u_s"], cfg["y_s"],
                           title=f"{B} controllers, {'robust' if cfg['robust'] else 'nominal'} scheme, slack {cfg['slack']}")
     eng.close()

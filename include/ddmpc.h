@@ -291,6 +291,21 @@ extern "C" {
                                          law), without finite bounds, off the phase kernels, and on a slack-only CONVEX handle (it
                                          keeps rr3_solve_kernel: DDMPC_OPT_LARGE_AFFINE_LAW is its option, and stays refused with
                                          bounds) */
+#define DDMPC_OPT_SETPOINT_LAW 18        /* ROBUST controllers on the register-resident kernels, slack NONE, scalar / diagonal weights:
+                                         1 = ddmpc_prepare also forms S = K0^-1 [1_0 .. 1_{m+p-1}], the response of beta to the
+                                         setpoint of every channel ((m+p) r doubles per instance: 4.4 KB at L = 30, n = 4, m = p = 2,
+                                         18 MB at 4096 instances; an allocation failure is DDMPC_ERR_HIP), which makes the setpoint an
+                                         argument of the step like the past window: ddmpc_step_setpoints, ddmpc_closed_loop_setpoints
+                                         and ddmpc_get_setpoint_gain (see there).  The columns of S are refined exactly as the columns
+                                         of the law are (DDMPC_OPT_REFINE).  With 1, ddmpc_solve, ddmpc_step, ddmpc_closed_loop,
+                                         ddmpc_get_gain and ddmpc_get_solution launch what they launch with 0 and return bit-equal
+                                         results.  0 (default): nothing is formed, the three calls are DDMPC_ERR_UNSUPPORTED.  Values
+                                         other than 0 / 1: DDMPC_ERR_INVALID.  Changing the value forgets what ddmpc_prepare kept.
+                                         Setting 1 is DDMPC_ERR_UNSUPPORTED, with a message that names the reason, on NOMINAL
+                                         controllers, with the CONVEX slack box, with DDMPC_WEIGHT_DENSE, beyond 271 rows, on a
+                                         trajectory beyond the LDS, with n(m+p) > 256 and on a handle with input or output bounds;
+                                         in the reverse order ddmpc_set_input_bounds / ddmpc_set_output_bounds refuse finite bounds
+                                         on a handle with the option on */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -566,6 +581,38 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
                       double* x, double* u_past, double* y_past, const double* w,
                       double* u_sys, double* y_sys, int32_t* status, int mem);
 
+/* Per-instance, per-step setpoints (DDMPC_OPT_SETPOINT_LAW = 1; DDMPC_ERR_UNSUPPORTED on all three calls without it).  The
+ * reduced system K0 beta = t is linear in t and t is linear in the setpoints, so with m + p more columns the law of
+ * ddmpc_prepare takes the setpoint as an argument:
+ *     beta_b = sum_f past_b[f] gain[b][1+f][:] + sum_c s_b[c] S[b][c][:],      s_b = [u_s_b ; y_s_b],
+ *     S[b][c][:] = K0_b^-1 1_c,  1_c[rho] = 1 iff rho mod (m+p) = c and row rho takes its target from a setpoint (every
+ *     prediction step, free or terminal; rho the internal time-major order of ddmpc_get_gain).
+ * With the terminal constraint a setpoint should be an equilibrium of the instance's plant, as for ddmpc_set_setpoints.
+ * ddmpc_step_setpoints: ddmpc_step with u_s [batch, m] and y_s [batch, p] (they follow `mem`, like the windows).  Prepares
+ *   on first use, then one launch ("ddmpc_setpoint_step_kernel").  status = the status of the factorisation, iters = 1; a
+ *   non-finite setpoint gives that instance DDMPC_STATUS_SOLVER_ERROR and leaves its neighbours as they are.  The handle's own
+ *   setpoints are neither read nor changed.  DDMPC_ERR_NOT_READY before ddmpc_set_data.
+ * ddmpc_closed_loop_setpoints: ddmpc_closed_loop with a schedule u_ref [batch, n_steps, m], y_ref [batch, n_steps, p]: the
+ *   solve made at step t uses row t, rows between solves are not read.  Everything else as for ddmpc_closed_loop (arguments,
+ *   stopped instances, 1 <= ns <= 16, 1 <= n_mpc_step <= L); an instance also stops, with DDMPC_STATUS_SOLVER_ERROR, at a solve
+ *   whose setpoint is not finite.  Always one fused launch ("ddmpc_closed_loop_setpoint_kernel", reported by
+ *   ddmpc_closed_loop_kernel_name): there is no per-step path, n_mpc_step * m > 256 is DDMPC_ERR_UNSUPPORTED, and
+ *   DDMPC_OPT_CLOSED_LOOP_PATH and DDMPC_OPT_CLOSED_LOOP_GRAPH are ignored.
+ * ddmpc_get_setpoint_gain: out [batch, m+p, r] doubles = S.  DDMPC_ERR_NOT_READY before a ddmpc_prepare with the option on.
+ * ddmpc_get_solution after either of the first two calls is DDMPC_ERR_NOT_READY (the reconstruction reads the shared
+ *   setpoint table); a later ddmpc_solve or ddmpc_step makes the solution readable again.
+ * LIMITS: ROBUST controllers only; slack NONE (no CONVEX slack box) and no input / output bounds; scalar / diagonal weights;
+ *   at most 271 rows and a trajectory that fits the LDS; n(m+p) <= 256.  The cold kernels know the handle's shared setpoints
+ *   only (ddmpc_solve).  Under DDMPC_REFINE_AUTO the instances whose law and S are refined are chosen from solves at the
+ *   handle's own setpoints, not at the ones passed later. */
+int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_past, const double* u_s, const double* y_s,
+                         double* u_opt, double* cost, int32_t* status, int32_t* iters, int mem);
+int ddmpc_closed_loop_setpoints(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps, int32_t n_mpc_step,
+                                double* x, double* u_past, double* y_past, const double* w,
+                                const double* u_ref, const double* y_ref,
+                                double* u_sys, double* y_sys, int32_t* status, int mem);
+int ddmpc_get_setpoint_gain(ddmpc_handle* h, double* out, int mem);
+
 /* Kernel facts for benchmarking: algorithmic flops and bytes of one cold solve
  * with this handle's configuration (see DESIGN.md "Roofline accounting"). */
 int ddmpc_cost_model(ddmpc_handle* h, double* flops_per_solve, double* bytes_per_solve);
@@ -576,7 +623,8 @@ const char* ddmpc_kernel_name(ddmpc_handle* h);
 /* Name of the kernel that stepped the plant in the last ddmpc_closed_loop: "ddmpc_closed_loop_warm_kernel" or
  * "ddmpc_closed_loop_convex_warm_kernel" / "ddmpc_closed_loop_box_kernel" (input bounds) when the whole loop ran fused in one launch, "ddmpc_plant_kernel" when it ran
  * per step (DDMPC_PATH_COLD, shapes beyond the fused loops' bounds, NOMINAL instances without a law, laws taken from
- * refining solves under DDMPC_OPT_CONVEX_WARM_LAW, handles beyond 271 rows); "" before the first loop.  Read-only. */
+ * refining solves under DDMPC_OPT_CONVEX_WARM_LAW, handles beyond 271 rows); "ddmpc_closed_loop_setpoint_kernel" after
+ * ddmpc_closed_loop_setpoints; "" before the first loop.  Read-only. */
 const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h);
 
 /* Diagnostics only: in-kernel phase stamps (shader-clock ticks) of the next solves.
