@@ -336,6 +336,11 @@ static bool prep_valid(const ddmpc_handle* h) { return h->prep.valid && h->prep.
 // of them comes through here: ddmpc_set_data, ddmpc_set_setpoints, both bounds calls, a new ddmpc_prepare).
 static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; h->last.large_seed = false; }
 
+// An option that decides which kernels serve a bounded handle on Route::RobustPhases was set (DDMPC_OPT_LARGE_BOX_CAPACITY,
+// _SAFEGUARD, _WARM_START, _LAW): the next solve may lay the per-instance record out differently, and setting one, to any value,
+// drops the seed (the next step starts from the empty set).
+static void forget_large_box_solve(ddmpc_handle* h) { h->last.valid = false; h->last.large_seed = false; }
+
 // A call that writes solve outputs starts the record afresh (nothing of an earlier call survives) and makes it readable at its end.
 static Route begin_solve(ddmpc_handle* h, Route route) { h->last = LastSolve{}; h->last.route = route; return route; }
 static void end_solve(ddmpc_handle* h, const double* up, const double* yp) { h->last.up = up; h->last.yp = yp; h->last.valid = true; }
@@ -349,7 +354,7 @@ static bool box_seed_valid(const ddmpc_handle* h) {
 
 // DDMPC_OPT_LARGE_BOX_WARM_START: the last solve of the handle left a seed the next step on Route::RobustPhases may read.  Unlike
 // box_seed_valid it does not ask for a finished record: the steps of the per-step closed loop follow each other inside one
-// call.  What drops it clears the flag itself (forget_prep, options 12, 13, 14 and 16).  Asked before begin_solve.
+// call.  What drops it clears the flag itself (forget_prep, forget_large_box_solve, option 12).  Asked before begin_solve.
 static bool large_seed_valid(const ddmpc_handle* h) {
   return h->large_box_warm && h->last.route == Route::RobustPhases && h->last.large_seed;
 }
@@ -1125,31 +1130,67 @@ static int launch_rr3_factors(ddmpc_handle* h) {
   return DDMPC_OK;
 }
 
-// A bounded handle with DDMPC_OPT_LARGE_BOX_CAPACITY above 64 is served by rr3_solve_box_wide_kernel (ddmpc_rr3_box_wide.hpp), and
-// so is one with DDMPC_OPT_LARGE_BOX_SAFEGUARD at every capacity (64 included: the safeguard writes one layout of W, tiles and record)
-// and one with DDMPC_OPT_LARGE_BOX_WARM_START (the seeded instantiation is that kernel's).
-static bool rr3_wide(const ddmpc_handle* h) {
-  return h->bounded && (h->large_box_cap > RR3_KMAX || h->large_box_safeguard != 0 || h->large_box_warm != 0);
+// What fixes the kernels and the memory layout of one solve on the kept factors, decided here and nowhere else.
+//   Plain    rr3_solve_kernel: no input / output bounds.  Instances it marks 5 go to the fall-back (launch_rr3_fallback).
+//   Box      rr3_solve_box_kernel: the instantiations that test the component table, RR3_KMAX columns of W.  No fall-back kernel
+//            knows the bounds (an instance beyond RR3_KMAX active components ends in status 4 inside the kernel).
+//   BoxWide  rr3_solve_box_wide_kernel (ddmpc_rr3_box_wide.hpp), the twin with `capacity` columns of W and the tiled k x k system:
+//            DDMPC_OPT_LARGE_BOX_CAPACITY above 64, DDMPC_OPT_LARGE_BOX_SAFEGUARD at every capacity (64 included: the safeguard
+//            writes one layout of W, tiles and record) and DDMPC_OPT_LARGE_BOX_WARM_START (the seeded instantiation is that kernel's).
+enum class Rr3Family { Plain, Box, BoxWide };
+struct Rr3Plan {
+  Rr3Family family;
+  int cap;                     // columns of W per instance
+  size_t lds;                  // dynamic LDS of every solve and safeguard launch, bytes
+  int nA, ldw;                 // rows ahead of the trailing block; leading dimension of W
+  long long wstride, kstride;  // per instance: doubles of W and the k x k system, ints of the record
+  bool filtered;               // DDMPC_OPT_LARGE_BOX_LAW: the instantiations with the instance filter (Rr3Only)
+  bool seed_read;              // DDMPC_OPT_LARGE_BOX_WARM_START with a valid seed: the seeded instantiation (without one, the kernel of the option 0)
+  bool seed_kept;              // ... every call leaves its set in d_large_seed (rr3_box_keep_seed_kernel)
+  bool safeguard;              // DDMPC_OPT_LARGE_BOX_SAFEGUARD: rr3_box_safeguard_kernel behind the solve launch
+};
+
+// Ints of the per-instance record: [k, state, iterations, k, switched positions (cap), active set (rv), start tick, ticks, peak k].
+static long long rr3_kstride(int cap, int rv) { return 4 + cap + rv + 4; }
+
+static Rr3Plan rr3_plan(const ddmpc_handle* h, const KParams& kq, bool filtered = false, bool seeded = false) {
+  const int r = kq.r, rv = (r + 1) & ~1;
+  const bool wide = h->bounded && (h->large_box_cap > RR3_KMAX || h->large_box_safeguard != 0 || h->large_box_warm != 0);
+  Rr3Plan P{};
+  P.family = wide ? Rr3Family::BoxWide : h->bounded ? Rr3Family::Box : Rr3Family::Plain;
+  P.cap = wide ? h->large_box_cap : RR3_KMAX;
+  P.lds = ((size_t)Rr3Lds::make(r).total + (wide ? (size_t)rr3w_lds_extra(P.cap) : h->bounded ? (size_t)RR3_BOX_LDS : 0)) * sizeof(double);
+  P.nA = (kq.convex || h->bounded) ? h->nA3 : r;
+  P.ldw = ((r - (P.nA & ~63)) + 63) & ~63;
+  P.filtered = filtered;
+  P.seed_read = wide && h->large_box_warm && seeded;
+  P.seed_kept = wide && h->large_box_warm;
+  P.safeguard = wide && h->large_box_safeguard;
+  // W with cap columns, then the k x k system: one (RR3_KMAX + 1)-strided block, or the 64 x 64 tiles of the wide kernel -- and
+  // behind them what rr3_box_safeguard_kernel keeps: the unfactored tiles, v, the entering column
+  P.wstride = (long long)P.cap * P.ldw + (wide ? rr3w_tiles(P.cap) * 4096 : (long long)RR3_KMAX * (RR3_KMAX + 1));
+  if (P.safeguard) P.wstride += rr3s_extra(P.cap, h->nbox3, P.ldw);
+  P.kstride = rr3_kstride(P.cap, rv);
+  return P;
 }
 
-// The descriptor of the kept factors and of the solve's workspace (sized here).
+// The table of boxed components of a bounded handle, as the kernels take it.
+static Rr3Box rr3_box(const ddmpc_handle* h) {
+  Rr3Box X{};
+  X.nbox = h->nbox3; X.ip = (const int*)h->d_r3bi.p; X.bd = (const double*)h->d_r3bd.p;
+  return X;
+}
+
+// The descriptor of the kept factors and of the solve's workspace (sized here, by the plan).
 static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
   const int r = kq.r, n16 = (r + 15) & ~15, rv = (r + 1) & ~1, VL = (r + 63) & ~63;
   const size_t B = (size_t)h->batch;
   const long long m64G = rr2_m64(n16);
-  const int nA = (kq.convex || h->bounded) ? h->nA3 : r, n0 = nA & ~63;
-  const int ldw = ((r - n0) + 63) & ~63;
-  long long wstride = (long long)RR3_KMAX * ldw + (long long)RR3_KMAX * (RR3_KMAX + 1), kstride = 4 + RR3_KMAX + rv + 4;
-  if (rr3_wide(h)) {    // rr3_solve_box_wide_kernel: W with `capacity` columns, then the 64 x 64 tiles of the k x k system
-    const int cap = h->large_box_cap;
-    wstride = (long long)cap * ldw + rr3w_tiles(cap) * 4096;
-    if (h->large_box_safeguard) wstride += rr3s_extra(cap, h->nbox3, ldw);   // rr3_box_safeguard_kernel: the unfactored tiles, v, the entering column
-    kstride = 4 + cap + rv + 4;
-  }
+  const Rr3Plan P = rr3_plan(h, kq);
   int rc;
-  if (rr3_wide(h) && h->large_box_warm && (rc = h->d_large_seed.ensure(B * (size_t)kq.rE))) return rc;   // DDMPC_OPT_LARGE_BOX_WARM_START
+  if (P.seed_kept && (rc = h->d_large_seed.ensure(B * (size_t)kq.rE))) return rc;
   if ((rc = h->d_rr2v.ensure(B * (size_t)R3_NV * VL * sizeof(double))) || (rc = h->d_rr2zp.ensure(B * (size_t)RR2_NG * VL * sizeof(double))) ||
-      (rc = h->d_rr3w.ensure(B * (size_t)wstride * sizeof(double))) || (rc = h->d_rr3k.ensure(B * (size_t)kstride * sizeof(int))) ||
+      (rc = h->d_rr3w.ensure(B * (size_t)P.wstride * sizeof(double))) || (rc = h->d_rr3k.ensure(B * (size_t)P.kstride * sizeof(int))) ||
       (rc = h->d_beta.ensure(B * (size_t)kq.rE * sizeof(double))) || (rc = h->d_act.ensure(B * (size_t)kq.rE)))
     return rc;
   Rr3& S = *out;
@@ -1159,153 +1200,111 @@ static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
   S.skip = (const int*)h->d_rrmeta.p; S.s_stride = 2 * (long long)rv + 2;
   S.dd = (const unsigned long long*)h->d_rr2d.p;
   S.perm = (const int*)h->d_perm.p;
-  S.rv = rv; S.r = r; S.nA = nA; S.n0 = n0;
+  S.rv = rv; S.r = r; S.nA = P.nA; S.n0 = P.nA & ~63;
   S.V = (double*)h->d_rr2v.p; S.vstride = (long long)R3_NV * VL; S.VL = VL;
   S.ZP = (double*)h->d_rr2zp.p;
-  S.Wg = (double*)h->d_rr3w.p; S.wstride = wstride; S.ldw = ldw;
-  S.kq = (int*)h->d_rr3k.p; S.kstride = kstride;
+  S.Wg = (double*)h->d_rr3w.p; S.wstride = P.wstride; S.ldw = P.ldw;
+  S.kq = (int*)h->d_rr3k.p; S.kstride = P.kstride;
+  return DDMPC_OK;
+}
+
+// Dynamic LDS of the one-workgroup kernels (ddmpc_large_solve_kernel, ddmpc_large_solve_wide_kernel), bytes.
+static size_t large_solve_lds(size_t r) {
+  const size_t rv = (r + 1) & ~(size_t)1;
+  return 6 * rv * sizeof(double) + 4 * rv * sizeof(int) + (size_t)PSD_PAN * sizeof(double);
+}
+
+// Instances the unbounded phase solve marked 5 (more switched components than W holds, a failed pivot of the k x k system): the
+// one-workgroup kernel of rounds 1-4 solves them from scratch in a workspace of its own; every other workgroup leaves at once.
+static int launch_rr3_fallback(ddmpc_handle* h, const KParams& kq, const double* up, const double* yp, double* uo, double* cost,
+                               int32_t* status, int32_t* iters) {
+  const size_t B = (size_t)h->batch, r = (size_t)kq.r, stride = large_robust_stride(kq, h->prm);
+  const size_t nfb = B < 8 ? B : 8;                         // (one slice of workspace per workgroup of the fall-back grid)
+  int rc;
+  if ((rc = h->d_rr_fb.ensure(nfb * stride * sizeof(double))) || (rc = h->d_rrmeta_fb.ensure(nfb * sizeof(int)))) return rc;
+  const size_t lds = large_solve_lds(r);
+  if (lds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)ddmpc_large_solve_kernel<0>, lds));
+  hipLaunchKernelGGL(ddmpc_large_solve_kernel<0>, dim3((unsigned)nfb), dim3(large_threads(r)), lds, h->stream, kq, 16 * h->kc.NT, h->ud, h->yd,
+                     up, yp, uo, cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, (double*)h->d_rr_fb.p,
+                     (long long)stride, (int*)h->d_rrmeta_fb.p, 5, (long long)B);
+  HIP_TRY(hipGetLastError());
   return DDMPC_OK;
 }
 
 // The solve on those factors (what a control step repeats, controller.py:389-407).  only (nullptr: the whole batch): per-instance
-// flags of the law step, the solve launches leave every other instance alone.  seeded (DDMPC_OPT_LARGE_BOX_WARM_START = 1 on a
-// bounded handle only): the iteration starts from the set in d_large_seed; with the option 1 every call leaves its set there.
+// flags of the law step, the solve launches leave every other instance alone -- on a bounded handle (DDMPC_OPT_LARGE_BOX_LAW) by
+// the filtered instantiations, the same launches for the instances the law step flagged.  seeded (DDMPC_OPT_LARGE_BOX_WARM_START
+// = 1 on a bounded handle only): the iteration starts from the set in d_large_seed; with the option 1 every call leaves its set
+// there.
 static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up, const double* yp, double* uo, double* cost,
                             int32_t* status, int32_t* iters, const int* only = nullptr, int* only_si = nullptr, bool seeded = false) {
-  const int r = kq.r, VL = (r + 63) & ~63;
-  const size_t B = (size_t)h->batch;
-  const Rr3Lds LD = Rr3Lds::make(r);
-  const size_t lds = (size_t)LD.total * sizeof(double);
+  const int r = kq.r;
+  const unsigned B = (unsigned)h->batch;
+  const Rr3Plan P = rr3_plan(h, kq, only != nullptr, seeded);
   Rr3 S;
   int rc;
   if ((rc = rr3_desc(h, kq, &S))) return rc;
+  h->last.box_cap = P.cap;
   const int RPs = 16 * h->kc.NT;
   const bool refine = kq.refine != DDMPC_REFINE_OFF && kq.lam != 0.0;
-  if (lds > 64 * 1024) {
-    HIP_TRY(raise_lds_limit((const void*)rr3_solve_kernel<false>, lds));
-    HIP_TRY(raise_lds_limit((const void*)rr3_solve_kernel<true>, lds));
-  }
-  Rr3Box X{};
-  size_t blds = lds;
-  const bool wide = rr3_wide(h);
-  const int cap = wide ? h->large_box_cap : RR3_KMAX;
-  h->last.box_cap = cap;
-  const Rr3Only flt{only};                                  // (bounded handles, DDMPC_OPT_LARGE_BOX_LAW: the filtered instantiations)
-  if (wide) {
-    // DDMPC_OPT_LARGE_BOX_CAPACITY above 64: the twin with `capacity` columns of W and the tiled k x k system
-    X.nbox = h->nbox3; X.ip = (const int*)h->d_r3bi.p; X.bd = (const double*)h->d_r3bd.p;
-    blds = lds + (size_t)rr3w_lds_extra(cap) * sizeof(double);
-    if (blds > 64 * 1024) {
-      HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<false>, blds));
-      HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<true>, blds));
-      if (only != nullptr) {
-        HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<false, Rr3Only>, blds));
-        HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_wide_kernel<true, Rr3Only>, blds));
-      }
-    }
-    if (only != nullptr && h->large_box_warm && seeded) {
-      // DDMPC_OPT_LARGE_BOX_LAW: the same launches for the instances the law step flagged, every other workgroup leaves at once
-      const auto kern = rr3_solve_box_wide_kernel<false, Rr3Seed, Rr3Only>;
-      const Rr3Seed seed{(const signed char*)h->d_large_seed.p, h->large_box_safeguard ? 1 : 0};
-      if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)kern, blds));
-      hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status, (int*)iters,
-                         (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap, seed, flt);
-    } else if (only != nullptr) {
-      hipLaunchKernelGGL((rr3_solve_box_wide_kernel<false, Rr3Only>), dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo,
-                         cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap, flt);
-    } else
-    if (h->large_box_warm && seeded) {
-      // DDMPC_OPT_LARGE_BOX_WARM_START with a valid seed: the seeded instantiation (without one, the kernel of the option 0)
-      const auto kern = rr3_solve_box_wide_kernel<false, Rr3Seed>;
-      const Rr3Seed seed{(const signed char*)h->d_large_seed.p, h->large_box_safeguard ? 1 : 0};
-      if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)kern, blds));
-      hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status, (int*)iters,
-                         (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap, seed);
-    } else
-    hipLaunchKernelGGL(rr3_solve_box_wide_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
-                       (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap);
-    if (h->large_box_safeguard) {
-      // DDMPC_OPT_LARGE_BOX_SAFEGUARD: the instances that reached max_iter are solved again by the primal method, before the
-      // Hankel products and the refinement launch; every other workgroup leaves at once
-      if (only != nullptr) {
-        if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)rr3_box_safeguard_kernel<Rr3Only>, blds));
-        hipLaunchKernelGGL(rr3_box_safeguard_kernel<Rr3Only>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
-                           (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap, flt);
-      } else {
-      if (blds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)rr3_box_safeguard_kernel<>, blds));
-      hipLaunchKernelGGL(rr3_box_safeguard_kernel<>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
-                         (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, cap);
-      }
-    }
-  } else
-  if (h->bounded) {
-    // input / output bounds: the instantiations that test the component table.  No fall-back kernel knows the bounds (an
-    // instance beyond RR3_KMAX active components ends in status 4 inside the kernel).  DDMPC_OPT_LARGE_BOX_LAW: the filtered
-    // instantiations serve the instances the law step flagged.
-    X.nbox = h->nbox3; X.ip = (const int*)h->d_r3bi.p; X.bd = (const double*)h->d_r3bd.p;
-    blds = lds + (size_t)RR3_BOX_LDS * sizeof(double);
-    if (blds > 64 * 1024) {
-      HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<false>, blds));
-      HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<true>, blds));
-      if (only != nullptr) {
-        HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<false, Rr3Only>, blds));
-        HIP_TRY(raise_lds_limit((const void*)rr3_solve_box_kernel<true, Rr3Only>, blds));
-      }
-    }
-    if (only != nullptr)
-      hipLaunchKernelGGL((rr3_solve_box_kernel<false, Rr3Only>), dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
-                         (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X, flt);
-    else
-    hipLaunchKernelGGL(rr3_solve_box_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
-                       (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, X);
-  } else
-  hipLaunchKernelGGL(rr3_solve_kernel<false>, dim3((unsigned)B), dim3(RR2_TS), lds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
-                     (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, refine ? 1 : 0, only);
+  const Rr3Box X = rr3_box(h);
+  const Rr3Only flt{only};
+  const Rr3Seed seed{(const signed char*)h->d_large_seed.p, P.safeguard ? 1 : 0};
+  auto launch = [&](auto kernel, int defer_outputs, auto... tail) -> int {
+    if (P.lds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)kernel, P.lds));
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(RR2_TS), P.lds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status, (int*)iters,
+                       (double*)h->d_beta.p, (signed char*)h->d_act.p, defer_outputs, tail...);
+    return DDMPC_OK;
+  };
+  const bool wide = P.family == Rr3Family::BoxWide, box = P.family == Rr3Family::Box, F = P.filtered;
+  const int defer = refine ? 1 : 0;
+  if      (wide && P.seed_read && F) rc = launch(rr3_solve_box_wide_kernel<false, Rr3Seed, Rr3Only>, defer, X, P.cap, seed, flt);
+  else if (wide && P.seed_read)      rc = launch(rr3_solve_box_wide_kernel<false, Rr3Seed>, defer, X, P.cap, seed);
+  else if (wide && F)                rc = launch(rr3_solve_box_wide_kernel<false, Rr3Only>, defer, X, P.cap, flt);
+  else if (wide)                     rc = launch(rr3_solve_box_wide_kernel<false>, defer, X, P.cap);
+  else if (box && F)                 rc = launch(rr3_solve_box_kernel<false, Rr3Only>, defer, X, flt);
+  else if (box)                      rc = launch(rr3_solve_box_kernel<false>, defer, X);
+  else                               rc = launch(rr3_solve_kernel<false>, defer, only);
+  if (rc) return rc;
+  // the instances that reached max_iter are solved again by the primal method, before the Hankel products and the refinement
+  // launch; every other workgroup leaves at once
+  if (P.safeguard && F) rc = launch(rr3_box_safeguard_kernel<Rr3Only>, defer, X, P.cap, flt);
+  else if (P.safeguard) rc = launch(rr3_box_safeguard_kernel<>, defer, X, P.cap);
+  if (rc) return rc;
   if (refine) {
     // H (H' beta) with exact products (the Hankel kernels of the NOMINAL pipeline: they read slot R3_X of the vectors)
     Rr2Solve H{};
-    H.V = S.V; H.vstride = S.vstride; H.VL = VL; H.ZP = S.ZP; H.fdiv = 1; H.r = r;
+    H.V = S.V; H.vstride = S.vstride; H.VL = S.VL; H.ZP = S.ZP; H.fdiv = 1; H.r = r;
     H.si = only_si;                                       // (the filtered re-solve: only the flagged instances, pass > 0 skips the rest)
     HankelLaunch hk;
     if ((rc = pick_hankel_launch(kq, &hk))) return rc;
-    launch_hankel(hk, h->stream, (unsigned)B, H, kq, h->ud, h->yd, (int)R3_X, only_si != nullptr ? 1 : 0);
-    if (wide && only != nullptr)
-      hipLaunchKernelGGL((rr3_solve_box_wide_kernel<true, Rr3Only>), dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo,
-                         cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X, cap, flt);
-    else if (wide)
-      hipLaunchKernelGGL(rr3_solve_box_wide_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
-                         (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X, cap);
-    else if (h->bounded && only != nullptr)
-      hipLaunchKernelGGL((rr3_solve_box_kernel<true, Rr3Only>), dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost,
-                         (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X, flt);
-    else if (h->bounded)
-      hipLaunchKernelGGL(rr3_solve_box_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), blds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
-                         (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, X);
-    else
-    hipLaunchKernelGGL(rr3_solve_kernel<true>, dim3((unsigned)B), dim3(RR2_TS), lds, h->stream, S, kq, RPs, up, yp, uo, cost, (int*)status,
-                       (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, 0, only);
+    launch_hankel(hk, h->stream, B, H, kq, h->ud, h->yd, (int)R3_X, only_si != nullptr ? 1 : 0);
+    if      (wide && F) rc = launch(rr3_solve_box_wide_kernel<true, Rr3Only>, 0, X, P.cap, flt);
+    else if (wide)      rc = launch(rr3_solve_box_wide_kernel<true>, 0, X, P.cap);
+    else if (box && F)  rc = launch(rr3_solve_box_kernel<true, Rr3Only>, 0, X, flt);
+    else if (box)       rc = launch(rr3_solve_box_kernel<true>, 0, X);
+    else                rc = launch(rr3_solve_kernel<true>, 0, only);
+    if (rc) return rc;
   }
-  if (wide && h->large_box_warm) {
+  if (P.seed_kept) {
     // the signed set the call finally reported (the solve, safeguard or refinement launch wrote it last) becomes the next step's seed
-    hipLaunchKernelGGL(rr3_box_keep_seed_kernel, dim3((unsigned)B), dim3(256), 0, h->stream, r, kq.rE, (const int*)status,
+    hipLaunchKernelGGL(rr3_box_keep_seed_kernel, dim3(B), dim3(256), 0, h->stream, r, kq.rE, (const int*)status,
                        (const signed char*)h->d_act.p, (signed char*)h->d_large_seed.p);
     h->last.large_seed = true;
   }
   HIP_TRY(hipGetLastError());
-  if (!h->bounded) {
-    // instances the phase solve marked 5 (more switched components than W holds, a failed pivot of the k x k system): the
-    // one-workgroup kernel of rounds 1-4 solves them from scratch in a workspace of its own; every other workgroup leaves at once
-    const size_t rr = (size_t)r, rvv = (rr + 1) & ~(size_t)1, stride = large_robust_stride(kq, h->prm);
-    const size_t nfb = B < 8 ? B : 8;                       // (one slice of workspace per workgroup of the fall-back grid)
-    if ((rc = h->d_rr_fb.ensure(nfb * stride * sizeof(double))) || (rc = h->d_rrmeta_fb.ensure(nfb * sizeof(int)))) return rc;
-    const size_t flds = 6 * rvv * sizeof(double) + 4 * rvv * sizeof(int) + (size_t)PSD_PAN * sizeof(double);
-    if (flds > 64 * 1024) HIP_TRY(raise_lds_limit((const void*)ddmpc_large_solve_kernel<0>, flds));
-    hipLaunchKernelGGL(ddmpc_large_solve_kernel<0>, dim3((unsigned)nfb), dim3(large_threads(rr)), flds, h->stream, kq, RPs, h->ud, h->yd, up, yp, uo,
-                       cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, (double*)h->d_rr_fb.p, (long long)stride,
-                       (int*)h->d_rrmeta_fb.p, 5, (long long)B);
-    HIP_TRY(hipGetLastError());
-  }
-  return DDMPC_OK;
+  return P.family == Rr3Family::Plain ? launch_rr3_fallback(h, kq, up, yp, uo, cost, status, iters) : DDMPC_OK;
+}
+
+// The per-instance flags of the law on Route::RobustPhases, d_r3flag (5 B ints): [no law | need | refine | si (2 B)].
+struct Rr3Flags {
+  int *nolaw, *need, *rfl;     // the law missed the threshold; the step left the instance to the solve; the law build's refinement passes
+  int* si;                     // [2 B]: need in the layout of Rr2Solve::si
+};
+static Rr3Flags rr3_flags(const ddmpc_handle* h) {
+  int* f = (int*)h->d_r3flag.p;
+  const size_t B = (size_t)h->batch;
+  return Rr3Flags{f, f + B, f + 2 * B, f + 3 * B};
 }
 
 // DDMPC_OPT_LARGE_AFFINE_LAW on Route::RobustPhases (ddmpc_rr3_law.hpp): the law beta(w) = g0 + G' w of every instance on the
@@ -1333,8 +1332,7 @@ static int launch_rr3_law_build(ddmpc_handle* h) {
   const int RPs = 16 * h->kc.NT;
   double* law = (double*)h->d_gz.p;
   double* Y = (double*)h->d_r3y.p;
-  int* nolaw = (int*)h->d_r3flag.p;
-  int* rfl = nolaw + 2 * B;
+  int *nolaw = rr3_flags(h).nolaw, *rfl = rr3_flags(h).rfl;
   HIP_TRY(hipMemsetAsync(nolaw, 0, B * sizeof(int), h->stream));
   std::vector<int> fl(Bc);
   for (size_t b0 = 0; b0 < B; b0 += Bc) {
@@ -1376,24 +1374,35 @@ static int launch_rr3_law_build(ddmpc_handle* h) {
   return DDMPC_OK;
 }
 
+// DDMPC_OPT_LARGE_BOX_LAW: the law serves a bounded handle on Route::RobustPhases.
+static bool rr3_box_law(const ddmpc_handle* h) { return h->large_box_law != 0 && h->large && !h->large_nominal && h->bounded; }
+
+// The launch of a control step on that law over the batch: what the two step kernels share, box: that of a bounded handle, which
+// takes the table and the capacity of the solve behind it.
+static int launch_rr3_law_kernel(ddmpc_handle* h, bool box, const double* up, const double* yp, double* uo, double* cost,
+                                 int32_t* status, int32_t* iters) {
+  const KParams& k = h->kp;
+  const Rr3Flags F = rr3_flags(h);
+  Rr3 S;
+  if (int rc = rr3_desc(h, k, &S)) return rc;
+  auto launch = [&](auto kernel, auto... tail) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(RR2_TS), 0, h->stream, S, k, 16 * h->kc.NT, h->prm.n * k.nch,
+                       (const double*)h->d_gz.p, (const int*)F.nolaw, up, yp, uo, cost, (int*)status, (int*)iters, (double*)h->d_beta.p,
+                       (signed char*)h->d_act.p, F.need, F.si, tail...);
+  };
+  if (box) launch(rr3_law_box_step_kernel, rr3_box(h), rr3_plan(h, k).cap);
+  else launch(rr3_law_step_kernel);
+  HIP_TRY(hipGetLastError());
+  return DDMPC_OK;
+}
+
 // A control step on that law: one launch over the batch, then -- under the slack box, or when some instance has no law -- the solve
 // on the kept factor restricted to the instances the step left to it.
 static int launch_rr3_law_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                                int32_t* iters) {
-  const KParams& k = h->kp;
-  const size_t B = (size_t)h->batch;
-  Rr3 S;
-  int rc;
-  if ((rc = rr3_desc(h, k, &S))) return rc;
-  const int* nolaw = (const int*)h->d_r3flag.p;
-  int* need = (int*)h->d_r3flag.p + B;
-  int* si = (int*)h->d_r3flag.p + 3 * B;                   // [2 B]: need in the layout of Rr2Solve::si
-  hipLaunchKernelGGL(rr3_law_step_kernel, dim3((unsigned)B), dim3(RR2_TS), 0, h->stream, S, k, 16 * h->kc.NT, h->prm.n * k.nch,
-                     (const double*)h->d_gz.p, nolaw, up, yp, uo, cost, (int*)status, (int*)iters, (double*)h->d_beta.p,
-                     (signed char*)h->d_act.p, need, si);
-  HIP_TRY(hipGetLastError());
-  if (k.convex || h->prep.r3_nolaw > 0) return launch_rr3_solve(h, k, up, yp, uo, cost, status, iters, need, si);
-  return DDMPC_OK;
+  if (int rc = launch_rr3_law_kernel(h, false, up, yp, uo, cost, status, iters)) return rc;
+  if (!h->kp.convex && h->prep.r3_nolaw == 0) return DDMPC_OK;
+  return launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters, rr3_flags(h).need, rr3_flags(h).si);
 }
 
 // DDMPC_OPT_LARGE_BOX_LAW (ddmpc_rr3_box_law.hpp): a control step of a bounded handle on that law -- one launch over the batch that
@@ -1401,26 +1410,12 @@ static int launch_rr3_law_step(ddmpc_handle* h, const double* up, const double* 
 // of the option 0) restricted to the instances the step left to it.  The solve launches are queued whatever the step found (no
 // read-back between them): their workgroups leave at once for a served instance, and rr3_box_keep_seed_kernel behind them reads
 // the empty set of a served instance like any other.
-static bool rr3_box_law(const ddmpc_handle* h) { return h->large_box_law != 0 && h->large && !h->large_nominal && h->bounded; }
-
 static int launch_rr3_law_box_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                                    int32_t* iters, bool seeded) {
-  const KParams& k = h->kp;
-  const size_t B = (size_t)h->batch;
-  Rr3 S;
-  int rc;
-  if ((rc = rr3_desc(h, k, &S))) return rc;
-  const int* nolaw = (const int*)h->d_r3flag.p;
-  int* need = (int*)h->d_r3flag.p + B;
-  int* si = (int*)h->d_r3flag.p + 3 * B;                   // [2 B]: need in the layout of Rr2Solve::si
-  Rr3Box X{};
-  X.nbox = h->nbox3; X.ip = (const int*)h->d_r3bi.p; X.bd = (const double*)h->d_r3bd.p;
-  hipLaunchKernelGGL(rr3_law_box_step_kernel, dim3((unsigned)B), dim3(RR2_TS), 0, h->stream, S, k, 16 * h->kc.NT, h->prm.n * k.nch,
-                     (const double*)h->d_gz.p, nolaw, up, yp, uo, cost, (int*)status, (int*)iters, (double*)h->d_beta.p,
-                     (signed char*)h->d_act.p, need, si, X, rr3_wide(h) ? h->large_box_cap : RR3_KMAX);
-  HIP_TRY(hipGetLastError());
-  return launch_rr3_solve(h, k, up, yp, uo, cost, status, iters, need, si, seeded);
+  if (int rc = launch_rr3_law_kernel(h, true, up, yp, uo, cost, status, iters)) return rc;
+  return launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters, rr3_flags(h).need, rr3_flags(h).si, seeded);
 }
+
 
 // ROBUST controllers beyond the register-resident kernels (Route::RobustPhases, Route::RobustOneWg).
 static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const double* up, const double* yp, double* uo,
@@ -1436,11 +1431,11 @@ static int launch_large_robust(ddmpc_handle* h, Route route, Stage stage, const 
     return DDMPC_OK;
   }
   // the one-workgroup kernel: matrices in a per-instance slice of a global workspace
-  const size_t r = (size_t)h->kp.r, rv = (r + 1) & ~(size_t)1, stride = large_robust_stride(h->kp, h->prm);
+  const size_t r = (size_t)h->kp.r, stride = large_robust_stride(h->kp, h->prm);
   if ((rc = h->d_rr.ensure((size_t)h->batch * stride * sizeof(double))) ||
       (rc = h->d_beta.ensure((size_t)h->batch * h->kp.rE * sizeof(double))) || (rc = h->d_act.ensure((size_t)h->batch * h->kp.rE)))
     return rc;
-  const size_t lds = 6 * rv * sizeof(double) + 4 * rv * sizeof(int) + (size_t)PSD_PAN * sizeof(double);
+  const size_t lds = large_solve_lds(r);
   if (lds + 1024 > 160 * 1024) return fail(DDMPC_ERR_UNSUPPORTED, "problem too large: %zu rows", r);
   if ((rc = h->d_rrmeta.ensure((size_t)h->batch * sizeof(int)))) return rc;
   auto launch = [&](auto fn) -> int {
@@ -2727,20 +2722,17 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value != 64 && value != 128 && value != 192 && value != 256)
         return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_CAPACITY must be 64, 128, 192 or 256");
       h->large_box_cap = value;           // (which bounded phase kernel is launched and how its workspace is sized: the factors do not depend on it)
-      h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
-      h->last.large_seed = false;
+      forget_large_box_solve(h);
       return DDMPC_OK;
     case DDMPC_OPT_LARGE_BOX_SAFEGUARD:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_SAFEGUARD must be 0 or 1");
       h->large_box_safeguard = value;     // (which kernels serve a bounded handle beyond 271 rows and how their workspace is sized: the factors do not depend on it)
-      h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
-      h->last.large_seed = false;
+      forget_large_box_solve(h);
       return DDMPC_OK;
     case DDMPC_OPT_LARGE_BOX_WARM_START:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_WARM_START must be 0 or 1");
       h->large_box_warm = value;          // (with 1 the wide kernels serve a bounded handle beyond 271 rows at every capacity: the factors do not depend on it)
-      h->last.valid = false;              // (the next solve may lay the per-instance record out differently)
-      h->last.large_seed = false;         // (setting it, to either value, drops the seed)
+      forget_large_box_solve(h);
       return DDMPC_OK;
     case DDMPC_OPT_LARGE_BOX_LAW:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_BOX_LAW must be 0 or 1");
@@ -2750,8 +2742,7 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
                     h->prm.n * h->kp.nch, WARM_MAX_NF);
       h->large_box_law = value;           // (ddmpc_prepare forms the law next to the factors: it is part of what is kept)
       forget_prep(h);
-      h->last.valid = false;
-      h->last.large_seed = false;
+      forget_large_box_solve(h);
       return DDMPC_OK;
     case DDMPC_OPT_SETPOINT_LAW:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_SETPOINT_LAW must be 0 or 1");
@@ -3488,8 +3479,7 @@ int ddmpc_debug_workspace(ddmpc_handle* h, int64_t b, double* ws_out, int64_t ws
     // ROBUST on the phase kernels (ddmpc_rr3.hpp): the per-instance record of the last solve --
     // [k, state, iterations, k, switched positions (capacity: RR3_KMAX, or DDMPC_OPT_LARGE_BOX_CAPACITY of the solve that wrote
     // it), active set (rv), start tick, ticks, peak k] -- into meta_out
-    const int rv = (h->kp.r + 1) & ~1;
-    const long long kstride = 4 + h->last.box_cap + rv + 4;
+    const long long kstride = rr3_kstride(h->last.box_cap, (h->kp.r + 1) & ~1);
     if (meta_avail) *meta_avail = kstride;
     if (ws_avail) *ws_avail = 0;
     if (b < 0 || b >= h->batch) return fail(DDMPC_ERR_INVALID, "instance out of range");
