@@ -1,4 +1,4 @@
-// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_setpoint_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp, ddmpc_rr3_box.hpp).
+// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_setpoint_law.hpp, ddmpc_setpoint_box_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp, ddmpc_rr3_box.hpp).
 // Host-side responsibilities: parameter validation with the reference's error
 // conditions (direct_data_driven_mpc_controller.py:165-168,211-222,298-343,664-670),
 // device buffer ownership, kernel-instance selection, launch.
@@ -9,6 +9,7 @@
 #include "ddmpc_rr3_box_safe.hpp"
 #include "ddmpc_box_law.hpp"
 #include "ddmpc_setpoint_law.hpp"
+#include "ddmpc_setpoint_box_law.hpp"
 #include "../../include/ddmpc.h"
 
 #include <cmath>
@@ -16,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <new>
@@ -217,7 +219,7 @@ struct Prep {
   int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch;
                                            //     BoxLaw: they iterate like the others and report optimal_inaccurate with a non-empty active set)
   int epoch = 0;                           // stamp of the flags recorded by the factor-export launch (AUTO)
-  bool setpoint = false;                   // DDMPC_OPT_SETPOINT_LAW: S was formed next to the law (d_sgain)
+  bool setpoint = false;                   // DDMPC_OPT_SETPOINT_LAW / _SETPOINT_BOX_LAW: S was formed next to the law (d_sgain)
 };
 
 struct ddmpc_handle {
@@ -294,6 +296,8 @@ struct ddmpc_handle {
   int large_box_law = 0;                   // DDMPC_OPT_LARGE_BOX_LAW: steps of a bounded handle beyond 271 rows on the affine law while inside the box
   int setpoint_law = 0;                    // DDMPC_OPT_SETPOINT_LAW: ddmpc_prepare also forms S = K0^-1 [1_c] (ddmpc_setpoint_law.hpp)
   DevBuf d_sgain, d_sptab;                 // ... S [batch][m+p][r]; the m + p table copies with a unit setpoint (refined columns)
+  int setpoint_box_law = 0;                // DDMPC_OPT_SETPOINT_BOX_LAW: the same on a handle that may carry bounds (ddmpc_setpoint_box_law.hpp); it governs when both are on
+  DevBuf d_chbnd;                          // ... [lo (m+p) | hi (m+p)] per channel, +-infinity without a bound (ddmpc_prepare on Route::BoxLaw)
   DevBuf d_sp, d_uref, d_yref;             // ... staging of host setpoints [u_s | y_s] (ddmpc_step_setpoints) and schedules (ddmpc_closed_loop_setpoints)
   const double *sp_us = nullptr, *sp_ys = nullptr;   // ... the device setpoints of the ddmpc_step_setpoints call in progress
   // input bounds (ddmpc_set_input_bounds) and output bounds (ddmpc_set_output_bounds): per channel, +-infinity = none; the
@@ -335,6 +339,9 @@ static bool prep_valid(const ddmpc_handle* h) { return h->prep.valid && h->prep.
 // DDMPC_OPT_LARGE_BOX_WARM_START, which belongs to the kept factors, the order and the box table (every call that changes one
 // of them comes through here: ddmpc_set_data, ddmpc_set_setpoints, both bounds calls, a new ddmpc_prepare).
 static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; h->last.large_seed = false; }
+
+// ddmpc_prepare forms S and the three setpoint calls are open: DDMPC_OPT_SETPOINT_LAW or DDMPC_OPT_SETPOINT_BOX_LAW is on.
+static bool setpoint_on(const ddmpc_handle* h) { return h->setpoint_law != 0 || h->setpoint_box_law != 0; }
 
 // An option that decides which kernels serve a bounded handle on Route::RobustPhases was set (DDMPC_OPT_LARGE_BOX_CAPACITY,
 // _SAFEGUARD, _WARM_START, _LAW): the next solve may lay the per-instance record out differently, and setting one, to any value,
@@ -926,7 +933,7 @@ int ddmpc_destroy(ddmpc_handle* h) {
                     &h->d_lfac, &h->d_lfacT, &h->d_gain, &h->d_prep_status, &h->d_zero, &h->d_dmat, &h->d_need, &h->d_io, &h->d_rr, &h->d_alpha, &h->d_zws, &h->d_resc, &h->d_xws, &h->d_rflag, &h->d_rrmeta, &h->d_gpre, &h->d_perm, &h->d_rr2d, &h->d_rr2res, &h->d_rr2mt, &h->d_rr2v, &h->d_rr2zp, &h->d_rr2sc, &h->d_wz, &h->d_gz, &h->d_gres, &h->d_zvirt, &h->d_rr3w, &h->d_rr3k, &h->d_large_seed, &h->d_rr_fb, &h->d_rrmeta_fb, &h->d_rr2cand, &h->d_rr2tol, &h->d_rr2rank, &h->d_wd, &h->d_rr2y,
                     &h->d_mcol, &h->d_cwl_tab, &h->d_cwl_sg, &h->d_cwl_ref, &h->d_r3y, &h->d_r3res, &h->d_r3zp, &h->d_r3flag,
                     &h->d_box_bd, &h->d_ubnd, &h->d_ybnd, &h->d_r3bi, &h->d_r3bd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp,
-                    &h->d_box_seed};
+                    &h->d_box_seed, &h->d_sgain, &h->d_sptab, &h->d_sp, &h->d_uref, &h->d_yref, &h->d_chbnd};
   for (DevBuf* b : bufs) b->release();
   h->h_io.release();
   h->h_flag.release();
@@ -1686,9 +1693,12 @@ static int solve_box(ddmpc_handle* h, const double* up, const double* yp, double
     std::swap(h->d_mcol, h->s_mcol); std::swap(h->d_cwl_ref, h->s_cwl_ref);
   };
   const Prep kept = h->prep;
+  const int sp = h->setpoint_law, spb = h->setpoint_box_law;   // (the solve's own preparation forms no S: the kept one stays)
+  h->setpoint_law = h->setpoint_box_law = 0;
   swap_bufs();
   h->prep = Prep{};
   int rc = ddmpc_prepare(h);
+  h->setpoint_law = sp; h->setpoint_box_law = spb;
   if (!rc) {
     begin_solve(h, Route::BoxLaw);
     rc = launch_box_step(h, up, yp, uo, cost, status, iters, false);   // (cold contract: from the empty set; it leaves a seed)
@@ -2499,7 +2509,22 @@ static int prepare_register_resident(ddmpc_handle* h, bool box) {
   }
   h->prep.cwl_nbox = nbox;
   if ((rc = enqueue_gain(h, nf, ncol, col_rho ? col_rho : (const int*)h->d_cwl_tab.p))) return rc;
-  const bool setpoint = h->setpoint_law != 0;     // DDMPC_OPT_SETPOINT_LAW (ROBUST, no box: refinable, no box list)
+  // DDMPC_OPT_SETPOINT_LAW / _SETPOINT_BOX_LAW (ROBUST, refinable): S comes from k0, the empty set's system, and knows no bounds
+  const bool setpoint = setpoint_on(h);
+  if (setpoint && box) {                           // the bounds per channel, for the per-instance refusal of ddmpc_setpoint_box_law.hpp
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> cb(2 * (size_t)k.nch);
+    for (int c = 0; c < k.nch; ++c) {
+      const std::vector<double>& lo = c < k.m ? h->umin_h : h->ymin_h;
+      const std::vector<double>& hi = c < k.m ? h->umax_h : h->ymax_h;
+      const int ch = c < k.m ? c : c - k.m;
+      cb[c] = lo.empty() ? -inf : lo[ch];
+      cb[k.nch + c] = hi.empty() ? inf : hi[ch];
+    }
+    if ((rc = h->d_chbnd.ensure(cb.size() * sizeof(double)))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->d_chbnd.p, cb.data(), cb.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));      // (cb is pageable host memory: the copy has left it)
+  }
   if (setpoint && ((rc = h->d_sgain.ensure(B * (size_t)k.nch * k.r * sizeof(double))) || (rc = enqueue_setpoint_gain(h)))) return rc;
   if (refinable && (k.refine == DDMPC_REFINE_ALWAYS || k.refine == DDMPC_REFINE_AUTO) && (rc = prep_refine_columns(h, k0))) return rc;
   if (setpoint && refinable && (k.refine == DDMPC_REFINE_ALWAYS || k.refine == DDMPC_REFINE_AUTO) &&
@@ -2581,8 +2606,29 @@ int ddmpc_get_gain(ddmpc_handle* h, double* out, int mem) {
 }
 
 // DDMPC_OPT_SETPOINT_LAW: one evaluation of the law and S with the setpoints of the call in progress (h->sp_us / h->sp_ys).
+// DDMPC_OPT_SETPOINT_BOX_LAW on a handle with finite bounds (Route::BoxLaw): one launch of ddmpc_setpoint_box_step_kernel, from the
+// empty set (DDMPC_OPT_BOX_WARM_START is not honoured, and the caller drops the seed with the record of the last solve).
 static int setpoint_step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                                   int32_t* iters) {
+  if (select_route(h) == Route::BoxLaw) {
+    begin_solve(h, Route::BoxLaw);
+    const bool yb = !h->ymin_h.empty();
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0,
+                         h->stream, h->kp, 16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p,
+                         (const double*)h->d_sgain.p, (const int*)h->d_prep_status.p, up, yp, h->sp_us, h->sp_ys, uo, cost,
+                         (int*)status, (int*)iters, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p,
+                         (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                         h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
+                         (int)(h->prm.use_terminal_constraint != 0));
+    };
+    if (yb && h->box_safeguard) launch(ddmpc_setpoint_box_step_kernel<true, true>);
+    else if (yb) launch(ddmpc_setpoint_box_step_kernel<false, true>);
+    else if (h->box_safeguard) launch(ddmpc_setpoint_box_step_kernel<true, false>);
+    else launch(ddmpc_setpoint_box_step_kernel<false, false>);
+    HIP_TRY(hipGetLastError());
+    return DDMPC_OK;
+  }
   begin_solve(h, Route::Cold);
   hipLaunchKernelGGL(ddmpc_setpoint_step_kernel, dim3((unsigned)h->batch), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
                      16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const double*)h->d_sgain.p,
@@ -2594,7 +2640,10 @@ static int setpoint_step_on_route(ddmpc_handle* h, const double* up, const doubl
 int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_past, const double* u_s, const double* y_s,
                          double* u_opt, double* cost, int32_t* status, int32_t* iters, int mem) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
-  if (!h->setpoint_law) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1");
+  if (!setpoint_on(h))
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1)");
+  if (h->bounded && !h->setpoint_box_law)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints on a handle with input or output bounds needs DDMPC_OPT_SETPOINT_BOX_LAW = 1");
   if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_step_setpoints");
   if (!u_s || !y_s) return fail(DDMPC_ERR_INVALID, "null argument");
   if (mem != DDMPC_MEM_HOST && mem != DDMPC_MEM_DEVICE) return fail(DDMPC_ERR_INVALID, "mem must be DDMPC_MEM_HOST or DDMPC_MEM_DEVICE");
@@ -2619,9 +2668,11 @@ int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_
 
 int ddmpc_get_setpoint_gain(ddmpc_handle* h, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
-  if (!h->setpoint_law) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_get_setpoint_gain needs DDMPC_OPT_SETPOINT_LAW = 1");
+  if (!setpoint_on(h))
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_get_setpoint_gain needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1)");
   if (!prep_valid(h) || !h->prep.setpoint)
-    return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare with DDMPC_OPT_SETPOINT_LAW = 1 must be called before ddmpc_get_setpoint_gain");
+    return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare with DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1) must be called before "
+                "ddmpc_get_setpoint_gain");
   HIP_TRY(hipSetDevice(h->device));
   const size_t bytes = (size_t)h->batch * h->kp.nch * h->kp.r * sizeof(double);
   HIP_TRY(hipMemcpyAsync(out, h->d_sgain.p, bytes, mem == DDMPC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
@@ -2761,11 +2812,34 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
         if (h->long_data)
           return fail(DDMPC_ERR_UNSUPPORTED, "%s: N = %d, the trajectory does not fit the LDS of the cold kernel (no refined columns there)", pre,
                       h->prm.N);
-        if (h->bounded)
+        if (h->bounded && !h->setpoint_box_law)     // (with DDMPC_OPT_SETPOINT_BOX_LAW = 1 that option governs)
           return fail(DDMPC_ERR_UNSUPPORTED, "%s is not available on a handle with input or output bounds (the setpoint step knows no bounds)", pre);
       }
       if (h->setpoint_law != value) forget_prep(h);     // (S is part of what ddmpc_prepare keeps)
       h->setpoint_law = value;
+      return DDMPC_OK;
+    case DDMPC_OPT_SETPOINT_BOX_LAW:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_SETPOINT_BOX_LAW must be 0 or 1");
+      if (value == 1) {                                 // (the refusals of DDMPC_OPT_SETPOINT_LAW but the one of bounds)
+        const char* pre = "DDMPC_OPT_SETPOINT_BOX_LAW";
+        if (h->prm.controller_type != DDMPC_ROBUST)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: ROBUST controllers only (a NOMINAL one fixes its outputs to the setpoint as hard rows)", pre);
+        if (h->kp.convex)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: not with the CONVEX slack box (slack NONE only: a slack-only CONVEX handle runs on other kernels, "
+                      "and the offsets of its slack components are not setpoints)", pre);
+        if (h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)", pre);
+        if (h->prm.n * h->kp.nch > WARM_MAX_NF)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: n*(m+p) = %d, the affine law of ddmpc_prepare holds %d", pre, h->prm.n * h->kp.nch, WARM_MAX_NF);
+        if (h->large)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels: beyond them the phase "
+                      "kernels have no M)", pre, h->kp.r);
+        if (h->long_data)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: N = %d, the trajectory does not fit the LDS of the cold kernel (no refined columns there)", pre,
+                      h->prm.N);
+      }
+      if (h->setpoint_box_law != value) forget_prep(h);   // (S is part of what ddmpc_prepare keeps)
+      h->setpoint_box_law = value;
       return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
@@ -2835,7 +2909,7 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
   }
   if (any) {
     if (const char* msg = setpoint_outside_bounds(h, h->us_h.data(), u_min, u_max)) return fail(DDMPC_ERR_INVALID, "u_min / u_max: %s", msg);
-    if (h->setpoint_law)
+    if (h->setpoint_law && !h->setpoint_box_law)
       return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: not with DDMPC_OPT_SETPOINT_LAW = 1 (the setpoint step knows no bounds)");
     if (p.controller_type != DDMPC_ROBUST)
       return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: ROBUST controllers only (a NOMINAL one has no regularised reduced system to iterate on)");
@@ -2904,7 +2978,7 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
   }
   if (any) {
     if (const char* msg = output_setpoint_outside_bounds(h, h->ys_h.data(), y_min, y_max)) return fail(DDMPC_ERR_INVALID, "y_min / y_max: %s", msg);
-    if (h->setpoint_law)
+    if (h->setpoint_law && !h->setpoint_box_law)
       return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: not with DDMPC_OPT_SETPOINT_LAW = 1 (the setpoint step knows no bounds)");
     if (p.controller_type != DDMPC_ROBUST)
       return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: ROBUST controllers only (a NOMINAL one has no regularised reduced system to iterate on)");
@@ -3329,7 +3403,28 @@ static int copy_loop_outputs(ddmpc_handle* h, int mem, const LoopBytes& nb, cons
 
 // DDMPC_OPT_SETPOINT_LAW: the fused loop with a setpoint schedule (a.ns .. a.stacc as for the other fused loops; u_ref / y_ref on
 // the device).  The loop's last solve leaves nothing ddmpc_get_solution could reconstruct.
+// DDMPC_OPT_SETPOINT_BOX_LAW on a handle with finite bounds (Route::BoxLaw): ddmpc_closed_loop_setpoint_box_kernel, from the empty set.
 static int launch_setpoint_loop(ddmpc_handle* h, const LoopArgs& a, const double* u_ref, const double* y_ref) {
+  if (select_route(h) == Route::BoxLaw) {
+    begin_solve(h, Route::BoxLaw);
+    const bool yb = !h->ymin_h.empty();
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0,
+                         h->stream, h->kp, 16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p,
+                         (const double*)h->d_sgain.p, (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps, a.n_mpc_step, a.x, a.up,
+                         a.yp, a.w, u_ref, y_ref, a.usys, a.ysys, a.stacc, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,
+                         (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                         h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
+                         (int)(h->prm.use_terminal_constraint != 0));
+    };
+    if (yb && h->box_safeguard) launch(ddmpc_closed_loop_setpoint_box_kernel<true, true>);
+    else if (yb) launch(ddmpc_closed_loop_setpoint_box_kernel<false, true>);
+    else if (h->box_safeguard) launch(ddmpc_closed_loop_setpoint_box_kernel<true, false>);
+    else launch(ddmpc_closed_loop_setpoint_box_kernel<false, false>);
+    HIP_TRY(hipGetLastError());
+    h->last.setpoint_call = true;
+    return DDMPC_OK;
+  }
   begin_solve(h, Route::Cold);
   hipLaunchKernelGGL(ddmpc_closed_loop_setpoint_kernel, dim3((unsigned)h->batch), dim3(warm_threads(h->kp.r)), 0, h->stream, h->kp,
                      16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const double*)h->d_sgain.p,
@@ -3356,7 +3451,10 @@ int ddmpc_closed_loop_setpoints(ddmpc_handle* h, const ddmpc_plant* plant, int32
                                 double* u_past, double* y_past, const double* w, const double* u_ref, const double* y_ref,
                                 double* u_sys, double* y_sys, int32_t* status, int mem) {
   if (!h || !u_ref || !y_ref) return fail(DDMPC_ERR_INVALID, "null argument");
-  if (!h->setpoint_law) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1");
+  if (!setpoint_on(h))
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1)");
+  if (h->bounded && !h->setpoint_box_law)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints on a handle with input or output bounds needs DDMPC_OPT_SETPOINT_BOX_LAW = 1");
   return closed_loop_impl(h, "ddmpc_closed_loop_setpoints", plant, n_steps, n_mpc_step, x, u_past, y_past, w, u_ref, y_ref, u_sys,
                           y_sys, status, mem);
 }
@@ -3412,7 +3510,7 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
       u_ref = (const double*)h->d_uref.p; y_ref = (const double*)h->d_yref.p;
     }
     if (!prep_valid(h) && (rc = ddmpc_prepare(h))) return rc;
-    h->loop_kernel = "ddmpc_closed_loop_setpoint_kernel";
+    h->loop_kernel = select_route(h) == Route::BoxLaw ? "ddmpc_closed_loop_setpoint_box_kernel" : "ddmpc_closed_loop_setpoint_kernel";
     if ((rc = launch_setpoint_loop(h, a, u_ref, y_ref))) return rc;
     return copy_loop_outputs(h, mem, nb, a, user, status);
   }

@@ -300,10 +300,27 @@ class BatchedDDMPC:
         the LDS, n(m+p) > 256 and a handle with bounds."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_SETPOINT_LAW, 1 if on else 0))
 
+    def set_setpoint_box_law(self, on: bool) -> None:
+        """`set_setpoint_law` for handles that carry input / output bounds (DDMPC_OPT_SETPOINT_BOX_LAW): True = `prepare` forms
+        S next to the law and M, finite bounds are accepted before or after it, and `step_setpoints` / `closed_loop_setpoints` on
+        a bounded handle run the active-set iteration of `step` with the instance's own setpoint in the law, the offsets of the
+        boxed components and the output stage (one launch each; `set_box_safeguard` applies).  Without finite bounds the calls
+        are those of `set_setpoint_law(True)`, bit-equal.  Per instance: a non-finite setpoint is solver_error; with the
+        terminal constraint a setpoint outside the bounds of its channel is infeasible (NaN outputs, iters 0).  `solve`,
+        `step`, `closed_loop`, `gain` and `get_solution` stay bit-equal to False (default).  Changing the value forgets what
+        `prepare` kept.  Raises ERR_UNSUPPORTED on NOMINAL controllers, the CONVEX slack box, dense weights, more than 271 rows,
+        a trajectory beyond the LDS and n(m+p) > 256.  The bounds are the handle's (not per instance), the iteration of the
+        new calls starts from the empty set (`set_box_warm_start` is not honoured), and `get_solution` is not available after
+        them."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_SETPOINT_BOX_LAW, 1 if on else 0))
+
     def step_setpoints(self, u_past, y_past, u_s, y_s, u_opt=None, cost=None, status=None, iters=None):
         """Warm control step with one setpoint per instance (`ddmpc_step_setpoints`): u_s [batch,m], y_s [batch,p], in the
         memory space of the windows; same outputs and array / tensor handling as `solve`.  The handle's own setpoints are not
-        read; `get_solution` is not available after it (until the next `solve` / `step`).  Needs `set_setpoint_law(True)`."""
+        read; `get_solution` is not available after it (until the next `solve` / `step`).  Needs `set_setpoint_law(True)`, or
+        `set_setpoint_box_law(True)`, which a handle with input / output bounds requires: there the step iterates on the box
+        as `step` does (`iters` counts its solves; infeasible with NaN outputs for a setpoint outside the bounds under the
+        terminal constraint)."""
         return self._solve(u_past, y_past, u_opt, cost, status, iters, True, (u_s, y_s))
 
     def setpoint_gain(self) -> np.ndarray:
@@ -314,7 +331,9 @@ class BatchedDDMPC:
 
     def closed_loop_setpoints(self, A, B, Cm, D, x0, u_past, y_past, w, u_ref, y_ref, n_mpc_step: int = 1):
         """`closed_loop` with a setpoint schedule per instance (`ddmpc_closed_loop_setpoints`, one fused launch): u_ref
-        [batch,n_steps,m], y_ref [batch,n_steps,p]; the solve made at step t tracks row t.  Needs `set_setpoint_law(True)`."""
+        [batch,n_steps,m], y_ref [batch,n_steps,p]; the solve made at step t tracks row t.  Needs `set_setpoint_law(True)`, or
+        `set_setpoint_box_law(True)`, which a handle with input / output bounds requires ('ddmpc_closed_loop_setpoint_box_kernel':
+        an instance stops at a solve that is not optimal and at a refused setpoint)."""
         return self.closed_loop(A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step, _ref=(u_ref, y_ref))
 
     def closed_loop(self, A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step: int = 1, _ref=None):
@@ -505,7 +524,8 @@ class BatchedDDMPC:
 
     def closed_loop_kernel_name(self) -> str:
         """The kernel that stepped the plant in the last `closed_loop`: one of the fused loops, or 'ddmpc_plant_kernel'
-        when the loop ran per step; 'ddmpc_closed_loop_setpoint_kernel' after `closed_loop_setpoints`."""
+        when the loop ran per step; 'ddmpc_closed_loop_setpoint_kernel' after `closed_loop_setpoints`
+        ('ddmpc_closed_loop_setpoint_box_kernel' on a handle with bounds)."""
         return self._lib.ddmpc_closed_loop_kernel_name(self._h).decode()
 
 

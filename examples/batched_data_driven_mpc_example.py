@@ -62,7 +62,9 @@ def parse_args():
                     help="with bounds beyond 271 rows: serve the steps that stay inside the box from the affine law, solve only the others")
     ap.add_argument("--setpoint_spread", type=float, default=None,
                     help="instance b tracks its own equilibrium: u_s + S * uniform(-1, 1) (generator seeded with --seed) and the "
-                         "output the plant settles at under it (robust scheme, slack None, no bounds; closed_loop_setpoints)")
+                         "output the plant settles at under it (robust scheme, slack None; closed_loop_setpoints).  Together with "
+                         "--u_min/--u_max or --y_min/--y_max every instance tracks its setpoint inside the box "
+                         "(set_setpoint_box_law; --box_safeguard applies)")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     return ap.parse_args()
 
@@ -124,8 +126,12 @@ def main():
     if a.large_box_law:
         eng.set_large_box_law(True)
     us_b = ys_b = None                           # --setpoint_spread: the setpoints of every instance, [B, m] and [B, p]
+    bounded = a.u_min is not None or a.y_min is not None
     if a.setpoint_spread is not None:
-        eng.set_setpoint_law(True)
+        if bounded:                              # setpoints per instance inside the box: DDMPC_OPT_SETPOINT_BOX_LAW
+            eng.set_setpoint_box_law(True)
+        else:
+            eng.set_setpoint_law(True)
         gain_dc = plant["C"] @ np.linalg.inv(np.eye(plant["A"].shape[0]) - plant["A"]) @ plant["B"] + plant["D"]
         us_b = np.asarray(cfg["u_s"], float) + a.setpoint_spread * np.random.default_rng(a.seed).uniform(-1.0, 1.0, (B, m))
         ys_b = us_b @ gain_dc.T                  # y_s = (C (I - A)^-1 B + D) u_s: an equilibrium of the plant
@@ -152,7 +158,14 @@ def main():
                           slack_type=L.SLACK_CONVEX if cfg["slack"] == "convex" else L.SLACK_NONE,
                           eps_max=cfg["eps_max"], lamb_alpha=cfg["lamb_alpha"], lamb_sigma=cfg["lamb_sigma"],
                           c=cfg["c"], use_terminal_constraint=cfg["tec"], device=a.device) as one:
-            if us_b is not None:
+            if us_b is not None and bounded:
+                one.set_setpoint_box_law(True)
+                if a.u_min is not None:
+                    one.set_input_bounds(a.u_min if len(a.u_min) > 1 else a.u_min[0], a.u_max if len(a.u_max) > 1 else a.u_max[0])
+                if a.y_min is not None:
+                    one.set_output_bounds(a.y_min if len(a.y_min) > 1 else a.y_min[0], a.y_max if len(a.y_max) > 1 else a.y_max[0])
+                one.set_box_safeguard(a.box_safeguard)
+            elif us_b is not None:
                 one.set_setpoint_law(True)
             one.set_data(data["u_d"][:1], data["y_d"][:1])
             U = np.concatenate([data["u_d"][0, -n:], u_sys[0]]); Y = np.concatenate([data["y_d"][0, -n:], y_sys[0]])

@@ -305,7 +305,37 @@ extern "C" {
                                          controllers, with the CONVEX slack box, with DDMPC_WEIGHT_DENSE, beyond 271 rows, on a
                                          trajectory beyond the LDS, with n(m+p) > 256 and on a handle with input or output bounds;
                                          in the reverse order ddmpc_set_input_bounds / ddmpc_set_output_bounds refuse finite bounds
-                                         on a handle with the option on */
+                                         on a handle with the option on (unless DDMPC_OPT_SETPOINT_BOX_LAW = 1, below) */
+#define DDMPC_OPT_SETPOINT_BOX_LAW 19    /* DDMPC_OPT_SETPOINT_LAW for handles that carry input / output bounds (up to 271 rows): 1 =
+                                         ddmpc_prepare forms S next to the law and M = K0^-1 E_box (S comes from the empty set's
+                                         system and knows no bounds; its columns are refined under DDMPC_REFINE_AUTO as those of the
+                                         law are), and ddmpc_step_setpoints / ddmpc_closed_loop_setpoints / ddmpc_get_setpoint_gain
+                                         are open.  M does not depend on the setpoint; per instance the setpoint enters the law, the
+                                         offsets a_s of the boxed components and the target of the output stage.  Without a finite
+                                         bound the calls launch exactly what they launch under DDMPC_OPT_SETPOINT_LAW, bit-equal;
+                                         with finite bounds ddmpc_step_setpoints is one launch of "ddmpc_setpoint_box_step_kernel"
+                                         (law, violation test, the primal-dual iteration of ddmpc_step on M with the same rule,
+                                         max_iter cap and statuses, DDMPC_OPT_BOX_SAFEGUARD honoured, output stage) and
+                                         ddmpc_closed_loop_setpoints one fused launch of "ddmpc_closed_loop_setpoint_box_kernel"
+                                         (n_mpc_step * m > 256: DDMPC_ERR_UNSUPPORTED).  `iters` counts as in ddmpc_step.  Per
+                                         instance: a non-finite setpoint is DDMPC_STATUS_SOLVER_ERROR; with the terminal constraint a
+                                         setpoint outside [u_min, u_max] / [y_min, y_max] of its channel is DDMPC_STATUS_INFEASIBLE
+                                         with u_opt and cost NaN and iters 0 (in the loop the instance stops there); neighbours are
+                                         untouched.  Without the terminal constraint a setpoint outside the box is legitimate.
+                                         Finite bounds are accepted on a handle with the option on, and the option on a bounded
+                                         handle; with DDMPC_OPT_SETPOINT_LAW = 1 as well this option governs, and with only that
+                                         one on the bounds stay refused.  ddmpc_solve, ddmpc_step, ddmpc_closed_loop, ddmpc_get_gain
+                                         and ddmpc_get_solution launch what they launch with 0 and return bit-equal results.
+                                         0 (default).  Values other than 0 / 1: DDMPC_ERR_INVALID.  Changing the value forgets what
+                                         ddmpc_prepare kept.  Setting 1 is DDMPC_ERR_UNSUPPORTED, with a message that names the
+                                         reason, on NOMINAL controllers, with the CONVEX slack box, with DDMPC_WEIGHT_DENSE, beyond
+                                         271 rows (the phase kernels have no M), on a trajectory beyond the LDS and with
+                                         n(m+p) > 256.  LIMITS: the CONVEX slack box stays refused, slack-only or with bounds (a
+                                         slack-only CONVEX handle runs on other kernels; putting it on the box route is a follow-up);
+                                         the bounds are the handle's, not per instance; the iteration of the new calls always starts
+                                         from the empty set (DDMPC_OPT_BOX_WARM_START is not honoured, and the calls drop the seed);
+                                         ddmpc_get_solution after them is DDMPC_ERR_NOT_READY; DDMPC_REFINE_ALWAYS stays refused on
+                                         bounded handles */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -581,7 +611,8 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
                       double* x, double* u_past, double* y_past, const double* w,
                       double* u_sys, double* y_sys, int32_t* status, int mem);
 
-/* Per-instance, per-step setpoints (DDMPC_OPT_SETPOINT_LAW = 1; DDMPC_ERR_UNSUPPORTED on all three calls without it).  The
+/* Per-instance, per-step setpoints (DDMPC_OPT_SETPOINT_LAW = 1, or DDMPC_OPT_SETPOINT_BOX_LAW = 1 -- see there for what the
+ * calls do on a handle with input / output bounds; DDMPC_ERR_UNSUPPORTED on all three calls without either).  The
  * reduced system K0 beta = t is linear in t and t is linear in the setpoints, so with m + p more columns the law of
  * ddmpc_prepare takes the setpoint as an argument:
  *     beta_b = sum_f past_b[f] gain[b][1+f][:] + sum_c s_b[c] S[b][c][:],      s_b = [u_s_b ; y_s_b],
@@ -601,7 +632,8 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
  * ddmpc_get_setpoint_gain: out [batch, m+p, r] doubles = S.  DDMPC_ERR_NOT_READY before a ddmpc_prepare with the option on.
  * ddmpc_get_solution after either of the first two calls is DDMPC_ERR_NOT_READY (the reconstruction reads the shared
  *   setpoint table); a later ddmpc_solve or ddmpc_step makes the solution readable again.
- * LIMITS: ROBUST controllers only; slack NONE (no CONVEX slack box) and no input / output bounds; scalar / diagonal weights;
+ * LIMITS: ROBUST controllers only; slack NONE (no CONVEX slack box) and no input / output bounds (with bounds:
+ *   DDMPC_OPT_SETPOINT_BOX_LAW); scalar / diagonal weights;
  *   at most 271 rows and a trajectory that fits the LDS; n(m+p) <= 256.  The cold kernels know the handle's shared setpoints
  *   only (ddmpc_solve).  Under DDMPC_REFINE_AUTO the instances whose law and S are refined are chosen from solves at the
  *   handle's own setpoints, not at the ones passed later. */
