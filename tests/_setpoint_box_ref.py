@@ -128,3 +128,131 @@ def outside_reference(b):
     t = tank()
     us, ys = outside_setpoints(t)
     return _cached(("outside", b), spec(False), b, us[b], ys[b], u_min=[0.0, 0.0], u_max=[2.0, 2.0])
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The cases the CPU and the GPU tests of the fused loop share (tests/test_setpoint_box_loop_reference.py,
+# tests/test_gpu_setpoint_box_loop.py): the loop of test_gpu_setpoint_box_law._tank_loop (B = 4, 21 steps, a switch at step 10)
+# under other bounds, schedules and caps, and the four-tank with L = 63 (268 rows).  Each reference loop is computed once.
+LOOP_NMS = (1, 4)
+T_SWITCH = 10
+# name: tec = the terminal constraint; bounds; rows = the instances compared with the reference loop; change = what the schedule
+# of _tank_loop becomes from step T_SWITCH on, {instance: (u_ref row, None = that channel unchanged; True = y_ref follows
+# through the dc gain)}; max_iter of the handle (0: the default)
+LOOP_CASES = {
+    "y-only": dict(tec=True, bounds=dict(y_min=[0.5, 0.6], y_max=[0.8, 0.95]), rows=(0, 3), change={}, max_iter=0),
+    "u-and-y": dict(tec=False, bounds=Y_CASES["y-one-sided-u-wide"][1], rows=(0, 3), change={}, max_iter=0),
+    "leaving": dict(tec=False, bounds=dict(u_min=[0.0, 0.0], u_max=[2.0, 2.0]), rows=(1, 3),
+                    change={1: ([2.3, None], False), 3: ([2.3, None], False)}, max_iter=0),
+    "tight-terminal": dict(tec=True, bounds=dict(u_min=[0.0, 0.0], u_max=[2.0, 2.0]), rows=(0, 3), change={}, max_iter=0),
+    "refused": dict(tec=True, bounds=dict(u_min=[0.0, 0.0], u_max=[2.0, 2.0]), rows=(1,), change={1: ([2.3, None], False)},
+                    max_iter=0),
+    "cap": dict(tec=True, bounds=dict(u_min=[-4.0, -4.0], u_max=[6.0, 6.0]), rows=(1,), change={1: ([3.0, 3.0], True)},
+                max_iter=6),
+    "u-and-y-cap": dict(tec=False, bounds=Y_CASES["y-one-sided-u-wide"][1], rows=(0, 3), change={}, max_iter=3),
+}
+
+
+# loop and step on identical problems (n_steps = n_mpc_step = 4, the schedule constant at a row of the case's schedule, the
+# data-tail windows): (case, schedule row, safeguard on); together the four <SAFE, YB> instantiations of the loop kernel
+LOOP_TWINS = [("y-only", 0, False), ("u-and-y", 0, False), ("leaving", 0, False), ("leaving", 20, False), ("cap", 20, True),
+              ("u-and-y-cap", 0, True)]
+
+
+def t_stop(nms):
+    """The step of the first solve at or after the switch: where an instance whose schedule goes bad at T_SWITCH stops."""
+    return -(-T_SWITCH // nms) * nms
+
+
+def dc_gain(pl):
+    A, Bm, Cm, D = (np.asarray(pl[k], float) for k in ("A", "B", "C", "D"))
+    return Cm @ np.linalg.inv(np.eye(A.shape[0]) - A) @ Bm + D
+
+
+def loop_case(name):
+    """(case, u_ref, y_ref) of test_gpu_setpoint_box_law._tank_loop with the case's terminal constraint and schedule."""
+    if ("loop-case", name) not in _CACHE:
+        from test_gpu_setpoint_box_law import _tank_loop      # (that module imports this one)
+        case, u_ref, y_ref = _tank_loop()
+        c = LOOP_CASES[name]
+        u_ref, y_ref = u_ref.copy(), y_ref.copy()
+        for b, (row, follow) in c["change"].items():
+            for ch, v in enumerate(row):
+                if v is not None:
+                    u_ref[b, T_SWITCH:, ch] = v
+            if follow:
+                y_ref[b] = u_ref[b] @ dc_gain(case["plant"]).T
+        _CACHE["loop-case", name] = (dict(case, spec=spec(c["tec"])), u_ref, y_ref)
+    return _CACHE["loop-case", name]
+
+
+def loop_reference(name, b, nms, steps=None):
+    """(u_sys, y_sys, x_end, u_past_end, y_past_end, sols) of instance b of the case; steps: the loop cut after so many steps."""
+    key = ("loop", name, b, nms, steps)
+    if key not in _CACHE:
+        from test_gpu_setpoint_box_law import _ref_loop
+        case, u_ref, y_ref = loop_case(name)
+        if steps is not None:
+            case = dict(case, w=case["w"][:, :steps])
+        _CACHE[key] = _ref_loop(case, b, u_ref[b][:steps], y_ref[b][:steps], nms, LOOP_CASES[name]["bounds"])
+    return _CACHE[key]
+
+
+def n_input_box(spec_, bounds):
+    """How many of the helper's boxed components are inputs (they come first in BoundedSolution.active)."""
+    if bounds.get("u_min") is None:
+        return 0
+    lo = np.broadcast_to(np.asarray(bounds["u_min"], float), (spec_.m,))
+    hi = np.broadcast_to(np.asarray(bounds["u_max"], float), (spec_.m,))
+    return (spec_.L - spec_.n if spec_.tec else spec_.L) * int(np.count_nonzero(np.isfinite(lo) | np.isfinite(hi)))
+
+
+def active_counts(spec_, bounds, sol):
+    """(active inputs, active outputs) of a BoundedSolution."""
+    k = n_input_box(spec_, bounds)
+    return int(np.count_nonzero(sol.active[:k])), int(np.count_nonzero(sol.active[k:]))
+
+
+# The largest shape: four-tank, L = 63 (4 (63 + 4) = 268 rows), seeds 500 .. 503, data-tail windows, setpoints as in tank().
+BIG_L, BIG_B, BIG_STEPS, BIG_NMS = 63, 4, 6, 2
+# name: (terminal constraint, bounds, length of the box list)
+BIG_CASES = {
+    "u-tight": (False, dict(u_min=[0.0, 0.0], u_max=[2.0, 2.0]), 126),
+    "u-wide-y-one-sided": (True, dict(u_min=[-4.0, -4.0], u_max=[6.0, 6.0], y_min=[-INF, 0.4], y_max=[1.0, INF]), 236),
+}
+
+
+def big_spec(tec):
+    return orc.spec_from_params(slack_var_constraint_type=0, tec=tec, L=BIG_L)
+
+
+def big():
+    if "big" not in _CACHE:
+        t, s = tank(), big_spec(True)
+        w = s.eps_max * np.random.default_rng(12).uniform(-1.0, 1.0, (BIG_B, BIG_STEPS, s.p))
+        rng = np.random.default_rng(11)
+        us = s.u_s + rng.uniform(-0.5, 0.5, (BIG_B, s.m))
+        ys = s.y_s + rng.uniform(-0.2, 0.2, (BIG_B, s.p))
+        _CACHE["big"] = dict(plant=orc.FOUR_TANK, B=BIG_B, w=w, us=us, ys=ys, x0=t["x_end"][:BIG_B].copy(),
+                             **{k: t[k][:BIG_B] for k in ("u_d", "y_d", "up", "yp")})
+    return _CACHE["big"]
+
+
+def big_step_reference(name, b):
+    tec, bounds, _ = BIG_CASES[name]
+    key = ("big-step", name, b)
+    if key not in _CACHE:
+        t = big()
+        _CACHE[key] = solve(big_spec(tec), t["u_d"][b], t["y_d"][b], t["up"][b], t["yp"][b], t["us"][b], t["ys"][b], **bounds)
+    return _CACHE[key]
+
+
+def big_loop_reference(name, b):
+    tec, bounds, _ = BIG_CASES[name]
+    key = ("big-loop", name, b)
+    if key not in _CACHE:
+        from test_gpu_setpoint_box_law import _ref_loop
+        t = big()
+        _CACHE[key] = _ref_loop(dict(t, spec=big_spec(tec)), b, np.tile(t["us"][b], (BIG_STEPS, 1)), np.tile(t["ys"][b], (BIG_STEPS, 1)),
+                                BIG_NMS, bounds)
+    return _CACHE[key]
