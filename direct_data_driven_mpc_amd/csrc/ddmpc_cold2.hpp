@@ -18,7 +18,10 @@
 //     DPP reduction) into LDS, then every wave forms x_J = M_J' (y_J - parts) redundantly from the M tiles in LDS.
 //   * the panel wave's chain (four 4-wide sub-steps per diagonal tile) is the critical path: the other waves' TRSM and
 //     trailing updates of step J run beside the factorisation of diagonal tile J+1 (its update with panel J comes first),
-//     and diagonal tile 0 is factored beside the other waves' Gram walks.
+//     and diagonal tile 0 is factored beside the other waves' Gram walks.  The walks down the tile diagonals (structured
+//     Gram) are unrolled, the operands of the next step in flight under the two MFMAs of the current one: in front of the
+//     loop every wave is as long as the panel wave's stretch to the barrier behind the fix-up, so cycles
+//     taken out of every wave's walk count, and work moved from the panel wave to the helpers does not.
 //   * the beta / active-set workspace is written only when asked for (ddmpc_get_solution re-solves on demand).
 //
 // Reference formulation: direct_data_driven_mpc_controller.py:409-445 (variables), :506-677 (constraints),
@@ -683,26 +686,37 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
       static_for<NT>([&](auto DD) __attribute__((always_inline)) {
         constexpr int d = DD;
         if constexpr (TM::tab.wave[d] == WAVE && d + 1 < NT) {
+          // Unrolled, the operands of step t + 1 on their way under the MFMAs of step t (a runtime loop over t that dispatched
+          // to the tile's registers took a load, its wait and two dependent MFMAs per trip, one after the other: ~570 cycles
+          // per step for a workgroup alone on a CU).  The MFMA sequence of every tile is unchanged.
           const double* pb = xs + 4 * l4 + l15;          // rows of tile column J = t: the A operand (k side)
           const double* pa = pb + 16 * d;                // rows of tile row I = d + t: the B operand (i side)
-          const int c = csub(0);
-#pragma nounroll
-          for (int t = 0; t + 1 < NT - d; ++t) {
-            const double a1 = pa[0], b1 = pb[0], a2 = pa[4 * c], b2 = pb[4 * c];
-            double a3 = 0.0, b3 = 0.0, a4 = 0.0, b4 = 0.0;
-            if (nsub == 2) { const int c1 = csub(1); a3 = pa[2]; b3 = pb[2]; a4 = pa[2 + 4 * c1]; b4 = pb[2 + 4 * c1]; }   // (kernel-uniform)
+          auto walk = [&](auto NSUB) __attribute__((always_inline)) {
+            constexpr bool two = NSUB() == 2;
+            const double* pa2 = pa + 4 * csub(0);
+            const double* pb2 = pb + 4 * csub(0);
+            const double* pa4 = pa + 2 + 4 * csub(1);
+            const double* pb4 = pb + 2 + 4 * csub(1);
+            double n_a1 = pa[0], n_b1 = pb[0], n_a2 = pa2[0], n_b2 = pb2[0];
+            double n_a3 = 0.0, n_b3 = 0.0, n_a4 = 0.0, n_b4 = 0.0;
+            if constexpr (two) { n_a3 = pa[2]; n_b3 = pb[2]; n_a4 = pa4[0]; n_b4 = pb4[0]; }
             static_for<NT - d - 1>([&](auto T) __attribute__((always_inline)) {
-              if (t == T) {
-                d4 v = __builtin_amdgcn_mfma_f64_16x16x4f64(-b1, a1, acc[TM::slot(d + T, T)], 0, 0, 0);
-                if (nsub == 2) {
-                  v = __builtin_amdgcn_mfma_f64_16x16x4f64(-b3, a3, v, 0, 0, 0);
-                  v = __builtin_amdgcn_mfma_f64_16x16x4f64(b4, a4, v, 0, 0, 0);
-                }
-                acc[TM::slot(d + T + 1, T + 1)] = __builtin_amdgcn_mfma_f64_16x16x4f64(b2, a2, v, 0, 0, 0);
+              const double a1 = n_a1, b1 = n_b1, a2 = n_a2, b2 = n_b2, a3 = n_a3, b3 = n_b3, a4 = n_a4, b4 = n_b4;
+              if constexpr (T() + 1 < NT - d - 1) {
+                constexpr int o = 16 * (T() + 1);
+                n_a1 = pa[o]; n_b1 = pb[o]; n_a2 = pa2[o]; n_b2 = pb2[o];
+                if constexpr (two) { n_a3 = pa[o + 2]; n_b3 = pb[o + 2]; n_a4 = pa4[o]; n_b4 = pb4[o]; }
               }
+              d4 v = __builtin_amdgcn_mfma_f64_16x16x4f64(-b1, a1, acc[TM::slot(d + T, T)], 0, 0, 0);
+              if constexpr (two) {
+                v = __builtin_amdgcn_mfma_f64_16x16x4f64(-b3, a3, v, 0, 0, 0);
+                v = __builtin_amdgcn_mfma_f64_16x16x4f64(b4, a4, v, 0, 0, 0);
+              }
+              acc[TM::slot(d + T + 1, T + 1)] = __builtin_amdgcn_mfma_f64_16x16x4f64(b2, a2, v, 0, 0, 0);
             });
-            pa += 16; pb += 16;
-          }
+          };
+          if (nsub == 2) walk(std::integral_constant<int, 2>{});   // (kernel-uniform)
+          else walk(std::integral_constant<int, 1>{});
         }
       });
       // (4) panel wave: its walk is short (one diagonal); diagonal tile 0 is fixed up and factored NOW, beside the other
@@ -736,6 +750,14 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
         acc[S] = fix_tile(std::integral_constant<int, I>{}, std::integral_constant<int, J>{}, acc[S], I == J ? dgv[J] : 0.0);
     });
     const long long tfx1 = now();
+    if constexpr (W > 1 && WAVE >= 1 && WAVE <= 3) {
+      // diagnostics: when helper wave 1..3 reaches the barrier behind the fix-up -- the low 32 bits of its clock in the upper
+      // half of slot 6 + WAVE (the panel wave ORs its sums into the lower halves behind the factorisation).  Stored at once.
+      if (stamps != nullptr) {
+        const unsigned long long th = __builtin_amdgcn_s_memtime();
+        if (lane == 0) stamps[6 + WAVE] = th << 32;
+      }
+    }
     __syncthreads();      // every wave has read tvec (targets) for its rhs entries; LT / PT2 / PB are free
     if constexpr (!CVX) {
       // diagnostics: the panel wave's cycles in the fix-up of its tiles and at the barrier behind it -- the part of stamp 3 -> 4
@@ -913,9 +935,11 @@ __device__ __forceinline__ void wave_body2(const KParams& P, double* __restrict_
       }
     });
     if (timing && threadIdx.x == 0) {
-      stamps[7] = tphF; stamps[8] = tphB;
-      if constexpr (CVX) { stamps[9] = 0; stamps[10] = 0; stamps[11] = 0; }         // (the rank-k update's three phases go there)
-      else { stamps[9] = tphT; stamps[10] += tphA; stamps[11] += tphU; }            // (upper halves: the fix-up split, written above)
+      // (upper halves of slots 7..9: the helpers' arrival at the barrier behind the fix-up, stored there)
+      constexpr unsigned long long HI = 0xffffffff00000000ull;
+      stamps[7] = (stamps[7] & HI) | (unsigned long long)tphF; stamps[8] = (stamps[8] & HI) | (unsigned long long)tphB;
+      if constexpr (CVX) { stamps[9] &= HI; stamps[10] = 0; stamps[11] = 0; }       // (the rank-k update's three phases go there)
+      else { stamps[9] = (stamps[9] & HI) | (unsigned long long)tphT; stamps[10] += tphA; stamps[11] += tphU; }
     }
     stamp();   // 4
 

@@ -39,7 +39,7 @@ def run(tag, B, Lh, N, slack, upd, reps=50):
             two = it == 2
             tot = st[:, 14] - st[:, 0]
             print("   cycles per workgroup: 1 iteration %.0f | 2 iterations %.0f; of the second (update=%s): forward %.0f  k x k %.0f  back %.0f"
-                  % (np.median(tot[~two]), np.median(tot[two]), upd, np.median(st[two, 9]), np.median(st[two, 10]), np.median(st[two, 11])), flush=True)
+                  % (np.median(tot[~two]), np.median(tot[two]), upd, np.median(st[two, 9] & 0xffffffff), np.median(st[two, 10]), np.median(st[two, 11])), flush=True)   # (upper half of slot 9: a helper's stamp)
         print("%-22s %s B=%5d  %7.1f us  %.3e solves/s  iters mean %.3f max %d  non-optimal %d" % (
             tag, eng.kernel_name(), B, ms * 1e3, B / ms * 1e3, it.mean(), it.max(), int((out[2] != 0).sum().item())), flush=True)
         return out[0].cpu().numpy(), it

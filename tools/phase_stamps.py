@@ -40,4 +40,24 @@ for i, nm in enumerate(["chol: panel wave in-tile factorisation (+ its diag upda
 fx, fw = st[:, 10] >> 32, st[:, 11] >> 32
 print("%-60s median %8.0f  p10 %8.0f  p90 %8.0f cycles (wave 0)" % ("fix-up: panel wave's own tiles", np.median(fx), np.percentile(fx, 10), np.percentile(fx, 90)))
 print("%-60s median %8.0f  p10 %8.0f  p90 %8.0f cycles (wave 0)" % ("fix-up: wait at the barrier behind it", np.median(fw), np.percentile(fw, 10), np.percentile(fw, 90)))
+# behind the barrier that publishes the lag blocks (stamp 2): when each wave is done with what it has to do ahead of the barrier
+# behind the fix-up -- the panel wave at the end of diagonal tile 0's factorisation (stamp 3), helper waves 1..3 on reaching
+# that barrier (low 32 bits of their clock in the upper halves of slots 7..9; zero where the instance has no such wave)
+t2 = st[:, 2] & 0xffffffff
+w0 = st[:, 3] - st[:, 2]
+print("%-60s median %8.0f  p10 %8.0f  p90 %8.0f cycles" % ("stamp 2 -> panel wave: tile 0 factored", np.median(w0), np.percentile(w0, 10), np.percentile(w0, 90)))
+arr = []
+for w in (1, 2, 3):
+    hi = st[:, 6 + w] >> 32
+    if not hi.any():
+        continue
+    a = (hi - t2) & 0xffffffff
+    arr.append(a)
+    print("%-60s median %8.0f  p10 %8.0f  p90 %8.0f cycles" % ("stamp 2 -> helper wave %d at the barrier behind the fix-up" % w, np.median(a), np.percentile(a, 10), np.percentile(a, 90)))
+if arr:
+    arr = np.stack(arr, axis=1)
+    bar = w0 + fx                       # the panel wave's own arrival at that barrier
+    sl_first, sl_last = bar - arr.min(axis=1), bar - arr.max(axis=1)
+    print("%-60s median %8.0f  p10 %8.0f  p90 %8.0f cycles" % ("slack at that barrier: earliest helper", np.median(sl_first), np.percentile(sl_first, 10), np.percentile(sl_first, 90)))
+    print("%-60s median %8.0f  p10 %8.0f  p90 %8.0f cycles" % ("slack at that barrier: latest helper", np.median(sl_last), np.percentile(sl_last, 10), np.percentile(sl_last, 90)))
 print("span first entry -> last exit: %.1f us" % ((st[:, 13].max() - st[:, 15].min()) * 10.0 / 1e3))
