@@ -1,4 +1,4 @@
-// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_setpoint_law.hpp, ddmpc_setpoint_box_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp, ddmpc_rr3_box.hpp).
+// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_setpoint_law.hpp, ddmpc_setpoint_box_law.hpp, ddmpc_setpoint_convex_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp, ddmpc_rr3_box.hpp).
 // Host-side responsibilities: parameter validation with the reference's error
 // conditions (direct_data_driven_mpc_controller.py:165-168,211-222,298-343,664-670),
 // device buffer ownership, kernel-instance selection, launch.
@@ -10,6 +10,7 @@
 #include "ddmpc_box_law.hpp"
 #include "ddmpc_setpoint_law.hpp"
 #include "ddmpc_setpoint_box_law.hpp"
+#include "ddmpc_setpoint_convex_law.hpp"
 #include "../../include/ddmpc.h"
 
 #include <cmath>
@@ -219,7 +220,7 @@ struct Prep {
   int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch;
                                            //     BoxLaw: they iterate like the others and report optimal_inaccurate with a non-empty active set)
   int epoch = 0;                           // stamp of the flags recorded by the factor-export launch (AUTO)
-  bool setpoint = false;                   // DDMPC_OPT_SETPOINT_LAW / _SETPOINT_BOX_LAW: S was formed next to the law (d_sgain)
+  bool setpoint = false;                   // DDMPC_OPT_SETPOINT_LAW / _SETPOINT_BOX_LAW / _SETPOINT_CONVEX_LAW: S was formed next to the law (d_sgain)
 };
 
 struct ddmpc_handle {
@@ -298,6 +299,8 @@ struct ddmpc_handle {
   DevBuf d_sgain, d_sptab;                 // ... S [batch][m+p][r]; the m + p table copies with a unit setpoint (refined columns)
   int setpoint_box_law = 0;                // DDMPC_OPT_SETPOINT_BOX_LAW: the same on a handle that may carry bounds (ddmpc_setpoint_box_law.hpp); it governs when both are on
   DevBuf d_chbnd;                          // ... [lo (m+p) | hi (m+p)] per channel, +-infinity without a bound (ddmpc_prepare on Route::BoxLaw)
+  int setpoint_convex_law = 0;             // DDMPC_OPT_SETPOINT_CONVEX_LAW: the same under the CONVEX slack box, slack-only or bounded (ddmpc_setpoint_convex_law.hpp);
+                                           //   never on together with the two above (they refuse CONVEX, this one slack NONE)
   DevBuf d_sp, d_uref, d_yref;             // ... staging of host setpoints [u_s | y_s] (ddmpc_step_setpoints) and schedules (ddmpc_closed_loop_setpoints)
   const double *sp_us = nullptr, *sp_ys = nullptr;   // ... the device setpoints of the ddmpc_step_setpoints call in progress
   // input bounds (ddmpc_set_input_bounds) and output bounds (ddmpc_set_output_bounds): per channel, +-infinity = none; the
@@ -340,8 +343,11 @@ static bool prep_valid(const ddmpc_handle* h) { return h->prep.valid && h->prep.
 // of them comes through here: ddmpc_set_data, ddmpc_set_setpoints, both bounds calls, a new ddmpc_prepare).
 static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; h->last.large_seed = false; }
 
-// ddmpc_prepare forms S and the three setpoint calls are open: DDMPC_OPT_SETPOINT_LAW or DDMPC_OPT_SETPOINT_BOX_LAW is on.
-static bool setpoint_on(const ddmpc_handle* h) { return h->setpoint_law != 0 || h->setpoint_box_law != 0; }
+// ddmpc_prepare forms S and the three setpoint calls are open: DDMPC_OPT_SETPOINT_LAW, _SETPOINT_BOX_LAW or _SETPOINT_CONVEX_LAW is on.
+static bool setpoint_on(const ddmpc_handle* h) { return h->setpoint_law != 0 || h->setpoint_box_law != 0 || h->setpoint_convex_law != 0; }
+// DDMPC_OPT_SETPOINT_CONVEX_LAW on a slack-only CONVEX handle (Route::Cold): ddmpc_prepare forms the slack box list with its
+// [a | c | lo | hi | 1/d] table and M for the setpoint calls, whether or not DDMPC_OPT_CONVEX_WARM_LAW is on.
+static bool setpoint_convex_slack_only(const ddmpc_handle* h) { return h->setpoint_convex_law != 0 && h->kp.convex && !h->large && !h->bounded; }
 
 // An option that decides which kernels serve a bounded handle on Route::RobustPhases was set (DDMPC_OPT_LARGE_BOX_CAPACITY,
 // _SAFEGUARD, _WARM_START, _LAW): the next solve may lay the per-instance record out differently, and setting one, to any value,
@@ -1693,12 +1699,12 @@ static int solve_box(ddmpc_handle* h, const double* up, const double* yp, double
     std::swap(h->d_mcol, h->s_mcol); std::swap(h->d_cwl_ref, h->s_cwl_ref);
   };
   const Prep kept = h->prep;
-  const int sp = h->setpoint_law, spb = h->setpoint_box_law;   // (the solve's own preparation forms no S: the kept one stays)
-  h->setpoint_law = h->setpoint_box_law = 0;
+  const int sp = h->setpoint_law, spb = h->setpoint_box_law, spc = h->setpoint_convex_law;   // (the solve's own preparation forms no S: the kept one stays)
+  h->setpoint_law = h->setpoint_box_law = h->setpoint_convex_law = 0;
   swap_bufs();
   h->prep = Prep{};
   int rc = ddmpc_prepare(h);
-  h->setpoint_law = sp; h->setpoint_box_law = spb;
+  h->setpoint_law = sp; h->setpoint_box_law = spb; h->setpoint_convex_law = spc;
   if (!rc) {
     begin_solve(h, Route::BoxLaw);
     rc = launch_box_step(h, up, yp, uo, cost, status, iters, false);   // (cold contract: from the empty set; it leaves a seed)
@@ -2266,8 +2272,9 @@ struct BoxList {
   std::vector<double> bd;      // Route::BoxLaw: [a | c | lo | hi | 1/d] per boxed component
 };
 static BoxList build_box_list(const KParams& k, int RP, const std::vector<int>& ti, const std::vector<double>& td,
-                              const double* umin, const double* umax, const double* ymin = nullptr, const double* ymax = nullptr) {
-  const bool box = umin != nullptr || ymin != nullptr;
+                              const double* umin, const double* umax, const double* ymin = nullptr, const double* ymax = nullptr,
+                              bool slack_bd = false) {
+  const bool box = umin != nullptr || ymin != nullptr || slack_bd;     // (slack_bd: the table of a slack-only list, DDMPC_OPT_SETPOINT_CONVEX_LAW)
   BoxList bl;
   std::vector<int>& tab = bl.tab;
   std::vector<int> box_of((size_t)k.r, -1), box_ofy, col, col_rho;
@@ -2485,7 +2492,8 @@ static int prepare_register_resident(ddmpc_handle* h, bool box) {
   const bool refinable = k.lam != 0.0;
   if (refinable && k.refine == DDMPC_REFINE_AUTO && (rc = prep_probe_tail(h, k0))) return rc;
   if (B * (size_t)(NT * (NT + 1) / 2) > 0x7fffffffULL) return fail(DDMPC_ERR_INVALID, "batch too large for ddmpc_prepare");
-  const bool cwl = convex_warm_on(h) || box;
+  const bool spc = !box && setpoint_convex_slack_only(h);   // (the slack-only list with its table, for the setpoint calls alone)
+  const bool cwl = convex_warm_on(h) || box || spc;
   int nbox = 0, ncol = 0;
   const int* col_rho = nullptr;                    // output bounds: the rows of M's columns (the end of the table)
   if (cwl) {
@@ -2493,15 +2501,16 @@ static int prepare_register_resident(ddmpc_handle* h, bool box) {
     std::vector<int> ti;
     std::vector<double> td;
     if (box) HIP_TRY(hipStreamSynchronize(h->stream));     // (a step in flight may still read the tables written below)
-    if ((rc = read_table(h->d_tabi, 3 * (size_t)RP, &ti)) || (box && (rc = read_table(h->d_tabd, 4 * (size_t)RP, &td)))) return rc;
+    if (spc) HIP_TRY(hipStreamSynchronize(h->stream));     // (a setpoint step in flight may still read d_box_bd)
+    if ((rc = read_table(h->d_tabi, 3 * (size_t)RP, &ti)) || ((box || spc) && (rc = read_table(h->d_tabd, 4 * (size_t)RP, &td)))) return rc;
     const bool ub = box && !h->umin_h.empty(), yb = box && !h->ymin_h.empty();
     const BoxList bl = build_box_list(k, RP, ti, td, ub ? h->umin_h.data() : nullptr, ub ? h->umax_h.data() : nullptr,
-                                      yb ? h->ymin_h.data() : nullptr, yb ? h->ymax_h.data() : nullptr);
+                                      yb ? h->ymin_h.data() : nullptr, yb ? h->ymax_h.data() : nullptr, spc);
     // (thread s of the box kernels looks at component s, and the LDS arrays by component hold WARM_MAX_R entries)
     if (bl.nbox > WARM_MAX_R)
       return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: the box list has %d components (slack, input and output), the kernels hold %d",
                   bl.nbox, WARM_MAX_R);
-    if ((rc = upload_box_list(h, bl, box))) return rc;
+    if ((rc = upload_box_list(h, bl, box || spc))) return rc;
     nbox = bl.nbox;
     ncol = bl.ncol;
     if (yb) col_rho = (const int*)h->d_cwl_tab.p + 2 * (nbox + k.r) + 1;
@@ -2509,9 +2518,9 @@ static int prepare_register_resident(ddmpc_handle* h, bool box) {
   }
   h->prep.cwl_nbox = nbox;
   if ((rc = enqueue_gain(h, nf, ncol, col_rho ? col_rho : (const int*)h->d_cwl_tab.p))) return rc;
-  // DDMPC_OPT_SETPOINT_LAW / _SETPOINT_BOX_LAW (ROBUST, refinable): S comes from k0, the empty set's system, and knows no bounds
+  // DDMPC_OPT_SETPOINT_LAW / _SETPOINT_BOX_LAW / _SETPOINT_CONVEX_LAW (ROBUST, refinable): S comes from k0, the empty set's system, and knows no bounds
   const bool setpoint = setpoint_on(h);
-  if (setpoint && box) {                           // the bounds per channel, for the per-instance refusal of ddmpc_setpoint_box_law.hpp
+  if (setpoint && (box || spc)) {                  // the bounds per channel, for the per-instance refusal of ddmpc_setpoint_box_law.hpp
     const double inf = std::numeric_limits<double>::infinity();
     std::vector<double> cb(2 * (size_t)k.nch);
     for (int c = 0; c < k.nch; ++c) {
@@ -2610,6 +2619,28 @@ int ddmpc_get_gain(ddmpc_handle* h, double* out, int mem) {
 // empty set (DDMPC_OPT_BOX_WARM_START is not honoured, and the caller drops the seed with the record of the last solve).
 static int setpoint_step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                                   int32_t* iters) {
+  if (h->setpoint_convex_law) {
+    // DDMPC_OPT_SETPOINT_CONVEX_LAW: ddmpc_setpoint_convex_step_kernel on the box list ddmpc_prepare kept -- the slack components
+    // alone (Route::Cold; no safeguard: the slack box does not cycle) or next to the bounded inputs / outputs (Route::BoxLaw)
+    const Route route = select_route(h);
+    begin_solve(h, route);
+    const bool yb = !h->ymin_h.empty(), safe = route == Route::BoxLaw && h->box_safeguard;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0,
+                         h->stream, h->kp, 16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p,
+                         (const double*)h->d_sgain.p, (const int*)h->d_prep_status.p, up, yp, h->sp_us, h->sp_ys, uo, cost,
+                         (int*)status, (int*)iters, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p,
+                         (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                         h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
+                         (int)(h->prm.use_terminal_constraint != 0));
+    };
+    if (yb && safe) launch(ddmpc_setpoint_convex_step_kernel<true, true>);
+    else if (yb) launch(ddmpc_setpoint_convex_step_kernel<false, true>);
+    else if (safe) launch(ddmpc_setpoint_convex_step_kernel<true, false>);
+    else launch(ddmpc_setpoint_convex_step_kernel<false, false>);
+    HIP_TRY(hipGetLastError());
+    return DDMPC_OK;
+  }
   if (select_route(h) == Route::BoxLaw) {
     begin_solve(h, Route::BoxLaw);
     const bool yb = !h->ymin_h.empty();
@@ -2641,8 +2672,8 @@ int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_
                          double* u_opt, double* cost, int32_t* status, int32_t* iters, int mem) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
   if (!setpoint_on(h))
-    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1)");
-  if (h->bounded && !h->setpoint_box_law)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box)");
+  if (h->bounded && !h->setpoint_box_law && !h->setpoint_convex_law)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints on a handle with input or output bounds needs DDMPC_OPT_SETPOINT_BOX_LAW = 1");
   if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_step_setpoints");
   if (!u_s || !y_s) return fail(DDMPC_ERR_INVALID, "null argument");
@@ -2669,7 +2700,7 @@ int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_
 int ddmpc_get_setpoint_gain(ddmpc_handle* h, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
   if (!setpoint_on(h))
-    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_get_setpoint_gain needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1)");
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_get_setpoint_gain needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box)");
   if (!prep_valid(h) || !h->prep.setpoint)
     return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare with DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1) must be called before "
                 "ddmpc_get_setpoint_gain");
@@ -2840,6 +2871,38 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       }
       if (h->setpoint_box_law != value) forget_prep(h);   // (S is part of what ddmpc_prepare keeps)
       h->setpoint_box_law = value;
+      return DDMPC_OK;
+    case DDMPC_OPT_SETPOINT_CONVEX_LAW:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_SETPOINT_CONVEX_LAW must be 0 or 1");
+      if (value == 1) {                                 // (CONVEX only, so never on together with options 18 / 19, which refuse it)
+        const char* pre = "DDMPC_OPT_SETPOINT_CONVEX_LAW";
+        if (h->prm.controller_type != DDMPC_ROBUST)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: ROBUST controllers only (a NOMINAL one fixes its outputs to the setpoint as hard rows)", pre);
+        if (!h->kp.convex)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: the CONVEX slack box only (slack NONE: DDMPC_OPT_SETPOINT_LAW, or DDMPC_OPT_SETPOINT_BOX_LAW "
+                      "with input / output bounds)", pre);
+        if (h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)", pre);
+        if (h->prm.n * h->kp.nch > WARM_MAX_NF)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: n*(m+p) = %d, the affine law of ddmpc_prepare holds %d", pre, h->prm.n * h->kp.nch, WARM_MAX_NF);
+        if (h->large)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels: beyond them the phase "
+                      "kernels have no M)", pre, h->kp.r);
+        if (h->long_data)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: N = %d, the trajectory does not fit the LDS of the cold kernel (no refined columns there)", pre,
+                      h->prm.N);
+        // every slack component must change its diagonal entry at the bound (d_s > 0), the rule of DDMPC_OPT_CONVEX_WARM_LAW
+        const int RP = 16 * h->kc.NT;
+        std::vector<double> td;
+        std::vector<int> ti;
+        if (int rc = read_table(h->d_tabd, 4 * (size_t)RP, &td)) return rc;
+        if (int rc = read_table(h->d_tabi, 3 * (size_t)RP, &ti)) return rc;
+        for (int rho = 0; rho < h->kp.r; ++rho)
+          if ((ti[rho] == K_WPRED || ti[rho] == K_WTERM) && !(td[rho] - td[RP + rho] > 0.0))
+            return fail(DDMPC_ERR_UNSUPPORTED, "%s: a boxed output component has no weight (Q entry 0)", pre);
+      }
+      if (h->setpoint_convex_law != value) forget_prep(h);   // (S, and on a slack-only handle the box list and M, are part of what ddmpc_prepare keeps)
+      h->setpoint_convex_law = value;
       return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
@@ -3405,6 +3468,27 @@ static int copy_loop_outputs(ddmpc_handle* h, int mem, const LoopBytes& nb, cons
 // the device).  The loop's last solve leaves nothing ddmpc_get_solution could reconstruct.
 // DDMPC_OPT_SETPOINT_BOX_LAW on a handle with finite bounds (Route::BoxLaw): ddmpc_closed_loop_setpoint_box_kernel, from the empty set.
 static int launch_setpoint_loop(ddmpc_handle* h, const LoopArgs& a, const double* u_ref, const double* y_ref) {
+  if (h->setpoint_convex_law) {            // DDMPC_OPT_SETPOINT_CONVEX_LAW: slack-only (Route::Cold) or bounded (Route::BoxLaw), as setpoint_step_on_route
+    const Route route = select_route(h);
+    begin_solve(h, route);
+    const bool yb = !h->ymin_h.empty(), safe = route == Route::BoxLaw && h->box_safeguard;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0,
+                         h->stream, h->kp, 16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p,
+                         (const double*)h->d_sgain.p, (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps, a.n_mpc_step, a.x, a.up,
+                         a.yp, a.w, u_ref, y_ref, a.usys, a.ysys, a.stacc, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,
+                         (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                         h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
+                         (int)(h->prm.use_terminal_constraint != 0));
+    };
+    if (yb && safe) launch(ddmpc_closed_loop_setpoint_convex_kernel<true, true>);
+    else if (yb) launch(ddmpc_closed_loop_setpoint_convex_kernel<false, true>);
+    else if (safe) launch(ddmpc_closed_loop_setpoint_convex_kernel<true, false>);
+    else launch(ddmpc_closed_loop_setpoint_convex_kernel<false, false>);
+    HIP_TRY(hipGetLastError());
+    h->last.setpoint_call = true;
+    return DDMPC_OK;
+  }
   if (select_route(h) == Route::BoxLaw) {
     begin_solve(h, Route::BoxLaw);
     const bool yb = !h->ymin_h.empty();
@@ -3452,8 +3536,8 @@ int ddmpc_closed_loop_setpoints(ddmpc_handle* h, const ddmpc_plant* plant, int32
                                 double* u_sys, double* y_sys, int32_t* status, int mem) {
   if (!h || !u_ref || !y_ref) return fail(DDMPC_ERR_INVALID, "null argument");
   if (!setpoint_on(h))
-    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1)");
-  if (h->bounded && !h->setpoint_box_law)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box)");
+  if (h->bounded && !h->setpoint_box_law && !h->setpoint_convex_law)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints on a handle with input or output bounds needs DDMPC_OPT_SETPOINT_BOX_LAW = 1");
   return closed_loop_impl(h, "ddmpc_closed_loop_setpoints", plant, n_steps, n_mpc_step, x, u_past, y_past, w, u_ref, y_ref, u_sys,
                           y_sys, status, mem);
@@ -3510,7 +3594,8 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
       u_ref = (const double*)h->d_uref.p; y_ref = (const double*)h->d_yref.p;
     }
     if (!prep_valid(h) && (rc = ddmpc_prepare(h))) return rc;
-    h->loop_kernel = select_route(h) == Route::BoxLaw ? "ddmpc_closed_loop_setpoint_box_kernel" : "ddmpc_closed_loop_setpoint_kernel";
+    h->loop_kernel = h->setpoint_convex_law ? "ddmpc_closed_loop_setpoint_convex_kernel"
+                     : select_route(h) == Route::BoxLaw ? "ddmpc_closed_loop_setpoint_box_kernel" : "ddmpc_closed_loop_setpoint_kernel";
     if ((rc = launch_setpoint_loop(h, a, u_ref, y_ref))) return rc;
     return copy_loop_outputs(h, mem, nb, a, user, status);
   }

@@ -314,10 +314,26 @@ class BatchedDDMPC:
         them."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_SETPOINT_BOX_LAW, 1 if on else 0))
 
+    def set_setpoint_convex_law(self, on: bool) -> None:
+        """`set_setpoint_law` / `set_setpoint_box_law` for ROBUST controllers with the CONVEX slack box, slack-only or with
+        input / output bounds set before or after it (DDMPC_OPT_SETPOINT_CONVEX_LAW): True = `prepare` forms S next to the law
+        and, on a slack-only handle, the slack box list and M whether or not `set_convex_warm_law` is on (L p r doubles per
+        instance: 65 KB at L = 30, m = p = 2).  `step_setpoints` / `closed_loop_setpoints` then run the active-set iteration
+        of `step` with the instance's own setpoint in the law, the offsets of the input / output components (a slack
+        component keeps offset 0) and the output stage; `set_box_safeguard` applies on bounded handles.  Per instance: a
+        non-finite setpoint is solver_error; with the terminal constraint a setpoint outside the bounds of its channel is
+        infeasible (NaN outputs, iters 0).  `solve`, `step`, `closed_loop`, `gain` and `get_solution` stay bit-equal to False
+        (default).  Changing the value forgets what `prepare` kept.  Raises ERR_UNSUPPORTED on NOMINAL controllers, slack
+        NONE (use `set_setpoint_law` / `set_setpoint_box_law`), dense weights, more than 271 rows, a trajectory beyond the
+        LDS, n(m+p) > 256 and a zero Q entry on a boxed output.  The iteration starts from the empty set, and `get_solution`
+        is not available after the calls."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_SETPOINT_CONVEX_LAW, 1 if on else 0))
+
     def step_setpoints(self, u_past, y_past, u_s, y_s, u_opt=None, cost=None, status=None, iters=None):
         """Warm control step with one setpoint per instance (`ddmpc_step_setpoints`): u_s [batch,m], y_s [batch,p], in the
         memory space of the windows; same outputs and array / tensor handling as `solve`.  The handle's own setpoints are not
-        read; `get_solution` is not available after it (until the next `solve` / `step`).  Needs `set_setpoint_law(True)`, or
+        read; `get_solution` is not available after it (until the next `solve` / `step`).  Needs `set_setpoint_law(True)`,
+        `set_setpoint_convex_law(True)` (CONVEX slack box), or
         `set_setpoint_box_law(True)`, which a handle with input / output bounds requires: there the step iterates on the box
         as `step` does (`iters` counts its solves; infeasible with NaN outputs for a setpoint outside the bounds under the
         terminal constraint)."""
@@ -331,7 +347,8 @@ class BatchedDDMPC:
 
     def closed_loop_setpoints(self, A, B, Cm, D, x0, u_past, y_past, w, u_ref, y_ref, n_mpc_step: int = 1):
         """`closed_loop` with a setpoint schedule per instance (`ddmpc_closed_loop_setpoints`, one fused launch): u_ref
-        [batch,n_steps,m], y_ref [batch,n_steps,p]; the solve made at step t tracks row t.  Needs `set_setpoint_law(True)`, or
+        [batch,n_steps,m], y_ref [batch,n_steps,p]; the solve made at step t tracks row t.  Needs `set_setpoint_law(True)`,
+        `set_setpoint_convex_law(True)` (CONVEX slack box: 'ddmpc_closed_loop_setpoint_convex_kernel'), or
         `set_setpoint_box_law(True)`, which a handle with input / output bounds requires ('ddmpc_closed_loop_setpoint_box_kernel':
         an instance stops at a solve that is not optimal and at a refused setpoint)."""
         return self.closed_loop(A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step, _ref=(u_ref, y_ref))
@@ -525,7 +542,8 @@ class BatchedDDMPC:
     def closed_loop_kernel_name(self) -> str:
         """The kernel that stepped the plant in the last `closed_loop`: one of the fused loops, or 'ddmpc_plant_kernel'
         when the loop ran per step; 'ddmpc_closed_loop_setpoint_kernel' after `closed_loop_setpoints`
-        ('ddmpc_closed_loop_setpoint_box_kernel' on a handle with bounds)."""
+        ('ddmpc_closed_loop_setpoint_box_kernel' on a handle with bounds, 'ddmpc_closed_loop_setpoint_convex_kernel' under
+        `set_setpoint_convex_law`)."""
         return self._lib.ddmpc_closed_loop_kernel_name(self._h).decode()
 
 

@@ -64,7 +64,8 @@ def parse_args():
                     help="instance b tracks its own equilibrium: u_s + S * uniform(-1, 1) (generator seeded with --seed) and the "
                          "output the plant settles at under it (robust scheme, slack None; closed_loop_setpoints).  Together with "
                          "--u_min/--u_max or --y_min/--y_max every instance tracks its setpoint inside the box "
-                         "(set_setpoint_box_law; --box_safeguard applies)")
+                         "(set_setpoint_box_law; --box_safeguard applies).  With slack Convex, bounded or not: "
+                         "set_setpoint_convex_law")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     return ap.parse_args()
 
@@ -128,7 +129,9 @@ def main():
     us_b = ys_b = None                           # --setpoint_spread: the setpoints of every instance, [B, m] and [B, p]
     bounded = a.u_min is not None or a.y_min is not None
     if a.setpoint_spread is not None:
-        if bounded:                              # setpoints per instance inside the box: DDMPC_OPT_SETPOINT_BOX_LAW
+        if cfg["slack"] == "convex":             # under the CONVEX slack box, bounded or not: DDMPC_OPT_SETPOINT_CONVEX_LAW
+            eng.set_setpoint_convex_law(True)
+        elif bounded:                            # setpoints per instance inside the box: DDMPC_OPT_SETPOINT_BOX_LAW
             eng.set_setpoint_box_law(True)
         else:
             eng.set_setpoint_law(True)
@@ -158,8 +161,11 @@ def main():
                           slack_type=L.SLACK_CONVEX if cfg["slack"] == "convex" else L.SLACK_NONE,
                           eps_max=cfg["eps_max"], lamb_alpha=cfg["lamb_alpha"], lamb_sigma=cfg["lamb_sigma"],
                           c=cfg["c"], use_terminal_constraint=cfg["tec"], device=a.device) as one:
-            if us_b is not None and bounded:
-                one.set_setpoint_box_law(True)
+            if us_b is not None and (bounded or cfg["slack"] == "convex"):
+                if cfg["slack"] == "convex":
+                    one.set_setpoint_convex_law(True)
+                else:
+                    one.set_setpoint_box_law(True)
                 if a.u_min is not None:
                     one.set_input_bounds(a.u_min if len(a.u_min) > 1 else a.u_min[0], a.u_max if len(a.u_max) > 1 else a.u_max[0])
                 if a.y_min is not None:

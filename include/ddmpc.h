@@ -305,7 +305,8 @@ extern "C" {
                                          controllers, with the CONVEX slack box, with DDMPC_WEIGHT_DENSE, beyond 271 rows, on a
                                          trajectory beyond the LDS, with n(m+p) > 256 and on a handle with input or output bounds;
                                          in the reverse order ddmpc_set_input_bounds / ddmpc_set_output_bounds refuse finite bounds
-                                         on a handle with the option on (unless DDMPC_OPT_SETPOINT_BOX_LAW = 1, below) */
+                                         on a handle with the option on (unless DDMPC_OPT_SETPOINT_BOX_LAW = 1, below).  CONVEX
+                                         handles: DDMPC_OPT_SETPOINT_CONVEX_LAW */
 #define DDMPC_OPT_SETPOINT_BOX_LAW 19    /* DDMPC_OPT_SETPOINT_LAW for handles that carry input / output bounds (up to 271 rows): 1 =
                                          ddmpc_prepare forms S next to the law and M = K0^-1 E_box (S comes from the empty set's
                                          system and knows no bounds; its columns are refined under DDMPC_REFINE_AUTO as those of the
@@ -330,12 +331,45 @@ extern "C" {
                                          ddmpc_prepare kept.  Setting 1 is DDMPC_ERR_UNSUPPORTED, with a message that names the
                                          reason, on NOMINAL controllers, with the CONVEX slack box, with DDMPC_WEIGHT_DENSE, beyond
                                          271 rows (the phase kernels have no M), on a trajectory beyond the LDS and with
-                                         n(m+p) > 256.  LIMITS: the CONVEX slack box stays refused, slack-only or with bounds (a
-                                         slack-only CONVEX handle runs on other kernels; putting it on the box route is a follow-up);
-                                         the bounds are the handle's, not per instance; the iteration of the new calls always starts
+                                         n(m+p) > 256.  CONVEX handles, slack-only or with bounds: DDMPC_OPT_SETPOINT_CONVEX_LAW,
+                                         below.  LIMITS: the bounds are the handle's, not per instance; the iteration of the new calls always starts
                                          from the empty set (DDMPC_OPT_BOX_WARM_START is not honoured, and the calls drop the seed);
                                          ddmpc_get_solution after them is DDMPC_ERR_NOT_READY; DDMPC_REFINE_ALWAYS stays refused on
                                          bounded handles */
+#define DDMPC_OPT_SETPOINT_CONVEX_LAW 20 /* DDMPC_OPT_SETPOINT_LAW / _SETPOINT_BOX_LAW for ROBUST controllers with the CONVEX slack box
+                                         (scalar / diagonal weights, up to 271 rows), slack-only or with input and / or output
+                                         bounds; the option and the bounds are accepted in either order.  1 = ddmpc_prepare forms S
+                                         next to the law (from the empty set's system, which knows neither the slack box nor the
+                                         bounds; refined as the law's columns are) and ddmpc_step_setpoints /
+                                         ddmpc_closed_loop_setpoints / ddmpc_get_setpoint_gain are open.  On a slack-only handle
+                                         ddmpc_prepare also forms the box list of the slack components, its table and
+                                         M = K0^-1 E_box, whether or not DDMPC_OPT_CONVEX_WARM_LAW is on: L p r doubles per instance
+                                         (65 KB at L = 30, n = 4, m = p = 2: 0.27 GB at 4096 instances; an allocation failure is
+                                         DDMPC_ERR_HIP); a bounded handle has them already.  ddmpc_step_setpoints is one launch of
+                                         "ddmpc_setpoint_convex_step_kernel", ddmpc_closed_loop_setpoints one fused launch of
+                                         "ddmpc_closed_loop_setpoint_convex_kernel" (n_mpc_step * m > 256: DDMPC_ERR_UNSUPPORTED):
+                                         the primal-dual iteration of ddmpc_step on the law, S and M -- same rule, max_iter cap,
+                                         statuses and count of `iters`; DDMPC_OPT_BOX_SAFEGUARD is honoured on bounded handles.  Per
+                                         instance the setpoint enters the law, the offsets of the input and output components (a
+                                         slack component keeps a = 0, c = -lam / lamb_sigma, lo / hi = -+ c eps_max) and the target of
+                                         the output stage.  The iteration always starts from the empty set (no active-set warm
+                                         start; the calls drop the seed).  An instance whose law came from refining solves
+                                         (DDMPC_REFINE_AUTO) reports DDMPC_STATUS_OPTIMAL_INACCURATE when its final set is not
+                                         empty: no cold re-solve is possible, the cold kernels read the shared setpoint table.  A
+                                         non-finite setpoint is DDMPC_STATUS_SOLVER_ERROR for that instance; with the terminal
+                                         constraint a setpoint outside [u_min, u_max] / [y_min, y_max] of its channel is
+                                         DDMPC_STATUS_INFEASIBLE with u_opt and cost NaN and iters 0 (in the loop the instance stops
+                                         there); neighbours are untouched.  ddmpc_get_solution after the calls is
+                                         DDMPC_ERR_NOT_READY.  ddmpc_solve, ddmpc_step, ddmpc_closed_loop, ddmpc_get_gain and
+                                         ddmpc_get_solution launch what they launch with 0 and return bit-equal results, with
+                                         DDMPC_OPT_CONVEX_WARM_LAW on and off, with and without bounds.  0 (default; accepted on
+                                         every handle).  Values other than 0 / 1: DDMPC_ERR_INVALID.  Changing the value forgets what
+                                         ddmpc_prepare kept.  Setting 1 is DDMPC_ERR_UNSUPPORTED, with a message that names the
+                                         reason, on NOMINAL controllers, with slack NONE (options 18 / 19 serve it: the three are
+                                         never on together), with DDMPC_WEIGHT_DENSE, beyond 271 rows, on a trajectory beyond the
+                                         LDS, with n(m+p) > 256 and where a boxed output component has a Q entry of 0 (the rule of
+                                         DDMPC_OPT_CONVEX_WARM_LAW).  LIMITS: the bounds are the handle's, not per instance;
+                                         DDMPC_REFINE_ALWAYS stays refused on bounded handles */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -612,7 +646,8 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
                       double* u_sys, double* y_sys, int32_t* status, int mem);
 
 /* Per-instance, per-step setpoints (DDMPC_OPT_SETPOINT_LAW = 1, or DDMPC_OPT_SETPOINT_BOX_LAW = 1 -- see there for what the
- * calls do on a handle with input / output bounds; DDMPC_ERR_UNSUPPORTED on all three calls without either).  The
+ * calls do on a handle with input / output bounds --, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 -- see there for what they do under
+ * the CONVEX slack box; DDMPC_ERR_UNSUPPORTED on all three calls without any of them).  The
  * reduced system K0 beta = t is linear in t and t is linear in the setpoints, so with m + p more columns the law of
  * ddmpc_prepare takes the setpoint as an argument:
  *     beta_b = sum_f past_b[f] gain[b][1+f][:] + sum_c s_b[c] S[b][c][:],      s_b = [u_s_b ; y_s_b],
@@ -632,8 +667,8 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
  * ddmpc_get_setpoint_gain: out [batch, m+p, r] doubles = S.  DDMPC_ERR_NOT_READY before a ddmpc_prepare with the option on.
  * ddmpc_get_solution after either of the first two calls is DDMPC_ERR_NOT_READY (the reconstruction reads the shared
  *   setpoint table); a later ddmpc_solve or ddmpc_step makes the solution readable again.
- * LIMITS: ROBUST controllers only; slack NONE (no CONVEX slack box) and no input / output bounds (with bounds:
- *   DDMPC_OPT_SETPOINT_BOX_LAW); scalar / diagonal weights;
+ * LIMITS: ROBUST controllers only; slack NONE and no input / output bounds (with bounds: DDMPC_OPT_SETPOINT_BOX_LAW; with
+ *   the CONVEX slack box, bounded or not: DDMPC_OPT_SETPOINT_CONVEX_LAW); scalar / diagonal weights;
  *   at most 271 rows and a trajectory that fits the LDS; n(m+p) <= 256.  The cold kernels know the handle's shared setpoints
  *   only (ddmpc_solve).  Under DDMPC_REFINE_AUTO the instances whose law and S are refined are chosen from solves at the
  *   handle's own setpoints, not at the ones passed later. */
@@ -655,8 +690,8 @@ const char* ddmpc_kernel_name(ddmpc_handle* h);
 /* Name of the kernel that stepped the plant in the last ddmpc_closed_loop: "ddmpc_closed_loop_warm_kernel" or
  * "ddmpc_closed_loop_convex_warm_kernel" / "ddmpc_closed_loop_box_kernel" (input bounds) when the whole loop ran fused in one launch, "ddmpc_plant_kernel" when it ran
  * per step (DDMPC_PATH_COLD, shapes beyond the fused loops' bounds, NOMINAL instances without a law, laws taken from
- * refining solves under DDMPC_OPT_CONVEX_WARM_LAW, handles beyond 271 rows); "ddmpc_closed_loop_setpoint_kernel" after
- * ddmpc_closed_loop_setpoints; "" before the first loop.  Read-only. */
+ * refining solves under DDMPC_OPT_CONVEX_WARM_LAW, handles beyond 271 rows); "ddmpc_closed_loop_setpoint_kernel" /
+ * "ddmpc_closed_loop_setpoint_box_kernel" / "ddmpc_closed_loop_setpoint_convex_kernel" after ddmpc_closed_loop_setpoints; "" before the first loop.  Read-only. */
 const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h);
 
 /* Diagnostics only: in-kernel phase stamps (shader-clock ticks) of the next solves.
