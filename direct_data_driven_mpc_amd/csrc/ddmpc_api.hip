@@ -215,6 +215,7 @@ struct Prep {
   Route route = Route::Cold;
   bool law = false;                        // beyond 271 rows: the affine law was formed (DDMPC_OPT_LARGE_AFFINE_LAW, DDMPC_OPT_LARGE_BOX_LAW)
   int r3_nolaw = 0;                        // ... ROBUST: instances whose law missed the refinement threshold (their steps take the filtered re-solve)
+  int r3_nosp = 0;                         // ... DDMPC_OPT_LARGE_SETPOINTS: instances whose S missed it (their setpoint steps take the filtered re-solve)
   int cwl_nbox = 0;                        // DDMPC_OPT_CONVEX_WARM_LAW, Route::BoxLaw: boxed components
   int box_threads = 0;                     // Route::BoxLaw: block of the box kernels (max(r, nbox) rounded up to 64)
   int cwl_nref = 0;                        // ... instances whose law came from refining solves (their steps keep the filtered cold launch;
@@ -303,6 +304,8 @@ struct ddmpc_handle {
                                            //   never on together with the two above (they refuse CONVEX, this one slack NONE)
   DevBuf d_sp, d_uref, d_yref;             // ... staging of host setpoints [u_s | y_s] (ddmpc_step_setpoints) and schedules (ddmpc_closed_loop_setpoints)
   const double *sp_us = nullptr, *sp_ys = nullptr;   // ... the device setpoints of the ddmpc_step_setpoints call in progress
+  long long sp_su = 0, sp_sy = 0;          // ... DDMPC_OPT_LARGE_SETPOINTS: their per-instance strides (m, p; a schedule row: n_steps m, n_steps p)
+  int large_setpoints = 0;                 // DDMPC_OPT_LARGE_SETPOINTS: the setpoint calls on Route::RobustPhases (a setpoint per instance on the kept factors)
   // input bounds (ddmpc_set_input_bounds) and output bounds (ddmpc_set_output_bounds): per channel, +-infinity = none; the
   // vectors are empty without a finite bound of their kind; `bounded` = some bound of either kind is finite (Route::BoxLaw)
   std::vector<double> umin_h, umax_h, ymin_h, ymax_h;
@@ -343,8 +346,11 @@ static bool prep_valid(const ddmpc_handle* h) { return h->prep.valid && h->prep.
 // of them comes through here: ddmpc_set_data, ddmpc_set_setpoints, both bounds calls, a new ddmpc_prepare).
 static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; h->last.large_seed = false; }
 
-// ddmpc_prepare forms S and the three setpoint calls are open: DDMPC_OPT_SETPOINT_LAW, _SETPOINT_BOX_LAW or _SETPOINT_CONVEX_LAW is on.
-static bool setpoint_on(const ddmpc_handle* h) { return h->setpoint_law != 0 || h->setpoint_box_law != 0 || h->setpoint_convex_law != 0; }
+// ddmpc_prepare forms S and the three setpoint calls are open: DDMPC_OPT_SETPOINT_LAW, _SETPOINT_BOX_LAW or _SETPOINT_CONVEX_LAW is on
+// -- or, beyond 271 rows, DDMPC_OPT_LARGE_SETPOINTS (the calls run on the kept factors; S next to the law of DDMPC_OPT_LARGE_AFFINE_LAW).
+static bool setpoint_on(const ddmpc_handle* h) {
+  return h->setpoint_law != 0 || h->setpoint_box_law != 0 || h->setpoint_convex_law != 0 || h->large_setpoints != 0;
+}
 // DDMPC_OPT_SETPOINT_CONVEX_LAW on a slack-only CONVEX handle (Route::Cold): ddmpc_prepare forms the slack box list with its
 // [a | c | lo | hi | 1/d] table and M for the setpoint calls, whether or not DDMPC_OPT_CONVEX_WARM_LAW is on.
 static bool setpoint_convex_slack_only(const ddmpc_handle* h) { return h->setpoint_convex_law != 0 && h->kp.convex && !h->large && !h->bounded; }
@@ -1250,7 +1256,8 @@ static int launch_rr3_fallback(ddmpc_handle* h, const KParams& kq, const double*
 // = 1 on a bounded handle only): the iteration starts from the set in d_large_seed; with the option 1 every call leaves its set
 // there.
 static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up, const double* yp, double* uo, double* cost,
-                            int32_t* status, int32_t* iters, const int* only = nullptr, int* only_si = nullptr, bool seeded = false) {
+                            int32_t* status, int32_t* iters, const int* only = nullptr, int* only_si = nullptr, bool seeded = false,
+                            const Rr3Setpoint* sp = nullptr) {
   const int r = kq.r;
   const unsigned B = (unsigned)h->batch;
   const Rr3Plan P = rr3_plan(h, kq, only != nullptr, seeded);
@@ -1277,6 +1284,7 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
   else if (wide)                     rc = launch(rr3_solve_box_wide_kernel<false>, defer, X, P.cap);
   else if (box && F)                 rc = launch(rr3_solve_box_kernel<false, Rr3Only>, defer, X, flt);
   else if (box)                      rc = launch(rr3_solve_box_kernel<false>, defer, X);
+  else if (sp)                       rc = launch(rr3_solve_kernel<false, Rr3Setpoint>, defer, only, *sp);   // (Plain only: the option refuses bounds)
   else                               rc = launch(rr3_solve_kernel<false>, defer, only);
   if (rc) return rc;
   // the instances that reached max_iter are solved again by the primal method, before the Hankel products and the refinement
@@ -1296,6 +1304,7 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     else if (wide)      rc = launch(rr3_solve_box_wide_kernel<true>, 0, X, P.cap);
     else if (box && F)  rc = launch(rr3_solve_box_kernel<true, Rr3Only>, 0, X, flt);
     else if (box)       rc = launch(rr3_solve_box_kernel<true>, 0, X);
+    else if (sp)        rc = launch(rr3_solve_kernel<true, Rr3Setpoint>, 0, only, *sp);
     else                rc = launch(rr3_solve_kernel<true>, 0, only);
     if (rc) return rc;
   }
@@ -1306,18 +1315,21 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     h->last.large_seed = true;
   }
   HIP_TRY(hipGetLastError());
-  return P.family == Rr3Family::Plain ? launch_rr3_fallback(h, kq, up, yp, uo, cost, status, iters) : DDMPC_OK;
+  // (with setpoints: no fall-back, it solves from the shared table -- the kernel reported the instances it marked 5 as 4)
+  return P.family == Rr3Family::Plain && !sp ? launch_rr3_fallback(h, kq, up, yp, uo, cost, status, iters) : DDMPC_OK;
 }
 
-// The per-instance flags of the law on Route::RobustPhases, d_r3flag (5 B ints): [no law | need | refine | si (2 B)].
+// The per-instance flags of the law on Route::RobustPhases, d_r3flag (7 B ints): [no law | need | refine | si (2 B) | no setpoint
+// law | refine S].
 struct Rr3Flags {
   int *nolaw, *need, *rfl;     // the law missed the threshold; the step left the instance to the solve; the law build's refinement passes
   int* si;                     // [2 B]: need in the layout of Rr2Solve::si
+  int *nosp, *rfs;             // DDMPC_OPT_LARGE_SETPOINTS: S missed the threshold (apart from nolaw: ddmpc_step does not read it); S's refinement passes
 };
 static Rr3Flags rr3_flags(const ddmpc_handle* h) {
   int* f = (int*)h->d_r3flag.p;
   const size_t B = (size_t)h->batch;
-  return Rr3Flags{f, f + B, f + 2 * B, f + 3 * B};
+  return Rr3Flags{f, f + B, f + 2 * B, f + 3 * B, f + 5 * B, f + 6 * B};
 }
 
 // DDMPC_OPT_LARGE_AFFINE_LAW on Route::RobustPhases (ddmpc_rr3_law.hpp): the law beta(w) = g0 + G' w of every instance on the
@@ -1331,59 +1343,74 @@ static int launch_rr3_law_build(ddmpc_handle* h) {
   const size_t B = (size_t)h->batch;
   const size_t Bc = std::min<size_t>(B, std::min<size_t>(32, (size_t)(65535 / nrhs)));
   const bool refine = k.refine != DDMPC_REFINE_OFF && k.lam != 0.0;
+  const bool with_s = h->large_setpoints != 0 && h->large_affine != 0;    // DDMPC_OPT_LARGE_SETPOINTS: S next to the law
   Rr3 S;
   int rc;
   if ((rc = rr3_desc(h, k, &S))) return rc;
-  if ((rc = h->d_gz.ensure((B * nrhs * (size_t)r + VL) * sizeof(double))) || (rc = h->d_r3flag.ensure(5 * B * sizeof(int))) ||
+  if ((rc = h->d_gz.ensure((B * nrhs * (size_t)r + VL) * sizeof(double))) || (rc = h->d_r3flag.ensure(7 * B * sizeof(int))) ||
       (rc = h->d_r3y.ensure(Bc * ncb * (size_t)VL * 64 * sizeof(double))))
     return rc;
+  if (with_s && (rc = h->d_sgain.ensure((B * k.nch * (size_t)r + VL) * sizeof(double)))) return rc;
   if (refine && ((rc = h->d_r3res.ensure(Bc * nrhs * (size_t)r * sizeof(double))) ||
                  (rc = h->d_r3zp.ensure(Bc * nrhs * (size_t)RR2_NG * VL * sizeof(double)))))
     return rc;
   HankelLaunch hk;
   if (refine && (rc = pick_hankel_launch(k, &hk))) return rc;
   const int RPs = 16 * h->kc.NT;
-  double* law = (double*)h->d_gz.p;
   double* Y = (double*)h->d_r3y.p;
-  int *nolaw = rr3_flags(h).nolaw, *rfl = rr3_flags(h).rfl;
-  HIP_TRY(hipMemsetAsync(nolaw, 0, B * sizeof(int), h->stream));
   std::vector<int> fl(Bc);
-  for (size_t b0 = 0; b0 < B; b0 += Bc) {
-    const size_t nb = std::min(Bc, B - b0);
-    const dim3 grid((unsigned)ncb, (unsigned)nb);
-    hipLaunchKernelGGL(rr3_law_fwd_kernel<false>, grid, dim3(RR2_TS), 0, h->stream, S, k, RPs, (long long)b0, nf, (const double*)nullptr,
-                       (const int*)nullptr, Y, nolaw);
-    hipLaunchKernelGGL(rr3_law_bwd_kernel<false>, grid, dim3(RR2_TS), 0, h->stream, S, (long long)b0, nf, (const int*)nullptr, Y, law, nolaw);
-    HIP_TRY(hipGetLastError());
-    if (!refine) continue;
-    Rr2Solve H{};
-    H.V = law + b0 * nrhs * (size_t)r; H.vstride = r; H.VL = VL; H.ZP = (double*)h->d_r3zp.p; H.fdiv = nrhs; H.r = r;
-    for (int pass = 0;; ++pass) {
-      const bool last = pass == k.refine_max, force = pass == 0 && k.refine == DDMPC_REFINE_ALWAYS;
-      HIP_TRY(hipMemsetAsync(rfl + b0, 0, nb * sizeof(int), h->stream));
-      launch_hankel(hk, h->stream, (unsigned)(nb * nrhs), H, k, h->ud + b0 * (size_t)k.N * k.m, h->yd + b0 * (size_t)k.N * k.p, 0, 0);
-      hipLaunchKernelGGL(rr3_law_resid_kernel, dim3((unsigned)nrhs, (unsigned)nb), dim3(256), 0, h->stream, k, RPs, (long long)b0, nf,
-                         (const double*)law, (const double*)h->d_r3zp.p, VL, (double*)h->d_r3res.p, rfl, force ? 1 : 0,
-                         last ? nolaw : nullptr);
+  // One set of right-hand sides through the three kernels, chunk by chunk: the law (RR3_RHS_LAW: nf + 1 columns into d_gz, flags
+  // nolaw / rfl), then -- apart from it, with flags of its own, so that the law's launches and the refinement decisions taken
+  // on it are those of a handle without the option -- S (RR3_RHS_SETPOINT: m + p columns into d_sgain, flags nosp / rfs).  The
+  // scratch (Y, residuals, Hankel sums) is sized by the law, which has the more columns.  *missed: instances above the threshold.
+  auto build = [&](int kind, int ncol, double* dst, int* nol, int* rfl, int* missed) -> int {
+    const int nfk = kind == RR3_RHS_SETPOINT ? ncol : ncol - 1;            // (the kernels' count: columns of S, or windows of the law)
+    const int ncbk = (ncol + 63) / 64;
+    HIP_TRY(hipMemsetAsync(nol, 0, B * sizeof(int), h->stream));
+    for (size_t b0 = 0; b0 < B; b0 += Bc) {
+      const size_t nb = std::min(Bc, B - b0);
+      const dim3 grid((unsigned)ncbk, (unsigned)nb);
+      hipLaunchKernelGGL(rr3_law_fwd_kernel<false>, grid, dim3(RR2_TS), 0, h->stream, S, k, RPs, (long long)b0, nfk, (const double*)nullptr,
+                         (const int*)nullptr, Y, nol, kind);
+      hipLaunchKernelGGL(rr3_law_bwd_kernel<false>, grid, dim3(RR2_TS), 0, h->stream, S, (long long)b0, nfk, (const int*)nullptr, Y, dst, nol, kind);
       HIP_TRY(hipGetLastError());
-      if (last) break;
-      HIP_TRY(hipMemcpyAsync(fl.data(), rfl + b0, nb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      bool any = false;
-      for (size_t i = 0; i < nb; ++i) any = any || fl[i] != 0;
-      if (!any) break;                                      // every law of the chunk is within the threshold
-      hipLaunchKernelGGL(rr3_law_fwd_kernel<true>, grid, dim3(RR2_TS), 0, h->stream, S, k, RPs, (long long)b0, nf,
-                         (const double*)h->d_r3res.p, (const int*)rfl, Y, nolaw);
-      hipLaunchKernelGGL(rr3_law_bwd_kernel<true>, grid, dim3(RR2_TS), 0, h->stream, S, (long long)b0, nf, (const int*)rfl, Y, law, nolaw);
-      HIP_TRY(hipGetLastError());
+      if (!refine) continue;
+      Rr2Solve H{};
+      H.V = dst + b0 * ncol * (size_t)r; H.vstride = r; H.VL = VL; H.ZP = (double*)h->d_r3zp.p; H.fdiv = ncol; H.r = r;
+      for (int pass = 0;; ++pass) {
+        const bool last = pass == k.refine_max, force = pass == 0 && k.refine == DDMPC_REFINE_ALWAYS;
+        HIP_TRY(hipMemsetAsync(rfl + b0, 0, nb * sizeof(int), h->stream));
+        launch_hankel(hk, h->stream, (unsigned)(nb * ncol), H, k, h->ud + b0 * (size_t)k.N * k.m, h->yd + b0 * (size_t)k.N * k.p, 0, 0);
+        hipLaunchKernelGGL(rr3_law_resid_kernel, dim3((unsigned)ncol, (unsigned)nb), dim3(256), 0, h->stream, k, RPs, (long long)b0, nfk,
+                           (const double*)dst, (const double*)h->d_r3zp.p, VL, (double*)h->d_r3res.p, rfl, force ? 1 : 0,
+                           last ? nol : nullptr, kind);
+        HIP_TRY(hipGetLastError());
+        if (last) break;
+        HIP_TRY(hipMemcpyAsync(fl.data(), rfl + b0, nb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        bool any = false;
+        for (size_t i = 0; i < nb; ++i) any = any || fl[i] != 0;
+        if (!any) break;                                      // every column set of the chunk is within the threshold
+        hipLaunchKernelGGL(rr3_law_fwd_kernel<true>, grid, dim3(RR2_TS), 0, h->stream, S, k, RPs, (long long)b0, nfk,
+                           (const double*)h->d_r3res.p, (const int*)rfl, Y, nol, kind);
+        hipLaunchKernelGGL(rr3_law_bwd_kernel<true>, grid, dim3(RR2_TS), 0, h->stream, S, (long long)b0, nfk, (const int*)rfl, Y, dst, nol, kind);
+        HIP_TRY(hipGetLastError());
+      }
     }
-  }
-  std::vector<int> nl(B);
-  HIP_TRY(hipMemcpyAsync(nl.data(), nolaw, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->prep.r3_nolaw = 0;
-  for (size_t i = 0; i < B; ++i) h->prep.r3_nolaw += nl[i] != 0;
+    std::vector<int> nl(B);
+    HIP_TRY(hipMemcpyAsync(nl.data(), nol, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *missed = 0;
+    for (size_t i = 0; i < B; ++i) *missed += nl[i] != 0;
+    return DDMPC_OK;
+  };
+  const Rr3Flags F = rr3_flags(h);
+  if ((rc = build(RR3_RHS_LAW, nrhs, (double*)h->d_gz.p, F.nolaw, F.rfl, &h->prep.r3_nolaw))) return rc;
   h->prep.law = true;
+  if (with_s) {
+    if ((rc = build(RR3_RHS_SETPOINT, k.nch, (double*)h->d_sgain.p, F.nosp, F.rfs, &h->prep.r3_nosp))) return rc;
+    h->prep.setpoint = true;
+  }
   return DDMPC_OK;
 }
 
@@ -1416,6 +1443,23 @@ static int launch_rr3_law_step(ddmpc_handle* h, const double* up, const double* 
   if (int rc = launch_rr3_law_kernel(h, false, up, yp, uo, cost, status, iters)) return rc;
   if (!h->kp.convex && h->prep.r3_nolaw == 0) return DDMPC_OK;
   return launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters, rr3_flags(h).need, rr3_flags(h).si);
+}
+
+// DDMPC_OPT_LARGE_SETPOINTS with the law and S present: one launch of rr3_setpoint_law_step_kernel over the batch, then -- under the
+// slack box, or when some instance has no law or no setpoint law -- the solve on the kept factor with the same setpoints,
+// restricted to the instances the step left to it (queued without a read-back).
+static int launch_rr3_setpoint_law_step(ddmpc_handle* h, const Rr3Setpoint& sp, const double* up, const double* yp, double* uo,
+                                        double* cost, int32_t* status, int32_t* iters) {
+  const KParams& k = h->kp;
+  const Rr3Flags F = rr3_flags(h);
+  Rr3 S;
+  if (int rc = rr3_desc(h, k, &S)) return rc;
+  hipLaunchKernelGGL(rr3_setpoint_law_step_kernel, dim3((unsigned)h->batch), dim3(RR2_TS), 0, h->stream, S, k, 16 * h->kc.NT,
+                     h->prm.n * k.nch, (const double*)h->d_gz.p, (const int*)F.nolaw, up, yp, uo, cost, (int*)status, (int*)iters,
+                     (double*)h->d_beta.p, (signed char*)h->d_act.p, F.need, F.si, (const double*)h->d_sgain.p, (const int*)F.nosp, sp);
+  HIP_TRY(hipGetLastError());
+  if (!k.convex && h->prep.r3_nolaw == 0 && h->prep.r3_nosp == 0) return DDMPC_OK;
+  return launch_rr3_solve(h, k, up, yp, uo, cost, status, iters, F.need, F.si, false, &sp);
 }
 
 // DDMPC_OPT_LARGE_BOX_LAW (ddmpc_rr3_box_law.hpp): a control step of a bounded handle on that law -- one launch over the batch that
@@ -2617,8 +2661,15 @@ int ddmpc_get_gain(ddmpc_handle* h, double* out, int mem) {
 // DDMPC_OPT_SETPOINT_LAW: one evaluation of the law and S with the setpoints of the call in progress (h->sp_us / h->sp_ys).
 // DDMPC_OPT_SETPOINT_BOX_LAW on a handle with finite bounds (Route::BoxLaw): one launch of ddmpc_setpoint_box_step_kernel, from the
 // empty set (DDMPC_OPT_BOX_WARM_START is not honoured, and the caller drops the seed with the record of the last solve).
+// DDMPC_OPT_LARGE_SETPOINTS (Route::RobustPhases): the solve on the kept factors with the instance's setpoint.
 static int setpoint_step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                                   int32_t* iters) {
+  if (h->large_setpoints) {
+    begin_solve(h, Route::RobustPhases);
+    const Rr3Setpoint sp{h->sp_us, h->sp_ys, h->sp_su, h->sp_sy};
+    if (h->large_affine && h->prep.law && h->prep.setpoint) return launch_rr3_setpoint_law_step(h, sp, up, yp, uo, cost, status, iters);
+    return launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters, nullptr, nullptr, false, &sp);
+  }
   if (h->setpoint_convex_law) {
     // DDMPC_OPT_SETPOINT_CONVEX_LAW: ddmpc_setpoint_convex_step_kernel on the box list ddmpc_prepare kept -- the slack components
     // alone (Route::Cold; no safeguard: the slack box does not cycle) or next to the bounded inputs / outputs (Route::BoxLaw)
@@ -2672,7 +2723,7 @@ int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_
                          double* u_opt, double* cost, int32_t* status, int32_t* iters, int mem) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
   if (!setpoint_on(h))
-    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box)");
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box), or beyond 271 rows DDMPC_OPT_LARGE_SETPOINTS = 1");
   if (h->bounded && !h->setpoint_box_law && !h->setpoint_convex_law)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints on a handle with input or output bounds needs DDMPC_OPT_SETPOINT_BOX_LAW = 1");
   if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_step_setpoints");
@@ -2681,7 +2732,7 @@ int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_
   if (!prep_valid(h))
     if (int rc = ddmpc_prepare(h)) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  h->sp_us = u_s; h->sp_ys = y_s;
+  h->sp_us = u_s; h->sp_ys = y_s; h->sp_su = h->prm.m; h->sp_sy = h->prm.p;
   if (mem == DDMPC_MEM_HOST) {
     const size_t B = (size_t)h->batch, nu = B * h->prm.m, ny = B * h->prm.p;
     if (int rc = h->d_sp.ensure((nu + ny) * sizeof(double))) return rc;
@@ -2700,7 +2751,10 @@ int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_
 int ddmpc_get_setpoint_gain(ddmpc_handle* h, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
   if (!setpoint_on(h))
-    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_get_setpoint_gain needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box)");
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_get_setpoint_gain needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box), or beyond 271 rows DDMPC_OPT_LARGE_SETPOINTS = 1");
+  if (h->large_setpoints && (!prep_valid(h) || !h->prep.setpoint))
+    return fail(DDMPC_ERR_NOT_READY, "ddmpc_get_setpoint_gain beyond 271 rows: S is formed next to the affine law only -- ddmpc_prepare with "
+                "DDMPC_OPT_LARGE_AFFINE_LAW = 1 (and DDMPC_OPT_LARGE_SETPOINTS = 1) must be called before it");
   if (!prep_valid(h) || !h->prep.setpoint)
     return fail(DDMPC_ERR_NOT_READY, "ddmpc_prepare with DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1) must be called before "
                 "ddmpc_get_setpoint_gain");
@@ -2904,6 +2958,34 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (h->setpoint_convex_law != value) forget_prep(h);   // (S, and on a slack-only handle the box list and M, are part of what ddmpc_prepare keeps)
       h->setpoint_convex_law = value;
       return DDMPC_OK;
+    case DDMPC_OPT_LARGE_SETPOINTS:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_SETPOINTS must be 0 or 1");
+      if (value == 1) {
+        const char* pre = "DDMPC_OPT_LARGE_SETPOINTS";
+        if (h->prm.controller_type != DDMPC_ROBUST)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: ROBUST controllers only (a NOMINAL one fixes its outputs to the setpoint as hard rows)", pre);
+        if (h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)", pre);
+        if (!h->large)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the option serves 272 .. 1024 rows (up to 271 rows: DDMPC_OPT_SETPOINT_LAW, "
+                      "DDMPC_OPT_SETPOINT_BOX_LAW, DDMPC_OPT_SETPOINT_CONVEX_LAW)", pre, h->kp.r);
+        if (h->kp.r > 1024)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 1024 (the phase kernels)", pre, h->kp.r);
+        if (h->large_pipeline != DDMPC_PIPELINE_PHASES)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: the phase kernels serve it only, and DDMPC_OPT_LARGE_PIPELINE selects the one-workgroup kernel", pre);
+        if (h->stamps_on)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: the phase kernels serve it only, and ddmpc_debug_stamps selects the one-workgroup kernel", pre);
+        if (h->batch > 65535)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: the phase kernels serve it only: batch %lld, the limit is 65535", pre, (long long)h->batch);
+        if (h->prm.n * h->kp.nch > WARM_MAX_NF)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: n*(m+p) = %d, the limit is %d", pre, h->prm.n * h->kp.nch, WARM_MAX_NF);
+        if (h->bounded)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s is not available on a handle with input or output bounds (beyond 271 rows the setpoint step "
+                      "knows no bounds)", pre);
+      }
+      if (h->large_setpoints != value) forget_prep(h);   // (S is part of what ddmpc_prepare keeps, as DDMPC_OPT_SETPOINT_LAW)
+      h->large_setpoints = value;
+      return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
       if (value == 1 && !h->gram_valu_ok) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_gram_tiles_kernel stages the whole trajectory in LDS: not at this shape");
@@ -2917,6 +2999,9 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
         return fail(DDMPC_ERR_INVALID, "pipeline must be DDMPC_PIPELINE_ONE_WORKGROUP or DDMPC_PIPELINE_PHASES");
       if (value == DDMPC_PIPELINE_ONE_WORKGROUP && h->large_nominal && h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
         return fail(DDMPC_ERR_UNSUPPORTED, "dense weighting matrices of a NOMINAL controller beyond 271 rows run on the phase kernels only");
+      if (value == DDMPC_PIPELINE_ONE_WORKGROUP && h->large_setpoints)
+        return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_PIPELINE_ONE_WORKGROUP is not available with DDMPC_OPT_LARGE_SETPOINTS = 1: the phase kernels "
+                    "serve the setpoint calls only");
       if (value == DDMPC_PIPELINE_ONE_WORKGROUP && h->large && h->bounded)
         return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_PIPELINE_ONE_WORKGROUP is not available on a handle with input or output bounds: beyond 271 rows "
                     "the phase kernels serve them only");
@@ -2929,6 +3014,8 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
 // Bounds beyond 271 rows are served by the bounded instantiations of the phase kernels (ddmpc_rr3.hpp) only: why this handle
 // cannot have them, or null.  `what`: "input bounds" / "output bounds".
 static int large_bounds_refusal(const ddmpc_handle* h, const char* what) {
+  if (h->large_setpoints)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: not with DDMPC_OPT_LARGE_SETPOINTS = 1 (beyond 271 rows the setpoint step knows no bounds)", what);
   if (!h->large_bounds)     // (opt-in: without the option a handle beyond 271 rows refuses bounds as it always did)
     return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels) unless "
                 "DDMPC_OPT_LARGE_BOUNDS = 1 (the phase kernels, 272 .. 1024 rows)", what, h->kp.r);
@@ -3277,6 +3364,7 @@ struct LoopArgs {
   int* stacc;                                              // status accumulator
   double* beta = nullptr; signed char* act = nullptr;      // beta / active set of the last solve (launch_fused_loop)
   double *lwup = nullptr, *lwyp = nullptr;                 // the past window of the last solve
+  const double *uref = nullptr, *yref = nullptr;           // DDMPC_OPT_LARGE_SETPOINTS: the schedules [batch][n_steps][m], [batch][n_steps][p] (run_step_loop)
 };
 struct LoopBytes { size_t x, up, yp, w, us; };             // state, windows, w (= y_sys) and u_sys of the whole batch
 
@@ -3401,8 +3489,14 @@ static int run_step_loop(ddmpc_handle* h, LoopPath path, const LoopArgs& a, cons
         HIP_TRY(hipMemcpyAsync(a.lwup, a.up, nb.up, hipMemcpyDeviceToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(a.lwyp, a.yp, nb.yp, hipMemcpyDeviceToDevice, h->stream));
       }
-      int rcs = (path == LoopPath::StepPrepared ? step_on_route : solve_on_route)(h, a.up, a.yp, (double*)h->d_uopt.p, (double*)h->d_cost.p,
-                                                                                  (int32_t*)h->d_status.p, nullptr);
+      launch_fn solve = path == LoopPath::StepPrepared ? step_on_route : solve_on_route;
+      if (a.uref) {       // the solve at step t reads row t of the schedules in place (the instance stride spans the schedule)
+        h->sp_us = a.uref + (size_t)t * p.m; h->sp_ys = a.yref + (size_t)t * p.p;
+        h->sp_su = (long long)a.n_steps * p.m; h->sp_sy = (long long)a.n_steps * p.p;
+        solve = setpoint_step_on_route;
+      }
+      int rcs = solve(h, a.up, a.yp, (double*)h->d_uopt.p, (double*)h->d_cost.p, (int32_t*)h->d_status.p, nullptr);
+      h->sp_us = h->sp_ys = nullptr;
       if (rcs) return rcs;
       const int nsub = (t + a.n_mpc_step <= a.n_steps) ? a.n_mpc_step : a.n_steps - t;
       hipLaunchKernelGGL(ddmpc_plant_kernel, dim3(pblocks), dim3(128), 0, h->stream, (long long)B, a.ns, p.m, p.p, p.n,
@@ -3536,7 +3630,7 @@ int ddmpc_closed_loop_setpoints(ddmpc_handle* h, const ddmpc_plant* plant, int32
                                 double* u_sys, double* y_sys, int32_t* status, int mem) {
   if (!h || !u_ref || !y_ref) return fail(DDMPC_ERR_INVALID, "null argument");
   if (!setpoint_on(h))
-    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box)");
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box), or beyond 271 rows DDMPC_OPT_LARGE_SETPOINTS = 1");
   if (h->bounded && !h->setpoint_box_law && !h->setpoint_convex_law)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints on a handle with input or output bounds needs DDMPC_OPT_SETPOINT_BOX_LAW = 1");
   return closed_loop_impl(h, "ddmpc_closed_loop_setpoints", plant, n_steps, n_mpc_step, x, u_past, y_past, w, u_ref, y_ref, u_sys,
@@ -3583,10 +3677,11 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
   // the plant steps that follow it move u_past / y_past on, so that window is kept apart
   if ((rc = h->d_lwup.ensure(nb.up)) || (rc = h->d_lwyp.ensure(nb.yp))) return rc;
   a.lwup = (double*)h->d_lwup.p; a.lwyp = (double*)h->d_lwyp.p;
-  if (u_ref) {
-    // DDMPC_OPT_SETPOINT_LAW: one fused launch, no per-step fall-back (DDMPC_OPT_CLOSED_LOOP_PATH / _GRAPH are not looked at)
-    if ((size_t)n_mpc_step * m > (size_t)WARM_MAX_NF)
-      return fail(DDMPC_ERR_UNSUPPORTED, "%s: n_mpc_step * m = %d, the fused loop holds %d inputs per solve", what, n_mpc_step * m, WARM_MAX_NF);
+  // the fused loops of DDMPC_OPT_SETPOINT_LAW / _BOX_LAW / _CONVEX_LAW hold n_mpc_step * m inputs per solve in LDS (checked before
+  // anything is staged); the per-step path of DDMPC_OPT_LARGE_SETPOINTS has no such limit
+  if (u_ref && !h->large_setpoints && (size_t)n_mpc_step * m > (size_t)WARM_MAX_NF)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: n_mpc_step * m = %d, the fused loop holds %d inputs per solve", what, n_mpc_step * m, WARM_MAX_NF);
+  if (u_ref) {                       // both setpoint loops: the schedules on the device, the preparation in place
     if (mem == DDMPC_MEM_HOST) {     // the schedules are [batch, n_steps, m] and [batch, n_steps, p]: the sizes of u_sys and y_sys
       if ((rc = h->d_uref.ensure(nb.us)) || (rc = h->d_yref.ensure(nb.w))) return rc;
       HIP_TRY(hipMemcpyAsync(h->d_uref.p, u_ref, nb.us, hipMemcpyHostToDevice, h->stream));
@@ -3594,6 +3689,19 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
       u_ref = (const double*)h->d_uref.p; y_ref = (const double*)h->d_yref.p;
     }
     if (!prep_valid(h) && (rc = ddmpc_prepare(h))) return rc;
+  }
+  if (u_ref && h->large_setpoints) {
+    // DDMPC_OPT_LARGE_SETPOINTS: the per-step path on what ddmpc_prepare kept (no fused kernel at this size, so no limit on
+    // n_mpc_step * m; DDMPC_OPT_CLOSED_LOOP_PATH is not looked at: the cold solve knows the shared setpoints only)
+    h->loop_kernel = kLoopKernel[(int)LoopPath::StepPrepared];
+    a.uref = u_ref; a.yref = y_ref;
+    rc = run_step_loop(h, LoopPath::StepPrepared, a, nb);
+    h->last = LastSolve{};             // (as ddmpc_step_setpoints: nothing ddmpc_get_solution could reconstruct)
+    h->last.setpoint_call = true;
+    return rc ? rc : copy_loop_outputs(h, mem, nb, a, user, status);
+  }
+  if (u_ref) {
+    // DDMPC_OPT_SETPOINT_LAW: one fused launch, no per-step fall-back (DDMPC_OPT_CLOSED_LOOP_PATH / _GRAPH are not looked at)
     h->loop_kernel = h->setpoint_convex_law ? "ddmpc_closed_loop_setpoint_convex_kernel"
                      : select_route(h) == Route::BoxLaw ? "ddmpc_closed_loop_setpoint_box_kernel" : "ddmpc_closed_loop_setpoint_kernel";
     if ((rc = launch_setpoint_loop(h, a, u_ref, y_ref))) return rc;
@@ -3629,6 +3737,9 @@ const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h) { return h ? h->loop_
 
 int ddmpc_debug_stamps(ddmpc_handle* h, int enable, uint64_t* out) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
+  if (enable && h->large_setpoints)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_debug_stamps is not available with DDMPC_OPT_LARGE_SETPOINTS = 1: stamps select the "
+                "one-workgroup kernel, and the phase kernels serve the setpoint calls only");
   if (enable && h->large && h->bounded)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_debug_stamps is not available on a handle with input or output bounds beyond 271 rows: stamps "
                 "select the one-workgroup kernel, and the phase kernels serve the bounds only");

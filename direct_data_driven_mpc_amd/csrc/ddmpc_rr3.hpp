@@ -51,6 +51,23 @@ struct Rr3 {
 };
 enum : int { R3_X = 0 /* beta, component order: what the Hankel kernel reads */, R3_BETA /* position order */, R3_T0, R3_NV };
 
+// DDMPC_OPT_LARGE_SETPOINTS: a setpoint per instance.  A trailing argument of rr3_solve_kernel, present in the
+// instantiations of ddmpc_step_setpoints / ddmpc_closed_loop_setpoints only: instance b reads u_s at us + b su (m doubles) and
+// y_s at ys + b sy (p doubles) -- su = m, sy = p for a step; su = n_steps m, sy = n_steps p with the bases moved to the row of
+// the solve for a schedule, which is then read in place.
+struct Rr3Setpoint {
+  const double* us; const double* ys;
+  long long su, sy;
+};
+// The setpoint of the channel of component rho (rho = k (m + p) + channel, the rule of ddmpc_setpoint_law.hpp): the target of
+// every component that takes it from a setpoint (tabi[1][rho] < 0), and tb of the output stage.  Without the argument: the
+// shared table row, as ever.
+__device__ __forceinline__ double rr3_setpoint(const KParams& P, int RPs, int rho, long long) { return P.tabd[2 * RPs + rho]; }
+__device__ __forceinline__ double rr3_setpoint(const KParams& P, int, int rho, long long b, const Rr3Setpoint& sp) {
+  const int c = rho % P.nch;
+  return (c < P.m) ? sp.us[b * sp.su + c] : sp.ys[b * sp.sy + (c - P.m)];
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // + lam D0 on the diagonal of the permuted Gram matrix (the Gram kernel wrote G itself); dense weighting matrices
 // (controller.py:708-710): + lam W^-1 on every pair of components (P.dmat, component order, shared by the batch -- L2).
@@ -408,11 +425,14 @@ __device__ __forceinline__ void rr3_small_solve(const double* Sm, int k, const d
 // The solve on the kept factor.  grid = batch, RR2_TS threads, dynamic LDS (Rr3Lds + W).  refine != 0: beta and everything the
 // refinement launch needs go to global memory and the outputs are left to rr3_refine_kernel; else the outputs are written here.
 // only (nullptr: every instance): per-instance flags, the instances without one leave at once (the filtered re-solve of the law step).
+// Sp...: empty (the kernel as it is launched without setpoints) or one Rr3Setpoint (both launches; an instance marked 5 -- more
+// than RR3_KMAX switched components, a failed pivot of the k x k system, a switched component with d <= 0 -- is reported as 4: the fall-back kernel knows the shared setpoints only and is not launched behind these instantiations).
 // ---------------------------------------------------------------------------------------------------------------
+template <class... Sp>
 __device__ __forceinline__ void rr3_outputs(const KParams& P, int RPs, const Rr3& S, long long b, const int* perm, const double* tv, const double* bv,
                                             const int* act, int st, int iter, double* red, double* __restrict__ u_opt, double* __restrict__ cost,
                                             int* __restrict__ status, int* __restrict__ iters, double* __restrict__ beta_ws,
-                                            signed char* __restrict__ act_ws, double* wa, double* wb) {
+                                            signed char* __restrict__ act_ws, double* wa, double* wb, const Sp&... sp) {
   // wa, wb: two LDS vectors of r doubles that are free by now (dense weighting matrices: beta in component order, W^-1 beta)
   const int tid = threadIdx.x, nthr = blockDim.x, r = P.r;
   const int n = P.npu / P.m;
@@ -434,7 +454,7 @@ __device__ __forceinline__ void rr3_outputs(const KParams& P, int RPs, const Rr3
       const double t = tv[i] + s_act * P.bound;
       const double z = t - P.lam * (D * bb + (P.dense_w ? wb[rho] : 0.0));
       const double wq = P.tabd[3 * RPs + rho];
-      const double tb = P.tabd[2 * RPs + rho];
+      const double tb = rr3_setpoint(P, RPs, rho, b, sp...);
       const int oidx = P.tabi[2 * RPs + rho];
       const int kind = P.tabi[0 * RPs + rho];
       if (!(fabs(bb) < 1e300)) bad = 1.0;
@@ -469,12 +489,14 @@ __device__ __forceinline__ void rr3_outputs(const KParams& P, int RPs, const Rr3
   }
 }
 
-template <bool REFINE_PASS>
+template <bool REFINE_PASS, class... Sp>
 __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_kernel(Rr3 S, KParams P, int RPs, const double* __restrict__ u_past,
                                                            const double* __restrict__ y_past, double* __restrict__ u_opt,
                                                            double* __restrict__ cost, int* __restrict__ status, int* __restrict__ iters,
                                                            double* __restrict__ beta_ws, signed char* __restrict__ act_ws, int defer_outputs,
-                                                           const int* __restrict__ only) {
+                                                           const int* __restrict__ only, Sp... sp) {
+  static_assert(sizeof...(Sp) <= 1, "one setpoint argument at most");
+  constexpr bool SETPOINTS = sizeof...(Sp) != 0;
   extern __shared__ __attribute__((aligned(16))) double r3_lds[];
   const long long b = blockIdx.x;
   if (only != nullptr && only[b] == 0) return;               // (workgroup-uniform) the law step of ddmpc_rr3_law.hpp finished this instance
@@ -548,7 +570,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_kernel(Rr3 S, KParams P, 
       if (i < r) {
         const int rho = perm[i];
         const int pidx = P.tabi[1 * RPs + rho];
-        t = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : P.tabd[2 * RPs + rho];
+        t = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : rr3_setpoint(P, RPs, rho, b, sp...);
         nbad += S.skip[b * S.s_stride + i] ? 1.0 : 0.0;
       }
       tv[i] = t; act[i] = 0; y2[i] = 0.0; bv[i] = 0.0;
@@ -668,9 +690,9 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_kernel(Rr3 S, KParams P, 
     }
     if (!defer_outputs || st != 0) {
       __syncthreads();
-      rr3_outputs(P, RPs, S, b, perm, tv, bv, act, st == 5 ? 4 : st, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws, y2, yv);
+      rr3_outputs(P, RPs, S, b, perm, tv, bv, act, st == 5 ? 4 : st, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws, y2, yv, sp...);
       __syncthreads();
-      if (tid == 0 && st == 5) status[b] = 5;                             // (host: finished by ddmpc_large_solve_kernel)
+      if (!SETPOINTS && tid == 0 && st == 5) status[b] = 5;               // (host: finished by ddmpc_large_solve_kernel)
     }
   } else {
     // ---- one pass of iterative refinement on the system of the final active set, then the outputs.
@@ -713,7 +735,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_kernel(Rr3 S, KParams P, 
     rr3_trsv_bwd(G, m64, r, live, nb, 0, yv, y2, red, tmp);                                                   // delta
     for (int i = tid; i < r; i += nthr) bv[i] += y2[i];
     __syncthreads();
-    rr3_outputs(P, RPs, S, b, perm, tv, bv, act, 0, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws, y2, yv);
+    rr3_outputs(P, RPs, S, b, perm, tv, bv, act, 0, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws, y2, yv, sp...);
   }
 }
 

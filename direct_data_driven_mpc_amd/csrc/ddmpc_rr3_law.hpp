@@ -17,6 +17,8 @@
 //   rr3_law_step_kernel   per control step: beta = g0 + G' w (the law streamed once), z, optimal_u, cost, status, the beta / active-set
 //                         workspace and the rr3 record -- or, under the slack box, a flag when a boxed slack leaves the box (those
 //                         instances are re-solved by rr3_solve_kernel on the kept factor, restricted to them).
+//   rr3_setpoint_law_step_kernel   DDMPC_OPT_LARGE_SETPOINTS: its twin with a setpoint per instance -- the law's rows 1 .. nf and the
+//                         m + p rows of S = K0^-1 [1_c], which the three build kernels form as a second kind of right-hand side.
 #pragma once
 #include "ddmpc_rr3.hpp"
 
@@ -24,8 +26,15 @@ namespace ddmpc {
 
 // Value of right-hand side c (0: t0, 1 .. nf: the unit window e_{c-1}) at component rho: column c of the law is row c of
 // ddmpc_get_gain's [nf+1][r] block.
-__device__ __forceinline__ double rr3_law_e(const KParams& P, int RPs, int rho, int c) {
+// The right-hand sides of the three build kernels come in two kinds.  RR3_RHS_LAW: the nf + 1 columns above, into the law.
+// RR3_RHS_SETPOINT (DDMPC_OPT_LARGE_SETPOINTS): the m + p multi-hot columns 1_c of ddmpc_setpoint_law.hpp -- one
+// where rho mod (m+p) = c and the component takes its target from a setpoint --, `nf` then counts these columns, into S
+// [batch][m+p][r].  The kernels' `law` argument is the destination of the kind.
+enum : int { RR3_RHS_LAW = 0, RR3_RHS_SETPOINT = 1 };
+__device__ __forceinline__ int rr3_law_nrhs(int nf, int kind) { return kind == RR3_RHS_SETPOINT ? nf : nf + 1; }
+__device__ __forceinline__ double rr3_law_e(const KParams& P, int RPs, int rho, int c, int kind = RR3_RHS_LAW) {
   const int pidx = P.tabi[1 * RPs + rho];
+  if (kind == RR3_RHS_SETPOINT) return (pidx < 0 && rho % P.nch == c) ? 1.0 : 0.0;
   if (c == 0) return (pidx < 0) ? P.tabd[2 * RPs + rho] : 0.0;
   return (pidx == c - 1) ? 1.0 : 0.0;
 }
@@ -35,12 +44,13 @@ __device__ __forceinline__ double rr3_law_e(const KParams& P, int RPs, int rho, 
 // only: instances that take part (nullptr: all); nolaw: set to 1 for an instance whose factor has a failed pivot.
 template <bool FROM_BUF>
 __global__ __launch_bounds__(RR2_TS) void rr3_law_fwd_kernel(Rr3 S, KParams P, int RPs, long long b0, int nf, const double* __restrict__ rhs,
-                                                             const int* __restrict__ only, double* __restrict__ Y, int* __restrict__ nolaw) {
+                                                             const int* __restrict__ only, double* __restrict__ Y, int* __restrict__ nolaw,
+                                                             int kind) {
   __shared__ __attribute__((aligned(16))) double Pb[64 * 65];
   const int cb = blockIdx.x, ncb = gridDim.x;
   const long long bl = blockIdx.y, b = b0 + bl;
   if (only != nullptr && only[b] == 0) return;                              // (workgroup-uniform)
-  const int r = S.r, nrhs = nf + 1, VL = (r + 63) & ~63;
+  const int r = S.r, nrhs = rr3_law_nrhs(nf, kind), VL = (r + 63) & ~63;
   const int* perm = S.perm;
   const double* Lm = S.ws + b * S.stride;
   const double* m64 = S.m64 + b * S.m64_stride;
@@ -92,7 +102,7 @@ __global__ __launch_bounds__(RR2_TS) void rr3_law_fwd_kernel(Rr3 S, KParams P, i
         double e = 0.0;
         if (i < r && ccol[t] >= 0) {
           const int rho = perm[i];
-          e = FROM_BUF ? rhs[(bl * nrhs + ccol[t]) * (long long)r + rho] : rr3_law_e(P, RPs, rho, ccol[t]);
+          e = FROM_BUF ? rhs[(bl * nrhs + ccol[t]) * (long long)r + rho] : rr3_law_e(P, RPs, rho, ccol[t], kind);
         }
         Pb[rloc * 65 + 16 * (ch + 2 * t) + l15] = e - acc[t][q];
       }
@@ -124,12 +134,12 @@ __global__ __launch_bounds__(RR2_TS) void rr3_law_fwd_kernel(Rr3 S, KParams P, i
 // an instance whose law has a non-finite entry.
 template <bool ADD>
 __global__ __launch_bounds__(RR2_TS) void rr3_law_bwd_kernel(Rr3 S, long long b0, int nf, const int* __restrict__ only, double* __restrict__ Y,
-                                                             double* __restrict__ law, int* __restrict__ nolaw) {
+                                                             double* __restrict__ law, int* __restrict__ nolaw, int kind) {
   __shared__ __attribute__((aligned(16))) double Pb[64 * 65];
   const int cb = blockIdx.x, ncb = gridDim.x;
   const long long bl = blockIdx.y, b = b0 + bl;
   if (only != nullptr && only[b] == 0) return;                              // (workgroup-uniform)
-  const int r = S.r, nrhs = nf + 1, VL = (r + 63) & ~63;
+  const int r = S.r, nrhs = rr3_law_nrhs(nf, kind), VL = (r + 63) & ~63;
   const int* perm = S.perm;
   const double* Lm = S.ws + b * S.stride;
   const double* m64 = S.m64 + b * S.m64_stride;
@@ -220,16 +230,16 @@ __global__ __launch_bounds__(RR2_TS) void rr3_law_bwd_kernel(Rr3 S, long long b0
 // grid = (nf+1, instances of the chunk), 256 threads.
 __global__ __launch_bounds__(256) void rr3_law_resid_kernel(KParams P, int RPs, long long b0, int nf, const double* __restrict__ law,
                                                             const double* __restrict__ ZP, int VL, double* __restrict__ R,
-                                                            int* __restrict__ flag, int force, int* __restrict__ nolaw) {
+                                                            int* __restrict__ flag, int force, int* __restrict__ nolaw, int kind) {
   __shared__ double red[8];
-  const int c = blockIdx.x, nrhs = nf + 1, r = P.r, tid = threadIdx.x;
+  const int c = blockIdx.x, nrhs = rr3_law_nrhs(nf, kind), r = P.r, tid = threadIdx.x;
   const long long bl = blockIdx.y, b = b0 + bl;
   const double* xc = law + (b * nrhs + c) * (long long)r;
   const double* zp = ZP + (bl * nrhs + c) * (long long)RR2_NG * VL;
   double* Rc = R + (bl * nrhs + c) * (long long)r;
   double rmx = 0.0, emx = 0.0;
   for (int rho = tid; rho < r; rho += blockDim.x) {
-    const double e = rr3_law_e(P, RPs, rho, c);
+    const double e = rr3_law_e(P, RPs, rho, c, kind);
     double hz = 0.0;
 #pragma unroll
     for (int g = 0; g < RR2_NG; ++g) hz += zp[g * (long long)VL + rho];
@@ -332,6 +342,94 @@ __global__ __launch_bounds__(RR2_TS) void rr3_law_step_kernel(Rr3 S, KParams P, 
     kq[4 + RR3_KMAX + S.rv] = (int)(t_begin & 0x7fffffff); kq[4 + RR3_KMAX + S.rv + 1] = (int)(t_end - t_begin);
   }
   rr3_outputs(P, RPs, S, b, perm, tv, bv, act, 0, 1, red, u_opt, cost, status, iters, beta_ws, act_ws, part, part + 1024);
+}
+
+// DDMPC_OPT_LARGE_SETPOINTS: the twin of rr3_law_step_kernel with a setpoint per instance.
+//     beta = sum_f w_f law[1 + f] + sum_c s_c S[c]        (column 0 of the law, the offset at the shared setpoints, is not read)
+// The same streaming scheme over nf + (m+p) rows: the rows of S follow those of the law in the four groups.  tv and tb of the
+// output stage come from the window or the instance's setpoint (sp).  An instance with no law, with no setpoint law (nosp) or
+// outside the box is left to the filtered solve on the kept factor with the same setpoints.  A non-finite setpoint reaches
+// every row of beta through S: status 4 from the output stage (or from the solve, should the switch test flag it).
+__global__ __launch_bounds__(RR2_TS) void rr3_setpoint_law_step_kernel(Rr3 S, KParams P, int RPs, int nf, const double* __restrict__ law,
+                                                                       const int* __restrict__ nolaw, const double* __restrict__ u_past,
+                                                                       const double* __restrict__ y_past, double* __restrict__ u_opt,
+                                                                       double* __restrict__ cost, int* __restrict__ status,
+                                                                       int* __restrict__ iters, double* __restrict__ beta_ws,
+                                                                       signed char* __restrict__ act_ws, int* __restrict__ need,
+                                                                       int* __restrict__ si, const double* __restrict__ sgain,
+                                                                       const int* __restrict__ nosp, Rr3Setpoint sp) {
+  __shared__ __attribute__((aligned(16))) double part[RR3_LAW_NG * 1024];
+  __shared__ double wv[2 * WARM_MAX_NF];                                    // the window (nf), then the setpoint (m + p <= nf)
+  __shared__ double tv[1024], bv[1024];
+  __shared__ int act[1024];
+  __shared__ double red[16];
+  const long long b = blockIdx.x;
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwave = nthr >> 6;
+  if (nolaw[b] != 0 || nosp[b] != 0) {                                      // (workgroup-uniform)
+    if (tid == 0) { need[b] = 1; si[2 * b] = 1; }
+    return;
+  }
+  const long long t_begin = (long long)__builtin_amdgcn_s_memrealtime();
+  const int r = S.r, nch = P.nch, nrows = nf + nch, n = P.npu / P.m;
+  const int* perm = S.perm;
+  const double* up = u_past + b * (long long)P.npu;
+  const double* yp = y_past + b * (long long)(n * P.p);
+  for (int j = tid; j < nrows; j += nthr)
+    wv[j] = (j < P.npu) ? up[j] : (j < nf) ? yp[j - P.npu]
+            : (j - nf < P.m) ? sp.us[b * sp.su + (j - nf)] : sp.ys[b * sp.sy + (j - nf - P.m)];
+  __syncthreads();
+  // row j of the stream: law row 1 + j (j < nf), else row j - nf of S
+  const double* gl = law + (b * (nf + 1) + 1) * (long long)r;
+  const double* sg = sgain + b * nch * (long long)r;
+  const int nc = (r + 63) >> 6, per = (nrows + RR3_LAW_NG - 1) / RR3_LAW_NG;
+  for (int task = wave; task < nc * RR3_LAW_NG; task += nwave) {
+    const int c = task / RR3_LAW_NG, g = task - c * RR3_LAW_NG;
+    const int rho = 64 * c + lane, rc = rho < r ? rho : r - 1;
+    const int j0 = g * per, j1 = (j0 + per < nrows) ? j0 + per : nrows;
+    double s0 = 0.0, s1 = 0.0;
+    int j = j0;
+    for (; j + 8 <= j1; j += 8) {
+      double v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (j + e < nf) ? gl[(long long)(j + e) * r + rc] : sg[(long long)(j + e - nf) * r + rc];
+#pragma unroll
+      for (int e = 0; e < 8; e += 2) { s0 = fma(v[e], wv[j + e], s0); s1 = fma(v[e + 1], wv[j + e + 1], s1); }
+    }
+    for (; j < j1; ++j) s0 = fma((j < nf) ? gl[(long long)j * r + rc] : sg[(long long)(j - nf) * r + rc], wv[j], s0);
+    part[g * 1024 + rho] = s0 + s1;
+  }
+  __syncthreads();
+  for (int i = tid; i < r; i += nthr) {
+    const int rho = perm[i];
+    double s = 0.0;
+#pragma unroll
+    for (int g = 0; g < RR3_LAW_NG; ++g) s += part[g * 1024 + rho];
+    const int pidx = P.tabi[1 * RPs + rho];
+    bv[i] = s;
+    tv[i] = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : rr3_setpoint(P, RPs, rho, b, sp);
+    act[i] = 0;
+  }
+  __syncthreads();
+  int out = 0;
+  if (P.convex)                                                            // slack box: the first iterate's switch test, on beta
+    for (int i = S.nA + tid; i < r; i += nthr) {
+      const double sh = P.sig_scale * bv[i];
+      out |= (sh > P.bound || sh < -P.bound) ? 1 : 0;
+    }
+  if (__syncthreads_or(out)) {
+    if (tid == 0) { need[b] = 1; si[2 * b] = 1; }
+    return;
+  }
+  int* kq = S.kq + b * S.kstride;
+  for (int i = tid; i < r; i += nthr) kq[4 + RR3_KMAX + i] = 0;
+  if (tid == 0) {
+    need[b] = 0; si[2 * b] = 0;
+    kq[0] = 0; kq[1] = 0; kq[2] = 1; kq[3] = 0;
+    const long long t_end = (long long)__builtin_amdgcn_s_memrealtime();
+    kq[4 + RR3_KMAX + S.rv] = (int)(t_begin & 0x7fffffff); kq[4 + RR3_KMAX + S.rv + 1] = (int)(t_end - t_begin);
+  }
+  rr3_outputs(P, RPs, S, b, perm, tv, bv, act, 0, 1, red, u_opt, cost, status, iters, beta_ws, act_ws, part, part + 1024, sp);
 }
 
 }  // namespace ddmpc

@@ -329,6 +329,23 @@ class BatchedDDMPC:
         is not available after the calls."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_SETPOINT_CONVEX_LAW, 1 if on else 0))
 
+    def set_large_setpoints(self, on: bool) -> None:
+        """ROBUST controllers on the phase kernels (272 .. 1024 rows), slack NONE or the CONVEX slack box, scalar / diagonal
+        weights, no bounds: True = `step_setpoints` and `closed_loop_setpoints` are open (DDMPC_OPT_LARGE_SETPOINTS).  The
+        factor `prepare` keeps does not depend on the setpoint, so the step on the kept factor takes the instance's own
+        setpoint: same launches, statuses and `iters` as `step`, active-set iteration under the slack box included.
+        With `set_large_affine_law(True)` as well `prepare` forms S = K0^-1 [1_c] next to the law ((m+p) r doubles per
+        instance, built and refined apart from it), the step is one launch on the law and S plus the kept-factor solve for
+        the instances without a law, without a setpoint law or outside the slack box, and `setpoint_gain` returns S.
+        `solve`, `step`, `closed_loop`, `gain` and `get_solution` stay bit-equal to False (default).  Changing the value
+        forgets what `prepare` kept.  Raises ERR_UNSUPPORTED on NOMINAL controllers, dense weights, up to 271 rows (use
+        `set_setpoint_law` / `set_setpoint_box_law` / `set_setpoint_convex_law`), more than 1024 rows, the one-workgroup
+        pipeline, debug stamps, batch > 65535, n(m+p) > 256 and a handle with bounds (bounds, the one-workgroup pipeline and
+        stamps are refused afterwards, too).  Under the slack box an instance with more than 64 slack components switched at
+        once, or with a failed pivot in the small system of the switched components, is solver_error in the two calls (`step` hands it to a fall-back kernel that knows the shared setpoints only);
+        `get_solution` is not available after them."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_SETPOINTS, 1 if on else 0))
+
     def step_setpoints(self, u_past, y_past, u_s, y_s, u_opt=None, cost=None, status=None, iters=None):
         """Warm control step with one setpoint per instance (`ddmpc_step_setpoints`): u_s [batch,m], y_s [batch,p], in the
         memory space of the windows; same outputs and array / tensor handling as `solve`.  The handle's own setpoints are not
@@ -336,11 +353,15 @@ class BatchedDDMPC:
         `set_setpoint_convex_law(True)` (CONVEX slack box), or
         `set_setpoint_box_law(True)`, which a handle with input / output bounds requires: there the step iterates on the box
         as `step` does (`iters` counts its solves; infeasible with NaN outputs for a setpoint outside the bounds under the
-        terminal constraint)."""
+        terminal constraint).  Beyond 271 rows: `set_large_setpoints(True)` -- the step of `step` on the kept factor with the
+        instance's setpoint, or with `set_large_affine_law(True)` one launch on the law and S plus the kept-factor solve for
+        the instances it leaves."""
         return self._solve(u_past, y_past, u_opt, cost, status, iters, True, (u_s, y_s))
 
     def setpoint_gain(self) -> np.ndarray:
-        """S of the prepared law: [batch, m+p, r], beta = gain[:,1:]^T [u_past; y_past] + S^T [u_s; y_s] (component order)."""
+        """S of the prepared law: [batch, m+p, r], beta = gain[:,1:]^T [u_past; y_past] + S^T [u_s; y_s] (component order).
+        Beyond 271 rows (`set_large_setpoints(True)`) S exists only next to the law of `set_large_affine_law(True)`:
+        ERR_NOT_READY otherwise."""
         out = np.empty((self.batch, self.m + self.p, (self.m + self.p) * (self.L + self.n)))
         L.check(self._lib.ddmpc_get_setpoint_gain(self._h, C.c_void_p(out.ctypes.data), L.MEM_HOST))
         return out
@@ -350,7 +371,9 @@ class BatchedDDMPC:
         [batch,n_steps,m], y_ref [batch,n_steps,p]; the solve made at step t tracks row t.  Needs `set_setpoint_law(True)`,
         `set_setpoint_convex_law(True)` (CONVEX slack box: 'ddmpc_closed_loop_setpoint_convex_kernel'), or
         `set_setpoint_box_law(True)`, which a handle with input / output bounds requires ('ddmpc_closed_loop_setpoint_box_kernel':
-        an instance stops at a solve that is not optimal and at a refused setpoint)."""
+        an instance stops at a solve that is not optimal and at a refused setpoint).  Beyond 271 rows
+        (`set_large_setpoints(True)`) the loop runs per step ('ddmpc_plant_kernel'), the solve at step t reading row t of the
+        schedules in place; n_mpc_step * m has no limit there."""
         return self.closed_loop(A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step, _ref=(u_ref, y_ref))
 
     def closed_loop(self, A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step: int = 1, _ref=None):

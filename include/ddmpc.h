@@ -370,6 +370,38 @@ extern "C" {
                                          LDS, with n(m+p) > 256 and where a boxed output component has a Q entry of 0 (the rule of
                                          DDMPC_OPT_CONVEX_WARM_LAW).  LIMITS: the bounds are the handle's, not per instance;
                                          DDMPC_REFINE_ALWAYS stays refused on bounded handles */
+#define DDMPC_OPT_LARGE_SETPOINTS 21     /* Per-instance, per-step setpoints beyond 271 rows: 1 = ddmpc_step_setpoints,
+                                         ddmpc_closed_loop_setpoints and ddmpc_get_setpoint_gain are open on a ROBUST handle on the
+                                         phase kernels (272 .. 1024 rows, scalar / diagonal weights, slack NONE or the CONVEX slack
+                                         box, no input / output bounds).  The factor K0 = L L' that ddmpc_prepare keeps does not depend
+                                         on the setpoint, so ddmpc_step_setpoints is the step of ddmpc_step on the kept factor with the
+                                         instance's own setpoint as the target of its setpoint rows and of the output stage: the same
+                                         launches, and under the slack box the same active-set iteration, max_iter cap, statuses and
+                                         `iters`.  With DDMPC_OPT_LARGE_AFFINE_LAW = 1 as well, ddmpc_prepare forms
+                                         S = K0^-1 [1_c] next to the law ((m+p) r more doubles per instance; built and refined apart
+                                         from the law, with the law's threshold and refine_max; an instance whose S misses the
+                                         threshold has "no setpoint law", which ddmpc_step does not look at), and the step is one
+                                         launch of "rr3_setpoint_law_step_kernel" -- beta = sum_f w_f gain[1+f] + sum_c s_c S[c] --
+                                         followed in the same call by the solve on the kept factor for the instances without a law,
+                                         without a setpoint law or outside the slack box.  ddmpc_closed_loop_setpoints runs the
+                                         per-step path ("ddmpc_plant_kernel"; no limit on n_mpc_step * m).  Per instance a non-finite
+                                         setpoint is DDMPC_STATUS_SOLVER_ERROR; neighbours are untouched.  ddmpc_get_solution after
+                                         the two calls is DDMPC_ERR_NOT_READY.  ddmpc_solve, ddmpc_step, ddmpc_closed_loop,
+                                         ddmpc_get_gain and ddmpc_get_solution launch what they launch with 0 and return bit-equal
+                                         results.  0 (default; accepted on every handle).  Values other than 0 / 1:
+                                         DDMPC_ERR_INVALID.  Changing the value forgets what ddmpc_prepare kept.  Setting 1 is
+                                         DDMPC_ERR_UNSUPPORTED, with a message that names the reason, on NOMINAL controllers, with
+                                         DDMPC_WEIGHT_DENSE, up to 271 rows (options 18 - 20 serve those), beyond 1024 rows, on a
+                                         handle that is not on the phase kernels (DDMPC_PIPELINE_ONE_WORKGROUP, ddmpc_debug_stamps,
+                                         batch > 65535), with n(m+p) > 256 and on a handle with input or output bounds; in the
+                                         reverse order the bounds calls, DDMPC_PIPELINE_ONE_WORKGROUP and ddmpc_debug_stamps are
+                                         refused on a handle with the option on.  LIMIT (CONVEX): an instance with more than 64 slack
+                                         components switched at once, or whose 64 x 64-at-most Woodbury system of the switched
+                                         components has a failed pivot, is DDMPC_STATUS_SOLVER_ERROR in the two calls (ddmpc_step hands
+                                         such an instance to a fall-back kernel, which knows the handle's shared setpoints only and
+                                         is not launched here); with the terminal constraint a setpoint that is no equilibrium of the
+                                         plant binds the terminal slacks, n p of them.  Options 18 - 20 keep their refusals beyond
+                                         271 rows */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -647,7 +679,8 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
 
 /* Per-instance, per-step setpoints (DDMPC_OPT_SETPOINT_LAW = 1, or DDMPC_OPT_SETPOINT_BOX_LAW = 1 -- see there for what the
  * calls do on a handle with input / output bounds --, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 -- see there for what they do under
- * the CONVEX slack box; DDMPC_ERR_UNSUPPORTED on all three calls without any of them).  The
+ * the CONVEX slack box --, or beyond 271 rows DDMPC_OPT_LARGE_SETPOINTS = 1 -- see there and the last paragraph below;
+ * DDMPC_ERR_UNSUPPORTED on all three calls without any of them).  The
  * reduced system K0 beta = t is linear in t and t is linear in the setpoints, so with m + p more columns the law of
  * ddmpc_prepare takes the setpoint as an argument:
  *     beta_b = sum_f past_b[f] gain[b][1+f][:] + sum_c s_b[c] S[b][c][:],      s_b = [u_s_b ; y_s_b],
@@ -671,7 +704,17 @@ int ddmpc_closed_loop(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps
  *   the CONVEX slack box, bounded or not: DDMPC_OPT_SETPOINT_CONVEX_LAW); scalar / diagonal weights;
  *   at most 271 rows and a trajectory that fits the LDS; n(m+p) <= 256.  The cold kernels know the handle's shared setpoints
  *   only (ddmpc_solve).  Under DDMPC_REFINE_AUTO the instances whose law and S are refined are chosen from solves at the
- *   handle's own setpoints, not at the ones passed later. */
+ *   handle's own setpoints, not at the ones passed later.
+ * Beyond 271 rows (DDMPC_OPT_LARGE_SETPOINTS = 1; ROBUST on the phase kernels, 272 .. 1024 rows, slack NONE or CONVEX, scalar /
+ *   diagonal weights, no bounds, n(m+p) <= 256): ddmpc_step_setpoints is the step on the kept factor with the instance's
+ *   setpoint (statuses and iters of ddmpc_step), or with DDMPC_OPT_LARGE_AFFINE_LAW = 1 one launch of
+ *   "rr3_setpoint_law_step_kernel" and the solve on the kept factor for the instances it leaves.  ddmpc_closed_loop_setpoints
+ *   runs per step ("ddmpc_plant_kernel"), reads row t of the schedules in place and has no limit on n_mpc_step * m.
+ *   ddmpc_get_setpoint_gain returns S when the law was built with it, else DDMPC_ERR_NOT_READY (without
+ *   DDMPC_OPT_LARGE_AFFINE_LAW no S is formed).  LIMITS: under the CONVEX slack box an instance with more than 64 slack components
+ *   switched at once, or with a failed pivot in the small system of the switched components, is DDMPC_STATUS_SOLVER_ERROR (the
+ *   two cases ddmpc_step hands to its fall-back kernel); bounded handles, the fall-back kernel, NOMINAL controllers, dense weights and
+ *   more than 1024 rows are not served. */
 int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_past, const double* u_s, const double* y_s,
                          double* u_opt, double* cost, int32_t* status, int32_t* iters, int mem);
 int ddmpc_closed_loop_setpoints(ddmpc_handle* h, const ddmpc_plant* plant, int32_t n_steps, int32_t n_mpc_step,
@@ -690,7 +733,7 @@ const char* ddmpc_kernel_name(ddmpc_handle* h);
 /* Name of the kernel that stepped the plant in the last ddmpc_closed_loop: "ddmpc_closed_loop_warm_kernel" or
  * "ddmpc_closed_loop_convex_warm_kernel" / "ddmpc_closed_loop_box_kernel" (input bounds) when the whole loop ran fused in one launch, "ddmpc_plant_kernel" when it ran
  * per step (DDMPC_PATH_COLD, shapes beyond the fused loops' bounds, NOMINAL instances without a law, laws taken from
- * refining solves under DDMPC_OPT_CONVEX_WARM_LAW, handles beyond 271 rows); "ddmpc_closed_loop_setpoint_kernel" /
+ * refining solves under DDMPC_OPT_CONVEX_WARM_LAW, handles beyond 271 rows -- ddmpc_closed_loop_setpoints included there); "ddmpc_closed_loop_setpoint_kernel" /
  * "ddmpc_closed_loop_setpoint_box_kernel" / "ddmpc_closed_loop_setpoint_convex_kernel" after ddmpc_closed_loop_setpoints; "" before the first loop.  Read-only. */
 const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h);
 
