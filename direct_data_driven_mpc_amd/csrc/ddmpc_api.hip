@@ -305,6 +305,7 @@ struct ddmpc_handle {
   DevBuf d_sp, d_uref, d_yref;             // ... staging of host setpoints [u_s | y_s] (ddmpc_step_setpoints) and schedules (ddmpc_closed_loop_setpoints)
   const double *sp_us = nullptr, *sp_ys = nullptr;   // ... the device setpoints of the ddmpc_step_setpoints call in progress
   long long sp_su = 0, sp_sy = 0;          // ... DDMPC_OPT_LARGE_SETPOINTS: their per-instance strides (m, p; a schedule row: n_steps m, n_steps p)
+  int large_setpoint_bounds = 0;           // DDMPC_OPT_LARGE_SETPOINT_BOUNDS: the setpoint calls on a bounded handle on Route::RobustPhases (the bounded phase kernels with the instance's setpoint)
   int large_setpoints = 0;                 // DDMPC_OPT_LARGE_SETPOINTS: the setpoint calls on Route::RobustPhases (a setpoint per instance on the kept factors)
   // input bounds (ddmpc_set_input_bounds) and output bounds (ddmpc_set_output_bounds): per channel, +-infinity = none; the
   // vectors are empty without a finite bound of their kind; `bounded` = some bound of either kind is finite (Route::BoxLaw)
@@ -347,9 +348,10 @@ static bool prep_valid(const ddmpc_handle* h) { return h->prep.valid && h->prep.
 static void forget_prep(ddmpc_handle* h) { h->prep = Prep{}; h->last.large_seed = false; }
 
 // ddmpc_prepare forms S and the three setpoint calls are open: DDMPC_OPT_SETPOINT_LAW, _SETPOINT_BOX_LAW or _SETPOINT_CONVEX_LAW is on
-// -- or, beyond 271 rows, DDMPC_OPT_LARGE_SETPOINTS (the calls run on the kept factors; S next to the law of DDMPC_OPT_LARGE_AFFINE_LAW).
+// -- or, beyond 271 rows, DDMPC_OPT_LARGE_SETPOINTS (the calls run on the kept factors; S next to the law of DDMPC_OPT_LARGE_AFFINE_LAW)
+// or DDMPC_OPT_LARGE_SETPOINT_BOUNDS (the same on a handle that may carry input / output bounds; no S).
 static bool setpoint_on(const ddmpc_handle* h) {
-  return h->setpoint_law != 0 || h->setpoint_box_law != 0 || h->setpoint_convex_law != 0 || h->large_setpoints != 0;
+  return h->setpoint_law != 0 || h->setpoint_box_law != 0 || h->setpoint_convex_law != 0 || h->large_setpoints != 0 || h->large_setpoint_bounds != 0;
 }
 // DDMPC_OPT_SETPOINT_CONVEX_LAW on a slack-only CONVEX handle (Route::Cold): ddmpc_prepare forms the slack box list with its
 // [a | c | lo | hi | 1/d] table and M for the setpoint calls, whether or not DDMPC_OPT_CONVEX_WARM_LAW is on.
@@ -460,11 +462,11 @@ struct LargeBox {
   std::vector<int> pm;          // [position -> component (rv) | component -> position (rv)]
   int nA = 0;                   // first boxed position
   int nbox = 0;                 // components of the table: ascending by position, the slack before the output on a shared row
-  std::vector<int> ip;          // [position (nbox) | output component? (nbox)]
+  std::vector<int> ip;          // [position (nbox) | output component? (nbox) | setpoint channel, -1 for a slack (nbox) | terminal constraint? (1)]
   std::vector<double> bd;       // [a | c | lo | hi | 1/d | shlo | shhi], nbox each, then [u_min (m) | u_max (m) | y_min (p) | y_max (p)]
 };
 static LargeBox build_large_box(const KParams& k, int RP, const std::vector<int>& ti, const std::vector<double>& td,
-                                const double* umin, const double* umax, const double* ymin, const double* ymax) {
+                                const double* umin, const double* umax, const double* ymin, const double* ymax, int tec) {
   LargeBox lb;
   const size_t rv = ((size_t)k.r + 1) & ~(size_t)1;
   lb.pm.assign(2 * rv, 0);
@@ -486,23 +488,25 @@ static LargeBox build_large_box(const KParams& k, int RP, const std::vector<int>
     if (cls == 0) lb.nA = pos;
   }
   if (umin == nullptr && ymin == nullptr) return lb;
-  std::vector<int> cpos, cy;
+  std::vector<int> cpos, cy, cch;
   std::vector<double> cols[R3B_NV];
-  auto add = [&](int i, int isy, double a, double c, double lo, double hi, double d) {
-    cpos.push_back(i); cy.push_back(isy);
+  auto add = [&](int i, int isy, int ch, double a, double c, double lo, double hi, double d) {
+    cpos.push_back(i); cy.push_back(isy); cch.push_back(ch);
     const double v[R3B_NV] = {a, c, lo, hi, 1.0 / d, lo - a, hi - a};
     for (int q = 0; q < R3B_NV; ++q) cols[q].push_back(v[q]);
   };
   for (int i = lb.nA; i < k.r; ++i) {
     const int rho = lb.pm[i], ch = rho % k.nch;
     const double D0 = td[rho], D1 = td[(size_t)RP + rho], tb = td[2 * (size_t)RP + rho];
-    if (slack(rho)) add(i, 0, 0.0, k.sig_scale, -k.bound, k.bound, k.lam * (D0 - D1));        // sigma = -lam beta / lamb_sigma
-    if (input(rho)) add(i, 0, tb, -k.lam * D0, umin[ch], umax[ch], k.lam * D0);               // u = u_s - lam beta / r
-    if (output(rho)) add(i, 1, tb, -k.lam * D1, ymin[ch - k.m], ymax[ch - k.m], k.lam * D1);  // ybar = y_s - lam beta / q
+    if (slack(rho)) add(i, 0, -1, 0.0, k.sig_scale, -k.bound, k.bound, k.lam * (D0 - D1));        // sigma = -lam beta / lamb_sigma
+    if (input(rho)) add(i, 0, ch, tb, -k.lam * D0, umin[ch], umax[ch], k.lam * D0);               // u = u_s - lam beta / r
+    if (output(rho)) add(i, 1, ch, tb, -k.lam * D1, ymin[ch - k.m], ymax[ch - k.m], k.lam * D1);  // ybar = y_s - lam beta / q
   }
   lb.nbox = (int)cpos.size();
   lb.ip = cpos;
   lb.ip.insert(lb.ip.end(), cy.begin(), cy.end());
+  lb.ip.insert(lb.ip.end(), cch.begin(), cch.end());         // (the setpoint instantiations of the bounded kernels: whose setpoint a_s is)
+  lb.ip.push_back(tec ? 1 : 0);
   for (int q = 0; q < R3B_NV; ++q) lb.bd.insert(lb.bd.end(), cols[q].begin(), cols[q].end());
   const double inf = std::numeric_limits<double>::infinity();          // [u_min | u_max | y_min | y_max] for the output stage
   for (int side = 0; side < 2; ++side)
@@ -516,7 +520,7 @@ static LargeBox build_large_box(const KParams& k, int RP, const std::vector<int>
 static int upload_large_box(ddmpc_handle* h) {
   const LargeBox lb = build_large_box(h->kp, 16 * h->kc.NT, h->ti_h, h->td_h, h->umin_h.empty() ? nullptr : h->umin_h.data(),
                                       h->umin_h.empty() ? nullptr : h->umax_h.data(), h->ymin_h.empty() ? nullptr : h->ymin_h.data(),
-                                      h->ymin_h.empty() ? nullptr : h->ymax_h.data());
+                                      h->ymin_h.empty() ? nullptr : h->ymax_h.data(), h->prm.use_terminal_constraint);
   int rc;
   h->nA3 = lb.nA;
   h->nbox3 = lb.nbox;
@@ -1172,9 +1176,12 @@ struct Rr3Plan {
 // Ints of the per-instance record: [k, state, iterations, k, switched positions (cap), active set (rv), start tick, ticks, peak k].
 static long long rr3_kstride(int cap, int rv) { return 4 + cap + rv + 4; }
 
-static Rr3Plan rr3_plan(const ddmpc_handle* h, const KParams& kq, bool filtered = false, bool seeded = false) {
+// setpoints: a call of DDMPC_OPT_LARGE_SETPOINT_BOUNDS, which honours neither the warm start nor the law (the kernels of a handle
+// with both options 0).
+static Rr3Plan rr3_plan(const ddmpc_handle* h, const KParams& kq, bool filtered = false, bool seeded = false, bool setpoints = false) {
   const int r = kq.r, rv = (r + 1) & ~1;
-  const bool wide = h->bounded && (h->large_box_cap > RR3_KMAX || h->large_box_safeguard != 0 || h->large_box_warm != 0);
+  const bool warm = h->large_box_warm != 0 && !setpoints;
+  const bool wide = h->bounded && (h->large_box_cap > RR3_KMAX || h->large_box_safeguard != 0 || warm);
   Rr3Plan P{};
   P.family = wide ? Rr3Family::BoxWide : h->bounded ? Rr3Family::Box : Rr3Family::Plain;
   P.cap = wide ? h->large_box_cap : RR3_KMAX;
@@ -1182,8 +1189,8 @@ static Rr3Plan rr3_plan(const ddmpc_handle* h, const KParams& kq, bool filtered 
   P.nA = (kq.convex || h->bounded) ? h->nA3 : r;
   P.ldw = ((r - (P.nA & ~63)) + 63) & ~63;
   P.filtered = filtered;
-  P.seed_read = wide && h->large_box_warm && seeded;
-  P.seed_kept = wide && h->large_box_warm;
+  P.seed_read = wide && warm && seeded;
+  P.seed_kept = wide && warm;
   P.safeguard = wide && h->large_box_safeguard;
   // W with cap columns, then the k x k system: one (RR3_KMAX + 1)-strided block, or the 64 x 64 tiles of the wide kernel -- and
   // behind them what rr3_box_safeguard_kernel keeps: the unfactored tiles, v, the entering column
@@ -1201,11 +1208,11 @@ static Rr3Box rr3_box(const ddmpc_handle* h) {
 }
 
 // The descriptor of the kept factors and of the solve's workspace (sized here, by the plan).
-static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out) {
+static int rr3_desc(ddmpc_handle* h, const KParams& kq, Rr3* out, bool setpoints = false) {
   const int r = kq.r, n16 = (r + 15) & ~15, rv = (r + 1) & ~1, VL = (r + 63) & ~63;
   const size_t B = (size_t)h->batch;
   const long long m64G = rr2_m64(n16);
-  const Rr3Plan P = rr3_plan(h, kq);
+  const Rr3Plan P = rr3_plan(h, kq, false, false, setpoints);
   int rc;
   if (P.seed_kept && (rc = h->d_large_seed.ensure(B * (size_t)kq.rE))) return rc;
   if ((rc = h->d_rr2v.ensure(B * (size_t)R3_NV * VL * sizeof(double))) || (rc = h->d_rr2zp.ensure(B * (size_t)RR2_NG * VL * sizeof(double))) ||
@@ -1254,16 +1261,17 @@ static int launch_rr3_fallback(ddmpc_handle* h, const KParams& kq, const double*
 // flags of the law step, the solve launches leave every other instance alone -- on a bounded handle (DDMPC_OPT_LARGE_BOX_LAW) by
 // the filtered instantiations, the same launches for the instances the law step flagged.  seeded (DDMPC_OPT_LARGE_BOX_WARM_START
 // = 1 on a bounded handle only): the iteration starts from the set in d_large_seed; with the option 1 every call leaves its set
-// there.
+// there.  sp (the setpoint calls beyond 271 rows): a setpoint per instance -- on a bounded handle the setpoint instantiations of
+// the bounded kernels over the whole batch, from the empty set, no seed read or kept; else rr3_solve_kernel's.
 static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up, const double* yp, double* uo, double* cost,
                             int32_t* status, int32_t* iters, const int* only = nullptr, int* only_si = nullptr, bool seeded = false,
                             const Rr3Setpoint* sp = nullptr) {
   const int r = kq.r;
   const unsigned B = (unsigned)h->batch;
-  const Rr3Plan P = rr3_plan(h, kq, only != nullptr, seeded);
+  const Rr3Plan P = rr3_plan(h, kq, only != nullptr, seeded, sp != nullptr);
   Rr3 S;
   int rc;
-  if ((rc = rr3_desc(h, kq, &S))) return rc;
+  if ((rc = rr3_desc(h, kq, &S, sp != nullptr))) return rc;
   h->last.box_cap = P.cap;
   const int RPs = 16 * h->kc.NT;
   const bool refine = kq.refine != DDMPC_REFINE_OFF && kq.lam != 0.0;
@@ -1278,18 +1286,22 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
   };
   const bool wide = P.family == Rr3Family::BoxWide, box = P.family == Rr3Family::Box, F = P.filtered;
   const int defer = refine ? 1 : 0;
-  if      (wide && P.seed_read && F) rc = launch(rr3_solve_box_wide_kernel<false, Rr3Seed, Rr3Only>, defer, X, P.cap, seed, flt);
+  if (sp && (wide || box) && F) return fail(DDMPC_ERR_UNSUPPORTED, "the bounded solve with setpoints takes no instance filter");
+  if      (wide && sp)               rc = launch(rr3_solve_box_wide_kernel<false, Rr3Setpoint>, defer, X, P.cap, *sp);
+  else if (box && sp)                rc = launch(rr3_solve_box_kernel<false, Rr3Setpoint>, defer, X, *sp);
+  else if (wide && P.seed_read && F) rc = launch(rr3_solve_box_wide_kernel<false, Rr3Seed, Rr3Only>, defer, X, P.cap, seed, flt);
   else if (wide && P.seed_read)      rc = launch(rr3_solve_box_wide_kernel<false, Rr3Seed>, defer, X, P.cap, seed);
   else if (wide && F)                rc = launch(rr3_solve_box_wide_kernel<false, Rr3Only>, defer, X, P.cap, flt);
   else if (wide)                     rc = launch(rr3_solve_box_wide_kernel<false>, defer, X, P.cap);
   else if (box && F)                 rc = launch(rr3_solve_box_kernel<false, Rr3Only>, defer, X, flt);
   else if (box)                      rc = launch(rr3_solve_box_kernel<false>, defer, X);
-  else if (sp)                       rc = launch(rr3_solve_kernel<false, Rr3Setpoint>, defer, only, *sp);   // (Plain only: the option refuses bounds)
+  else if (sp)                       rc = launch(rr3_solve_kernel<false, Rr3Setpoint>, defer, only, *sp);   // (Plain: no finite bounds on the handle)
   else                               rc = launch(rr3_solve_kernel<false>, defer, only);
   if (rc) return rc;
   // the instances that reached max_iter are solved again by the primal method, before the Hankel products and the refinement
   // launch; every other workgroup leaves at once
-  if (P.safeguard && F) rc = launch(rr3_box_safeguard_kernel<Rr3Only>, defer, X, P.cap, flt);
+  if (P.safeguard && sp) rc = launch(rr3_box_safeguard_kernel<Rr3Setpoint>, defer, X, P.cap, *sp);
+  else if (P.safeguard && F) rc = launch(rr3_box_safeguard_kernel<Rr3Only>, defer, X, P.cap, flt);
   else if (P.safeguard) rc = launch(rr3_box_safeguard_kernel<>, defer, X, P.cap);
   if (rc) return rc;
   if (refine) {
@@ -1300,7 +1312,9 @@ static int launch_rr3_solve(ddmpc_handle* h, const KParams& kq, const double* up
     HankelLaunch hk;
     if ((rc = pick_hankel_launch(kq, &hk))) return rc;
     launch_hankel(hk, h->stream, B, H, kq, h->ud, h->yd, (int)R3_X, only_si != nullptr ? 1 : 0);
-    if      (wide && F) rc = launch(rr3_solve_box_wide_kernel<true, Rr3Only>, 0, X, P.cap, flt);
+    if      (wide && sp) rc = launch(rr3_solve_box_wide_kernel<true, Rr3Setpoint>, 0, X, P.cap, *sp);
+    else if (box && sp)  rc = launch(rr3_solve_box_kernel<true, Rr3Setpoint>, 0, X, *sp);
+    else if (wide && F) rc = launch(rr3_solve_box_wide_kernel<true, Rr3Only>, 0, X, P.cap, flt);
     else if (wide)      rc = launch(rr3_solve_box_wide_kernel<true>, 0, X, P.cap);
     else if (box && F)  rc = launch(rr3_solve_box_kernel<true, Rr3Only>, 0, X, flt);
     else if (box)       rc = launch(rr3_solve_box_kernel<true>, 0, X);
@@ -2662,12 +2676,19 @@ int ddmpc_get_gain(ddmpc_handle* h, double* out, int mem) {
 // DDMPC_OPT_SETPOINT_BOX_LAW on a handle with finite bounds (Route::BoxLaw): one launch of ddmpc_setpoint_box_step_kernel, from the
 // empty set (DDMPC_OPT_BOX_WARM_START is not honoured, and the caller drops the seed with the record of the last solve).
 // DDMPC_OPT_LARGE_SETPOINTS (Route::RobustPhases): the solve on the kept factors with the instance's setpoint.
+// DDMPC_OPT_LARGE_SETPOINT_BOUNDS (the same route, with or without finite bounds): that solve, never the law or S.
 static int setpoint_step_on_route(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                                   int32_t* iters) {
   if (h->large_setpoints) {
     begin_solve(h, Route::RobustPhases);
     const Rr3Setpoint sp{h->sp_us, h->sp_ys, h->sp_su, h->sp_sy};
     if (h->large_affine && h->prep.law && h->prep.setpoint) return launch_rr3_setpoint_law_step(h, sp, up, yp, uo, cost, status, iters);
+    return launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters, nullptr, nullptr, false, &sp);
+  }
+  if (h->large_setpoint_bounds) {
+    // (a bounded handle has a table: a ROBUST controller has L >= 2 n, so a finite bound of a channel boxes >= n free steps)
+    begin_solve(h, Route::RobustPhases);
+    const Rr3Setpoint sp{h->sp_us, h->sp_ys, h->sp_su, h->sp_sy};
     return launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters, nullptr, nullptr, false, &sp);
   }
   if (h->setpoint_convex_law) {
@@ -2723,8 +2744,8 @@ int ddmpc_step_setpoints(ddmpc_handle* h, const double* u_past, const double* y_
                          double* u_opt, double* cost, int32_t* status, int32_t* iters, int mem) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
   if (!setpoint_on(h))
-    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box), or beyond 271 rows DDMPC_OPT_LARGE_SETPOINTS = 1");
-  if (h->bounded && !h->setpoint_box_law && !h->setpoint_convex_law)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box), or beyond 271 rows DDMPC_OPT_LARGE_SETPOINTS = 1 (on a handle with input or output bounds there: DDMPC_OPT_LARGE_SETPOINT_BOUNDS = 1)");
+  if (h->bounded && !h->setpoint_box_law && !h->setpoint_convex_law && !h->large_setpoint_bounds)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_step_setpoints on a handle with input or output bounds needs DDMPC_OPT_SETPOINT_BOX_LAW = 1");
   if (!h->have_data) return fail(DDMPC_ERR_NOT_READY, "ddmpc_set_data must be called before ddmpc_step_setpoints");
   if (!u_s || !y_s) return fail(DDMPC_ERR_INVALID, "null argument");
@@ -2752,6 +2773,9 @@ int ddmpc_get_setpoint_gain(ddmpc_handle* h, double* out, int mem) {
   if (!h || !out) return fail(DDMPC_ERR_INVALID, "null argument");
   if (!setpoint_on(h))
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_get_setpoint_gain needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box), or beyond 271 rows DDMPC_OPT_LARGE_SETPOINTS = 1");
+  if (h->large_setpoint_bounds && !h->large_setpoints)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_get_setpoint_gain: DDMPC_OPT_LARGE_SETPOINT_BOUNDS = 1 forms no S (beyond 271 rows there is no S on a "
+                "bounded handle: its setpoint calls solve on the kept factors)");
   if (h->large_setpoints && (!prep_valid(h) || !h->prep.setpoint))
     return fail(DDMPC_ERR_NOT_READY, "ddmpc_get_setpoint_gain beyond 271 rows: S is formed next to the affine law only -- ddmpc_prepare with "
                 "DDMPC_OPT_LARGE_AFFINE_LAW = 1 (and DDMPC_OPT_LARGE_SETPOINTS = 1) must be called before it");
@@ -2986,6 +3010,30 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (h->large_setpoints != value) forget_prep(h);   // (S is part of what ddmpc_prepare keeps, as DDMPC_OPT_SETPOINT_LAW)
       h->large_setpoints = value;
       return DDMPC_OK;
+    case DDMPC_OPT_LARGE_SETPOINT_BOUNDS:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_LARGE_SETPOINT_BOUNDS must be 0 or 1");
+      if (value == 1) {                                 // (the refusals of DDMPC_OPT_LARGE_SETPOINTS but the one of bounds)
+        const char* pre = "DDMPC_OPT_LARGE_SETPOINT_BOUNDS";
+        if (h->prm.controller_type != DDMPC_ROBUST)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: ROBUST controllers only (a NOMINAL one fixes its outputs to the setpoint as hard rows)", pre);
+        if (h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)", pre);
+        if (!h->large)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the option serves 272 .. 1024 rows (up to 271 rows: DDMPC_OPT_SETPOINT_BOX_LAW, "
+                      "DDMPC_OPT_SETPOINT_CONVEX_LAW)", pre, h->kp.r);
+        if (h->kp.r > 1024)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 1024 (the phase kernels)", pre, h->kp.r);
+        if (h->large_pipeline != DDMPC_PIPELINE_PHASES)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: the phase kernels serve it only, and DDMPC_OPT_LARGE_PIPELINE selects the one-workgroup kernel", pre);
+        if (h->stamps_on)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: the phase kernels serve it only, and ddmpc_debug_stamps selects the one-workgroup kernel", pre);
+        if (h->batch > 65535)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: the phase kernels serve it only: batch %lld, the limit is 65535", pre, (long long)h->batch);
+        if (h->prm.n * h->kp.nch > WARM_MAX_NF)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: n*(m+p) = %d, the limit is %d", pre, h->prm.n * h->kp.nch, WARM_MAX_NF);
+      }
+      h->large_setpoint_bounds = value;   // (which calls are accepted: the kept factor does not depend on the setpoint, nothing prepared differs)
+      return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
       if (value == 1 && !h->gram_valu_ok) return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_gram_tiles_kernel stages the whole trajectory in LDS: not at this shape");
@@ -3002,6 +3050,9 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value == DDMPC_PIPELINE_ONE_WORKGROUP && h->large_setpoints)
         return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_PIPELINE_ONE_WORKGROUP is not available with DDMPC_OPT_LARGE_SETPOINTS = 1: the phase kernels "
                     "serve the setpoint calls only");
+      if (value == DDMPC_PIPELINE_ONE_WORKGROUP && h->large_setpoint_bounds)
+        return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_PIPELINE_ONE_WORKGROUP is not available with DDMPC_OPT_LARGE_SETPOINT_BOUNDS = 1: the phase "
+                    "kernels serve the setpoint calls only");
       if (value == DDMPC_PIPELINE_ONE_WORKGROUP && h->large && h->bounded)
         return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_PIPELINE_ONE_WORKGROUP is not available on a handle with input or output bounds: beyond 271 rows "
                     "the phase kernels serve them only");
@@ -3630,8 +3681,8 @@ int ddmpc_closed_loop_setpoints(ddmpc_handle* h, const ddmpc_plant* plant, int32
                                 double* u_sys, double* y_sys, int32_t* status, int mem) {
   if (!h || !u_ref || !y_ref) return fail(DDMPC_ERR_INVALID, "null argument");
   if (!setpoint_on(h))
-    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box), or beyond 271 rows DDMPC_OPT_LARGE_SETPOINTS = 1");
-  if (h->bounded && !h->setpoint_box_law && !h->setpoint_convex_law)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints needs DDMPC_OPT_SETPOINT_LAW = 1 (or DDMPC_OPT_SETPOINT_BOX_LAW = 1, or DDMPC_OPT_SETPOINT_CONVEX_LAW = 1 under the CONVEX slack box), or beyond 271 rows DDMPC_OPT_LARGE_SETPOINTS = 1 (on a handle with input or output bounds there: DDMPC_OPT_LARGE_SETPOINT_BOUNDS = 1)");
+  if (h->bounded && !h->setpoint_box_law && !h->setpoint_convex_law && !h->large_setpoint_bounds)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_closed_loop_setpoints on a handle with input or output bounds needs DDMPC_OPT_SETPOINT_BOX_LAW = 1");
   return closed_loop_impl(h, "ddmpc_closed_loop_setpoints", plant, n_steps, n_mpc_step, x, u_past, y_past, w, u_ref, y_ref, u_sys,
                           y_sys, status, mem);
@@ -3679,7 +3730,7 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
   a.lwup = (double*)h->d_lwup.p; a.lwyp = (double*)h->d_lwyp.p;
   // the fused loops of DDMPC_OPT_SETPOINT_LAW / _BOX_LAW / _CONVEX_LAW hold n_mpc_step * m inputs per solve in LDS (checked before
   // anything is staged); the per-step path of DDMPC_OPT_LARGE_SETPOINTS has no such limit
-  if (u_ref && !h->large_setpoints && (size_t)n_mpc_step * m > (size_t)WARM_MAX_NF)
+  if (u_ref && !h->large_setpoints && !h->large_setpoint_bounds && (size_t)n_mpc_step * m > (size_t)WARM_MAX_NF)
     return fail(DDMPC_ERR_UNSUPPORTED, "%s: n_mpc_step * m = %d, the fused loop holds %d inputs per solve", what, n_mpc_step * m, WARM_MAX_NF);
   if (u_ref) {                       // both setpoint loops: the schedules on the device, the preparation in place
     if (mem == DDMPC_MEM_HOST) {     // the schedules are [batch, n_steps, m] and [batch, n_steps, p]: the sizes of u_sys and y_sys
@@ -3690,8 +3741,8 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
     }
     if (!prep_valid(h) && (rc = ddmpc_prepare(h))) return rc;
   }
-  if (u_ref && h->large_setpoints) {
-    // DDMPC_OPT_LARGE_SETPOINTS: the per-step path on what ddmpc_prepare kept (no fused kernel at this size, so no limit on
+  if (u_ref && (h->large_setpoints || h->large_setpoint_bounds)) {
+    // DDMPC_OPT_LARGE_SETPOINTS / _LARGE_SETPOINT_BOUNDS: the per-step path on what ddmpc_prepare kept (no fused kernel at this size, so no limit on
     // n_mpc_step * m; DDMPC_OPT_CLOSED_LOOP_PATH is not looked at: the cold solve knows the shared setpoints only)
     h->loop_kernel = kLoopKernel[(int)LoopPath::StepPrepared];
     a.uref = u_ref; a.yref = y_ref;
@@ -3739,6 +3790,9 @@ int ddmpc_debug_stamps(ddmpc_handle* h, int enable, uint64_t* out) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
   if (enable && h->large_setpoints)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_debug_stamps is not available with DDMPC_OPT_LARGE_SETPOINTS = 1: stamps select the "
+                "one-workgroup kernel, and the phase kernels serve the setpoint calls only");
+  if (enable && h->large_setpoint_bounds)
+    return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_debug_stamps is not available with DDMPC_OPT_LARGE_SETPOINT_BOUNDS = 1: stamps select the "
                 "one-workgroup kernel, and the phase kernels serve the setpoint calls only");
   if (enable && h->large && h->bounded)
     return fail(DDMPC_ERR_UNSUPPORTED, "ddmpc_debug_stamps is not available on a handle with input or output bounds beyond 271 rows: stamps "
@@ -3828,7 +3882,7 @@ int ddmpc_debug_large_box_order(int32_t m, int32_t p, int32_t n, int32_t L, int3
     ti[rho] = ch < m ? ((is_int || is_term) ? K_UFIX : K_UFREE) : (is_int ? K_WINT : is_term ? K_WTERM : K_WPRED);
     td[rho] = 2.0; td[(size_t)RP + rho] = 1.0;
   }
-  const LargeBox lb = build_large_box(k, RP, ti, td, u_min, u_max, y_min, y_max);
+  const LargeBox lb = build_large_box(k, RP, ti, td, u_min, u_max, y_min, y_max, use_terminal_constraint);
   if (perm_out) for (int i = 0; i < k.r; ++i) perm_out[i] = lb.pm[i];
   if (n_a) *n_a = lb.nA;
   if (nbox) *nbox = lb.nbox;

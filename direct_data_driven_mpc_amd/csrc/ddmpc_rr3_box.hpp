@@ -21,7 +21,7 @@ namespace ddmpc {
 // Behind the seven columns: [u_min (m) | u_max (m) | y_min (p) | y_max (p)] for the output stage (+-infinity where there is none).
 struct Rr3Box {
   int nbox;
-  const int* ip;                                      // [position (nbox) | output component? (nbox)]
+  const int* ip;                                      // [position (nbox) | output component? (nbox) | setpoint channel, -1 for a slack (nbox) | terminal constraint? (1)]
   const double* bd;                                   // [a | c | lo | hi | 1/d | shlo | shhi] (nbox each), then the bounds per channel
 };
 enum : int { R3B_A = 0, R3B_C, R3B_LO, R3B_HI, R3B_INVD, R3B_SHLO, R3B_SHHI, R3B_NV };
@@ -38,6 +38,50 @@ template <class T, class A0, class... A>
 __device__ __forceinline__ T rr3_get_arg(A0 a0, A... a) {
   if constexpr (std::is_same_v<T, A0>) return a0;
   else return rr3_get_arg<T>(a...);
+}
+// DDMPC_OPT_LARGE_SETPOINT_BOUNDS: a setpoint per instance on a bounded handle -- one trailing Rr3Setpoint
+// (ddmpc_rr3.hpp) of the bounded kernels, alone in the pack.  The factor, W, the k x k system and the bounds do not depend on the
+// setpoint; it enters through the four helpers below, which without the argument read the shared tables as the kernels always did:
+//   rr3_target     the target of a component that takes it from a setpoint (tabi[1][rho] < 0), and tb of the output stage
+//   rr3_box_a      the offset a_s of a boxed component: the instance's setpoint of its channel (ip[2 nbox + s]), 0 for a slack
+//   rr3_box_shift  bound - a_s, the one subtraction the host makes for the table's columns (build_large_box): with the handle's
+//                  own setpoints every value is the table's, bit for bit
+// The third block of ip and the flag behind it are read by the instantiations with the argument only.
+template <class... A>
+__device__ __forceinline__ double rr3_target(const KParams& P, int RPs, int rho, long long b, const A&... a) {
+  if constexpr (rr3_has_arg<Rr3Setpoint, A...>) return rr3_setpoint(P, RPs, rho, b, rr3_get_arg<Rr3Setpoint>(a...));
+  else return rr3_setpoint(P, RPs, rho, b);
+}
+template <class... A>
+__device__ __forceinline__ double rr3_box_a(const KParams& P, const Rr3Box& X, int s, long long b, const A&... a) {
+  if constexpr (rr3_has_arg<Rr3Setpoint, A...>) {
+    const int c = X.ip[2 * X.nbox + s];
+    if (c < 0) return 0.0;
+    const Rr3Setpoint sp = rr3_get_arg<Rr3Setpoint>(a...);
+    return (c < P.m) ? sp.us[b * sp.su + c] : sp.ys[b * sp.sy + (c - P.m)];
+  } else {
+    return X.bd[(size_t)R3B_A * X.nbox + s];
+  }
+}
+template <class... A>
+__device__ __forceinline__ double rr3_box_shift(const KParams& P, const Rr3Box& X, int s, bool up, long long b, const A&... a) {
+  if constexpr (rr3_has_arg<Rr3Setpoint, A...>) return X.bd[(size_t)(up ? R3B_HI : R3B_LO) * X.nbox + s] - rr3_box_a(P, X, s, b, a...);
+  else return X.bd[(size_t)(up ? R3B_SHHI : R3B_SHLO) * X.nbox + s];
+}
+// The status of a setpoint the solve launch refuses, or 0 (the same value in every thread: the rule of setpoint_box_refusal,
+// ddmpc_setpoint_box_law.hpp): 4 for a non-finite one; DDMPC_STATUS_INFEASIBLE for one outside the bounds of its channel when the
+// terminal constraint fixes the last n steps to it.
+__device__ __forceinline__ int rr3_setpoint_refusal(const KParams& P, const Rr3Box& X, long long b, const Rr3Setpoint& sp) {
+  const double* bnd = X.bd + (size_t)R3B_NV * X.nbox;                       // [u_min | u_max | y_min | y_max]
+  int bad = 0, out = 0;
+  for (int c = 0; c < P.nch; ++c) {
+    const bool u = c < P.m;
+    const double v = u ? sp.us[b * sp.su + c] : sp.ys[b * sp.sy + (c - P.m)];
+    const double lo = u ? bnd[c] : bnd[2 * P.m + (c - P.m)], hi = u ? bnd[P.m + c] : bnd[2 * P.m + P.p + (c - P.m)];
+    bad |= !(fabs(v) < 1e300);
+    out |= (v < lo) || (v > hi);
+  }
+  return bad ? 4 : ((X.ip[3 * X.nbox] != 0 && out) ? 2 : 0);
 }
 // What the bounded kernels keep in LDS behind Rr3Lds::total (doubles): the table indices of the active components (RR3_KMAX
 // ints) and their shifts (RR3_KMAX doubles).  Nothing else is indexed by component in LDS.
@@ -62,10 +106,13 @@ __device__ __forceinline__ void rr3_box_row(const KParams& P, int RPs, const Rr3
 // input is its bound exactly and an active output gives ybar = bound, sigma = z - bound (= -lam beta / lamb_sigma, or
 // +- c eps_max with the slack held too); the cost terms are r (u - u_s)^2 and q (ybar - y_s)^2 + lamb_sigma sigma^2 in every
 // state.  An instance that failed (st != 0) reports NaN inputs and cost: no fall-back kernel knows the bounds.
+// A...: the trailing pack of the calling kernel (with an Rr3Setpoint: tb is the instance's, and a refused setpoint outside its
+// bounds -- st 2 -- reports 0 iterations).
+template <class... A>
 __device__ __forceinline__ void rr3_box_outputs(const KParams& P, int RPs, const Rr3Box& X, long long b, const int* perm, const double* tv,
                                                 const double* bv, const int* act, int st, int iter, double* red, double* __restrict__ u_opt,
                                                 double* __restrict__ cost, int* __restrict__ status, int* __restrict__ iters,
-                                                double* __restrict__ beta_ws, signed char* __restrict__ act_ws) {
+                                                double* __restrict__ beta_ws, signed char* __restrict__ act_ws, const A&... a) {
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));     // (opaque per call, see rr3_trsv_fwd)
   const int nthr = blockDim.x, r = P.r;
@@ -83,7 +130,7 @@ __device__ __forceinline__ void rr3_box_outputs(const KParams& P, int RPs, const
     rr3_box_row(P, RPs, X, rho, code, tv[i], &D, &t);
     const double z = t - P.lam * D * bb;
     const double wq = P.tabd[3 * RPs + rho];
-    const double tb = P.tabd[2 * RPs + rho];
+    const double tb = rr3_target(P, RPs, rho, b, a...);
     const int kind = P.tabi[0 * RPs + rho];
     if (!(fabs(bb) < 1e300)) bad = 1.0;
     double contrib = P.lam * bb * z;
@@ -107,6 +154,7 @@ __device__ __forceinline__ void rr3_box_outputs(const KParams& P, int RPs, const
     cost[b] = (st == 0) ? tot : nanv;
     status[b] = st;
     if (iters) iters[b] = iter > 0 ? iter : 1;
+    if constexpr (rr3_has_arg<Rr3Setpoint, A...>) { if (iters && st == 2) iters[b] = 0; }
   }
 }
 
@@ -117,7 +165,8 @@ __device__ __forceinline__ void rr3_box_outputs(const KParams& P, int RPs, const
 // shifts of the active components, ascending (two components of one row give two equal columns of W); the k x k system is
 // diag(1 / d_s) - W'W with each component's own d_s, its right-hand side takes the component's own shift.  More than RR3_KMAX
 // active components in an iteration, or a non-positive pivot of the k x k system: status 4 at that iteration.
-// Only...: empty (the kernel as it is launched without a filter) or one Rr3Only.
+// Only...: empty (the kernel as it is launched without a filter), one Rr3Only, or one Rr3Setpoint (both launches; the solve
+// launch refuses a setpoint by rr3_setpoint_refusal before anything is iterated, and its record keeps the others off the instance).
 // ---------------------------------------------------------------------------------------------------------------
 template <bool REFINE_PASS, class... Only>
 __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_kernel(Rr3 S, KParams P, int RPs, const double* __restrict__ u_past,
@@ -125,10 +174,11 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_kernel(Rr3 S, KParams
                                                                double* __restrict__ cost, int* __restrict__ status, int* __restrict__ iters,
                                                                double* __restrict__ beta_ws, signed char* __restrict__ act_ws, int defer_outputs,
                                                                Rr3Box X, Only... only) {
-  static_assert(sizeof...(Only) == 0 || (sizeof...(Only) == 1 && rr3_has_arg<Rr3Only, Only...>), "one filter at most");
+  static_assert(sizeof...(Only) == 0 || (sizeof...(Only) == 1 && (rr3_has_arg<Rr3Only, Only...> || rr3_has_arg<Rr3Setpoint, Only...>)),
+                "one filter or one setpoint at most");
   extern __shared__ __attribute__((aligned(16))) double r3_lds[];
   const long long b = blockIdx.x;
-  if constexpr (sizeof...(Only) != 0) {
+  if constexpr (rr3_has_arg<Rr3Only, Only...>) {
     if (rr3_get_arg<Rr3Only>(only...).only[b] == 0) return;                 // (workgroup-uniform)
   }
   const int tid = threadIdx.x, nthr = blockDim.x;
@@ -196,13 +246,17 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_kernel(Rr3 S, KParams
       if (i < r) {
         const int rho = perm[i];
         const int pidx = P.tabi[1 * RPs + rho];
-        t = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : P.tabd[2 * RPs + rho];
+        t = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : rr3_target(P, RPs, rho, b, only...);
         nbad += S.skip[b * S.s_stride + i] ? 1.0 : 0.0;
       }
       tv[i] = t; act[i] = 0; y2[i] = 0.0; bv[i] = 0.0;
     }
     if (tid == 0) flagw[3] = 0;
     if (block_sum(nbad, tmp) != 0.0) st = 4;                 // (uniform) a pivot of K0 failed: not positive definite numerically
+    if constexpr (rr3_has_arg<Rr3Setpoint, Only...>) {       // (uniform) a refused setpoint: nothing is iterated
+      const int refuse = rr3_setpoint_refusal(P, X, b, rr3_get_arg<Rr3Setpoint>(only...));
+      if (refuse != 0) st = refuse;
+    }
     __syncthreads();
     if (st == 0) {
       rr3_trsv_fwd<1>(G, m64, r, live, 0, [&](int, int i) { return tv[i]; }, [&](int) { return yv; }, tmp);
@@ -226,7 +280,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_kernel(Rr3 S, KParams
             const int i = X.ip[s], isy = X.ip[X.nbox + s];
             const int code = __hip_atomic_load(&act[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             const int cur = isy ? rr3_say(code) : rr3_sa(code);
-            const double hat = fma(X.bd[(size_t)R3B_C * X.nbox + s], bv[i], X.bd[(size_t)R3B_A * X.nbox + s]);
+            const double hat = fma(X.bd[(size_t)R3B_C * X.nbox + s], bv[i], rr3_box_a(P, X, s, b, only...));
             const int upv = hat > X.bd[(size_t)R3B_HI * X.nbox + s], dnv = hat < X.bd[(size_t)R3B_LO * X.nbox + s];
             const int ns = cur > 0 ? upv : (cur < 0 ? -dnv : upv - dnv);
             if (ns != cur) { atomicAdd(&act[i], (ns - cur) * (isy ? 4 : 1)); flagw[0] = 1; }
@@ -245,7 +299,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_kernel(Rr3 S, KParams
               const int slot = base + __popcll(mk & ((1ull << (ot & 63)) - 1ull));
               if (a != 0 && slot < RR3_KMAX) {
                 list[slot] = i; lcomp[slot] = s;
-                lsh[slot] = X.bd[(size_t)(a > 0 ? R3B_SHHI : R3B_SHLO) * X.nbox + s];
+                lsh[slot] = rr3_box_shift(P, X, s, a > 0, b, only...);
               }
               base += __popcll(mk);
             }
@@ -303,7 +357,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_kernel(Rr3 S, KParams
     }
     if (!defer_outputs || st != 0) {
       __syncthreads();
-      rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, st, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws);
+      rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, st, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws, only...);
     }
   } else {
     // ---- one pass of iterative refinement on the system of the final active set, then the outputs.
@@ -341,7 +395,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_kernel(Rr3 S, KParams
     rr3_trsv_bwd(G, m64, r, live, nb, 0, yv, y2, red, tmp);                                                   // delta
     for (int i = tid; i < r; i += nthr) bv[i] += y2[i];
     __syncthreads();
-    rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, 0, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws);
+    rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, 0, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws, only...);
   }
 }
 

@@ -31,7 +31,8 @@ __host__ __device__ constexpr long long rr3s_extra(int cap, int nbox, int ldw) {
   return rr3w_tiles(cap) * 4096 + ((nbox + 15) & ~15) + 16ll * ldw;
 }
 
-// Only...: empty (the kernel as it is launched without a filter) or one Rr3Only (DDMPC_OPT_LARGE_BOX_LAW).
+// Only...: empty (the kernel as it is launched without a filter), one Rr3Only (DDMPC_OPT_LARGE_BOX_LAW), or one Rr3Setpoint
+// (DDMPC_OPT_LARGE_SETPOINT_BOUNDS: the staging, the offsets and the shifts of the instance's setpoint, as in the solve launch).
 template <class... Only>
 __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KParams P, int RPs, const double* __restrict__ u_past,
                                                                    const double* __restrict__ y_past, double* __restrict__ u_opt,
@@ -39,10 +40,11 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KPa
                                                                    int* __restrict__ iters, double* __restrict__ beta_ws,
                                                                    signed char* __restrict__ act_ws, int defer_outputs, Rr3Box X, int cap,
                                                                    Only... only) {
-  static_assert(sizeof...(Only) == 0 || (sizeof...(Only) == 1 && rr3_has_arg<Rr3Only, Only...>), "one filter at most");
+  static_assert(sizeof...(Only) == 0 || (sizeof...(Only) == 1 && (rr3_has_arg<Rr3Only, Only...> || rr3_has_arg<Rr3Setpoint, Only...>)),
+                "one filter or one setpoint at most");
   extern __shared__ __attribute__((aligned(16))) double r3_lds[];
   const long long b = blockIdx.x;
-  if constexpr (sizeof...(Only) != 0) {
+  if constexpr (rr3_has_arg<Rr3Only, Only...>) {
     if (rr3_get_arg<Rr3Only>(only...).only[b] == 0) return;                 // (workgroup-uniform)
   }
   int* kq = S.kq + b * S.kstride;
@@ -202,7 +204,11 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KPa
     if (i < r) {
       const int rho = perm[i];
       const int pidx = P.tabi[1 * RPs + rho];
-      t = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : P.tabd[2 * RPs + rho];
+      // TWO COPIES OF ONE STATEMENT, to be edited together: they differ in the last operand only.  The instantiations without a
+      // setpoint keep the statement they had (through rr3_target their staging loop was compiled into other code, compared in
+      // the assembly); the solve kernels stage the same t through rr3_target alone.
+      if constexpr (rr3_has_arg<Rr3Setpoint, Only...>) t = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : rr3_target(P, RPs, rho, b, only...);
+      else t = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : P.tabd[2 * RPs + rho];
     }
     tv[i] = t; act[i] = 0; y2[i] = 0.0; bv[i] = 0.0;
   }
@@ -217,7 +223,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KPa
     asm volatile("" : "+v"(ot));
     for (int s = ot; s < nbox; s += nthr) {
       const int i = X.ip[s], isy = X.ip[nbox + s];
-      const double hat = fma(X.bd[(size_t)R3B_C * nbox + s], bv[i], X.bd[(size_t)R3B_A * nbox + s]);
+      const double hat = fma(X.bd[(size_t)R3B_C * nbox + s], bv[i], rr3_box_a(P, X, s, b, only...));
       const double lo = X.bd[(size_t)R3B_LO * nbox + s], hi = X.bd[(size_t)R3B_HI * nbox + s];
       const int side = (hat > hi) - (hat < lo);
       vg[s] = side > 0 ? hi : (side < 0 ? lo : hat);
@@ -234,7 +240,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KPa
         const int slot = base + __popcll(mk & ((1ull << (ot & 63)) - 1ull));
         if (a != 0 && slot < cap) {
           list[slot] = i; lcomp[slot] = s;
-          lsh[slot] = X.bd[(size_t)(a > 0 ? R3B_SHHI : R3B_SHLO) * nbox + s];
+          lsh[slot] = rr3_box_shift(P, X, s, a > 0, b, only...);
         }
         base += __popcll(mk);
       }
@@ -299,7 +305,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KPa
       const int i = X.ip[s], isy = X.ip[nbox + s];
       const int cur = isy ? rr3_say(act[i]) : rr3_sa(act[i]);
       if (cur != 0) continue;
-      const double hat = fma(X.bd[(size_t)R3B_C * nbox + s], bv[i], X.bd[(size_t)R3B_A * nbox + s]);
+      const double hat = fma(X.bd[(size_t)R3B_C * nbox + s], bv[i], rr3_box_a(P, X, s, b, only...));
       const double lo = X.bd[(size_t)R3B_LO * nbox + s], hi = X.bd[(size_t)R3B_HI * nbox + s];
       if (hat > hi || hat < lo) {
         const double v = vg[s];
@@ -312,14 +318,14 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KPa
     if (sb != NONE) {
       // step 3: move to the blocking point; component sb joins at its bound, as column k of W
       const int ib = X.ip[sb], yb = X.ip[nbox + sb];
-      const double hb = fma(X.bd[(size_t)R3B_C * nbox + sb], bv[ib], X.bd[(size_t)R3B_A * nbox + sb]);
+      const double hb = fma(X.bd[(size_t)R3B_C * nbox + sb], bv[ib], rr3_box_a(P, X, sb, b, only...));
       const int sd = hb > X.bd[(size_t)R3B_HI * nbox + sb] ? 1 : -1;
       if (k >= cap) { k = cap + 1; continue; }                // (uniform) the next solve cannot be made
       for (int s = ot; s < nbox; s += nthr) {
         const int i = X.ip[s], isy = X.ip[nbox + s];
         const int cur = isy ? rr3_say(act[i]) : rr3_sa(act[i]);
         if (cur != 0) continue;
-        const double hat = fma(X.bd[(size_t)R3B_C * nbox + s], bv[i], X.bd[(size_t)R3B_A * nbox + s]);
+        const double hat = fma(X.bd[(size_t)R3B_C * nbox + s], bv[i], rr3_box_a(P, X, s, b, only...));
         const double v = vg[s];
         vg[s] = (s == sb) ? X.bd[(size_t)(sd > 0 ? R3B_HI : R3B_LO) * nbox + s] : v + alpha * (hat - v);
       }
@@ -327,7 +333,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KPa
       if (ot == 0) {
         act[ib] += sd * (yb ? 4 : 1);
         list[k] = ib; lcomp[k] = sb;
-        lsh[k] = X.bd[(size_t)(sd > 0 ? R3B_SHHI : R3B_SHLO) * nbox + sb];
+        lsh[k] = rr3_box_shift(P, X, sb, sd > 0, b, only...);
       }
       __syncthreads();
       rr3w_w_forward(G, m64, r, live, b0, n0, list + k, 1, Wn, 16, big);    // one column substitution on L_TT
@@ -347,14 +353,14 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KPa
     for (int s = ot; s < nbox; s += nthr) {
       const int i = X.ip[s], isy = X.ip[nbox + s];
       const int cur = isy ? rr3_say(act[i]) : rr3_sa(act[i]);
-      if (cur == 0) vg[s] = fma(X.bd[(size_t)R3B_C * nbox + s], bv[i], X.bd[(size_t)R3B_A * nbox + s]);
+      if (cur == 0) vg[s] = fma(X.bd[(size_t)R3B_C * nbox + s], bv[i], rr3_box_a(P, X, s, b, only...));
     }
     key = inf; ks = NONE;
     if (ot < k) {
       const int s = lcomp[ot], i = list[ot];
       const int cur = X.ip[nbox + s] ? rr3_say(act[i]) : rr3_sa(act[i]);
       const double c = X.bd[(size_t)R3B_C * nbox + s];
-      const double hat = fma(c, bv[i], X.bd[(size_t)R3B_A * nbox + s]);
+      const double hat = fma(c, bv[i], rr3_box_a(P, X, s, b, only...));
       const double bd = X.bd[(size_t)(cur > 0 ? R3B_HI : R3B_LO) * nbox + s];
       key = -((double)cur * (bd - hat) / fabs(c));
       ks = s;
@@ -403,7 +409,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_box_safeguard_kernel(Rr3 S, KPa
   }
   if (!defer_outputs || st != 0) {
     __syncthreads();
-    rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, st, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws);
+    rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, st, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws, only...);
   }
 }
 

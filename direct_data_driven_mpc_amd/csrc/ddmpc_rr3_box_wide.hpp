@@ -249,6 +249,7 @@ struct Rr3Seed {
 // The record of a failed instance holds the count of its LAST run (kq[2] >= max_iter: that run ended at its own cap, what
 // rr3_box_safeguard_kernel asks), that of a finished one the whole count.
 // Behind the seed, or alone: one Rr3Only (DDMPC_OPT_LARGE_BOX_LAW, the instance filter; both launches).
+// Or, alone in the pack: one Rr3Setpoint (DDMPC_OPT_LARGE_SETPOINT_BOUNDS, both launches; as in rr3_solve_box_kernel).
 // ---------------------------------------------------------------------------------------------------------------
 template <bool REFINE_PASS, class... Seed>
 __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KParams P, int RPs, const double* __restrict__ u_past,
@@ -257,9 +258,10 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
                                                                     int* __restrict__ iters, double* __restrict__ beta_ws,
                                                                     signed char* __restrict__ act_ws, int defer_outputs, Rr3Box X, int cap,
                                                                     Seed... seed) {
-  constexpr bool SEEDED = rr3_has_arg<Rr3Seed, Seed...>, ONLY = rr3_has_arg<Rr3Only, Seed...>;
-  static_assert(sizeof...(Seed) == (SEEDED ? 1 : 0) + (ONLY ? 1 : 0) && !(REFINE_PASS && SEEDED),
-                "one seed (for the solve launch only) and one filter at most");
+  constexpr bool SEEDED = rr3_has_arg<Rr3Seed, Seed...>, ONLY = rr3_has_arg<Rr3Only, Seed...>, SETPOINTS = rr3_has_arg<Rr3Setpoint, Seed...>;
+  static_assert(sizeof...(Seed) == (SEEDED ? 1 : 0) + (ONLY ? 1 : 0) + (SETPOINTS ? 1 : 0) && !(REFINE_PASS && SEEDED) &&
+                    !(SETPOINTS && (SEEDED || ONLY)),
+                "one seed (for the solve launch only) and one filter at most, or one setpoint alone");
   extern __shared__ __attribute__((aligned(16))) double r3_lds[];
   const long long b = blockIdx.x;
   if constexpr (ONLY) {
@@ -395,7 +397,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
       if (i < r) {
         const int rho = perm[i];
         const int pidx = P.tabi[1 * RPs + rho];
-        t = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : P.tabd[2 * RPs + rho];
+        t = (pidx >= 0) ? ((pidx < P.npu) ? up[pidx] : yp[pidx - P.npu]) : rr3_target(P, RPs, rho, b, seed...);
         nbad += S.skip[b * S.s_stride + i] ? 1.0 : 0.0;
       }
       tv[i] = t; act[i] = 0; y2[i] = 0.0; bv[i] = 0.0;
@@ -403,6 +405,10 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
     if (tid == 0) flagw[3] = 0;
     if constexpr (SEEDED) { if (tid == 0) flagw[5] = 0; }      // [5] the seed holds an active component
     if (block_sum(nbad, tmp) != 0.0) st = 4;                 // (uniform) a pivot of K0 failed: not positive definite numerically
+    if constexpr (SETPOINTS) {                               // (uniform) a refused setpoint: nothing is iterated
+      const int refuse = rr3_setpoint_refusal(P, X, b, rr3_get_arg<Rr3Setpoint>(seed...));
+      if (refuse != 0) st = refuse;
+    }
     __syncthreads();
     if (st == 0) {
       rr3_trsv_fwd<1>(G, m64, r, live, 0, [&](int, int i) { return tv[i]; }, [&](int) { return yv; }, tmp);
@@ -433,7 +439,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
             const int i = X.ip[s], isy = X.ip[X.nbox + s];
             const int code = __hip_atomic_load(&act[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             const int cur = isy ? rr3_say(code) : rr3_sa(code);
-            const double hat = fma(X.bd[(size_t)R3B_C * X.nbox + s], bv[i], X.bd[(size_t)R3B_A * X.nbox + s]);
+            const double hat = fma(X.bd[(size_t)R3B_C * X.nbox + s], bv[i], rr3_box_a(P, X, s, b, seed...));
             const int upv = hat > X.bd[(size_t)R3B_HI * X.nbox + s], dnv = hat < X.bd[(size_t)R3B_LO * X.nbox + s];
             const int ns = cur > 0 ? upv : (cur < 0 ? -dnv : upv - dnv);
             if (ns != cur) { atomicAdd(&act[i], (ns - cur) * (isy ? 4 : 1)); flagw[0] = 1; }
@@ -487,7 +493,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
               const int slot = base + __popcll(mk & ((1ull << (ot & 63)) - 1ull));
               if (a != 0 && slot < cap) {
                 list[slot] = i; lcomp[slot] = s;
-                lsh[slot] = X.bd[(size_t)(a > 0 ? R3B_SHHI : R3B_SHLO) * X.nbox + s];
+                lsh[slot] = rr3_box_shift(P, X, s, a > 0, b, seed...);
               }
               base += __popcll(mk);
             }
@@ -556,7 +562,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
     }
     if (!defer_outputs || st != 0) {
       __syncthreads();
-      rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, st, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws);
+      rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, st, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws, seed...);
     }
   } else {
     // ---- one pass of iterative refinement on the system of the final active set (as rr3_solve_box_kernel), then the outputs
@@ -590,7 +596,7 @@ __global__ __launch_bounds__(RR2_TS, 4) void rr3_solve_box_wide_kernel(Rr3 S, KP
     rr3_trsv_bwd(G, m64, r, live, nb, 0, yv, y2, red, tmp);                                                   // delta
     for (int i = tid; i < r; i += nthr) bv[i] += y2[i];
     __syncthreads();
-    rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, 0, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws);
+    rr3_box_outputs(P, RPs, X, b, perm, tv, bv, act, 0, iter, tmp, u_opt, cost, status, iters, beta_ws, act_ws, seed...);
   }
 }
 

@@ -346,6 +346,24 @@ class BatchedDDMPC:
         `get_solution` is not available after them."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_SETPOINTS, 1 if on else 0))
 
+    def set_large_setpoint_bounds(self, on: bool) -> None:
+        """ROBUST controllers on the phase kernels (272 .. 1024 rows) with input and / or output bounds
+        (`set_large_bounds(True)` admits them; either order), slack NONE or the CONVEX slack box, scalar / diagonal weights:
+        True = `step_setpoints` and `closed_loop_setpoints` are open (DDMPC_OPT_LARGE_SETPOINT_BOUNDS).  Neither the kept
+        factor nor the bounds depend on the setpoint, so the bounded solve of `step` takes the instance's own setpoint as
+        target, as the offset of every boxed input / output component and in the output stage; at the handle's own setpoints
+        it is bit-equal to `step`.  The capacity and the safeguard apply as to `step`; the warm start and the box law are
+        not honoured (empty set, whole batch on the kept factor, the seed is dropped).  Per instance: a non-finite setpoint
+        is solver_error, a setpoint outside its channel's bounds under the terminal constraint is infeasible (NaN outputs,
+        iters 0), an instance beyond the capacity or with a failed pivot is solver_error.  Without finite bounds the calls
+        run what `set_large_setpoints` runs on the kept factors.  `setpoint_gain` raises ERR_UNSUPPORTED (no S at this size
+        on a bounded handle); `get_solution` is not available after the calls.  `solve`, `step`, `closed_loop`, `gain` and
+        `get_solution` stay bit-equal to False (default); changing the value forgets nothing `prepare` kept.  Raises
+        ERR_UNSUPPORTED on NOMINAL controllers, dense weights, up to 271 rows (use `set_setpoint_box_law` /
+        `set_setpoint_convex_law`), more than 1024 rows, the one-workgroup pipeline, debug stamps, batch > 65535 and
+        n(m+p) > 256.  `set_large_setpoints(True)` keeps refusing bounds."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_SETPOINT_BOUNDS, 1 if on else 0))
+
     def step_setpoints(self, u_past, y_past, u_s, y_s, u_opt=None, cost=None, status=None, iters=None):
         """Warm control step with one setpoint per instance (`ddmpc_step_setpoints`): u_s [batch,m], y_s [batch,p], in the
         memory space of the windows; same outputs and array / tensor handling as `solve`.  The handle's own setpoints are not
@@ -355,7 +373,8 @@ class BatchedDDMPC:
         as `step` does (`iters` counts its solves; infeasible with NaN outputs for a setpoint outside the bounds under the
         terminal constraint).  Beyond 271 rows: `set_large_setpoints(True)` -- the step of `step` on the kept factor with the
         instance's setpoint, or with `set_large_affine_law(True)` one launch on the law and S plus the kept-factor solve for
-        the instances it leaves."""
+        the instances it leaves; on a handle with bounds there, `set_large_setpoint_bounds(True)` -- the bounded solve of
+        `step` with the instance's setpoint."""
         return self._solve(u_past, y_past, u_opt, cost, status, iters, True, (u_s, y_s))
 
     def setpoint_gain(self) -> np.ndarray:
@@ -373,7 +392,8 @@ class BatchedDDMPC:
         `set_setpoint_box_law(True)`, which a handle with input / output bounds requires ('ddmpc_closed_loop_setpoint_box_kernel':
         an instance stops at a solve that is not optimal and at a refused setpoint).  Beyond 271 rows
         (`set_large_setpoints(True)`) the loop runs per step ('ddmpc_plant_kernel'), the solve at step t reading row t of the
-        schedules in place; n_mpc_step * m has no limit there."""
+        schedules in place; n_mpc_step * m has no limit there.  The same holds on a bounded handle beyond 271 rows with
+        `set_large_setpoint_bounds(True)`."""
         return self.closed_loop(A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step, _ref=(u_ref, y_ref))
 
     def closed_loop(self, A, B, Cm, D, x0, u_past, y_past, w, n_mpc_step: int = 1, _ref=None):

@@ -65,7 +65,8 @@ def parse_args():
                          "output the plant settles at under it (robust scheme, slack None; closed_loop_setpoints).  Together with "
                          "--u_min/--u_max or --y_min/--y_max every instance tracks its setpoint inside the box "
                          "(set_setpoint_box_law; --box_safeguard applies).  With slack Convex, bounded or not: "
-                         "set_setpoint_convex_law")
+                         "set_setpoint_convex_law.  With bounds and a long horizon, beyond 271 rows: "
+                         "set_large_setpoint_bounds (--large_box_capacity / --large_box_safeguard apply)")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     return ap.parse_args()
 
@@ -129,7 +130,9 @@ def main():
     us_b = ys_b = None                           # --setpoint_spread: the setpoints of every instance, [B, m] and [B, p]
     bounded = a.u_min is not None or a.y_min is not None
     if a.setpoint_spread is not None:
-        if cfg["slack"] == "convex":             # under the CONVEX slack box, bounded or not: DDMPC_OPT_SETPOINT_CONVEX_LAW
+        if bounded and (m + p) * (Lh + n) > 271: # bounds beyond 271 rows, slack NONE or CONVEX: DDMPC_OPT_LARGE_SETPOINT_BOUNDS
+            eng.set_large_setpoint_bounds(True)
+        elif cfg["slack"] == "convex":           # under the CONVEX slack box, bounded or not: DDMPC_OPT_SETPOINT_CONVEX_LAW
             eng.set_setpoint_convex_law(True)
         elif bounded:                            # setpoints per instance inside the box: DDMPC_OPT_SETPOINT_BOX_LAW
             eng.set_setpoint_box_law(True)
@@ -162,7 +165,13 @@ def main():
                           eps_max=cfg["eps_max"], lamb_alpha=cfg["lamb_alpha"], lamb_sigma=cfg["lamb_sigma"],
                           c=cfg["c"], use_terminal_constraint=cfg["tec"], device=a.device) as one:
             if us_b is not None and (bounded or cfg["slack"] == "convex"):
-                if cfg["slack"] == "convex":
+                if bounded and (m + p) * (Lh + n) > 271:
+                    one.set_large_bounds(True)
+                    one.set_large_setpoint_bounds(True)
+                    if a.large_box_capacity is not None:
+                        one.set_large_box_capacity(a.large_box_capacity)
+                    one.set_large_box_safeguard(a.large_box_safeguard)
+                elif cfg["slack"] == "convex":
                     one.set_setpoint_convex_law(True)
                 else:
                     one.set_setpoint_box_law(True)

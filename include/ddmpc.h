@@ -402,6 +402,41 @@ extern "C" {
                                          is not launched here); with the terminal constraint a setpoint that is no equilibrium of the
                                          plant binds the terminal slacks, n p of them.  Options 18 - 20 keep their refusals beyond
                                          271 rows */
+#define DDMPC_OPT_LARGE_SETPOINT_BOUNDS 22 /* Per-instance, per-step setpoints on handles with input / output bounds beyond 271
+                                         rows: 1 = ddmpc_step_setpoints and ddmpc_closed_loop_setpoints are open on a ROBUST handle
+                                         on the phase kernels (272 .. 1024 rows, scalar / diagonal weights, slack NONE or the CONVEX
+                                         slack box) that may carry input bounds, output bounds or both (DDMPC_OPT_LARGE_BOUNDS = 1
+                                         admits them, as ever; the option and the bounds are accepted in either order).  The kept
+                                         factor and the bounds do not depend on the setpoint: the calls run the bounded solve of
+                                         ddmpc_step on the kept factor over the whole batch with the instance's own setpoint as the
+                                         target of its setpoint rows, as the offset a_s of every boxed input / output component (the
+                                         shifts are bound - a_s, formed on the device) and in the output stage -- the setpoint
+                                         instantiations of "rr3_solve_box_kernel" / "rr3_solve_box_wide_kernel" /
+                                         "rr3_box_safeguard_kernel".  With every instance given the handle's own setpoints the result
+                                         is bit-equal to ddmpc_step on a handle without warm start or box law.  On a handle without
+                                         finite bounds the calls run what DDMPC_OPT_LARGE_SETPOINTS runs on the kept factors (no law,
+                                         no S).  DDMPC_OPT_LARGE_BOX_CAPACITY and DDMPC_OPT_LARGE_BOX_SAFEGUARD apply as to
+                                         ddmpc_step; DDMPC_OPT_LARGE_BOX_WARM_START and DDMPC_OPT_LARGE_BOX_LAW may be on but are not
+                                         honoured: the calls start from the empty set, read and keep no seed, and drop the seed with
+                                         the record of the last solve.  Per instance (neighbours untouched): a non-finite setpoint is
+                                         DDMPC_STATUS_SOLVER_ERROR with NaN outputs; with the terminal constraint a setpoint outside
+                                         the bounds of its channel is DDMPC_STATUS_INFEASIBLE with NaN outputs and iters 0; an instance
+                                         beyond the capacity or with a failed pivot is DDMPC_STATUS_SOLVER_ERROR with NaN outputs, as
+                                         ddmpc_step reports it.  ddmpc_closed_loop_setpoints runs the per-step path
+                                         ("ddmpc_plant_kernel").  ddmpc_get_solution after the two calls is DDMPC_ERR_NOT_READY;
+                                         ddmpc_get_setpoint_gain is DDMPC_ERR_UNSUPPORTED (no S at this size on a bounded handle)
+                                         unless DDMPC_OPT_LARGE_SETPOINTS provides it.  ddmpc_solve, ddmpc_step, ddmpc_closed_loop,
+                                         ddmpc_get_gain and ddmpc_get_solution launch what they launch with 0 and return bit-equal
+                                         results.  0 (default; accepted on every handle).  Values other than 0 / 1:
+                                         DDMPC_ERR_INVALID.  Changing the value forgets nothing ddmpc_prepare kept.  Setting 1 is
+                                         DDMPC_ERR_UNSUPPORTED, with a message that names the reason, on NOMINAL controllers, with
+                                         DDMPC_WEIGHT_DENSE, up to 271 rows (options 19 / 20 serve those), beyond 1024 rows, on a
+                                         handle that is not on the phase kernels (DDMPC_PIPELINE_ONE_WORKGROUP, ddmpc_debug_stamps,
+                                         batch > 65535) and with n(m+p) > 256; DDMPC_PIPELINE_ONE_WORKGROUP and ddmpc_debug_stamps are
+                                         refused on a handle with the option on.  DDMPC_OPT_LARGE_SETPOINTS keeps every refusal it
+                                         has, bounds included, whether or not this option is on.  Not covered: NOMINAL controllers,
+                                         dense weights, more than 1024 rows, per-instance bounds, a setpoint form of the large box
+                                         law, the active-set warm start for these calls, a fused loop kernel */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
