@@ -53,6 +53,7 @@ EXPORTS = (
     "ddmpc_pe_guard", "ddmpc_solve_from_host", "ddmpc_debug_workspace", "ddmpc_debug_poison_allocations",
     "ddmpc_closed_loop_kernel_name", "ddmpc_set_input_bounds", "ddmpc_set_output_bounds", "ddmpc_debug_large_box_order",
     "ddmpc_step_setpoints", "ddmpc_closed_loop_setpoints", "ddmpc_get_setpoint_gain",
+    "ddmpc_set_instance_input_bounds", "ddmpc_set_instance_output_bounds",
 )
 
 c_double_p = C.POINTER(C.c_double)
@@ -112,6 +113,10 @@ def load() -> C.CDLL:
     lib.ddmpc_set_input_bounds.restype = C.c_int
     lib.ddmpc_set_output_bounds.argtypes = [vp, vp, vp]
     lib.ddmpc_set_output_bounds.restype = C.c_int
+    lib.ddmpc_set_instance_input_bounds.argtypes = [vp, vp, vp]
+    lib.ddmpc_set_instance_input_bounds.restype = C.c_int
+    lib.ddmpc_set_instance_output_bounds.argtypes = [vp, vp, vp]
+    lib.ddmpc_set_instance_output_bounds.restype = C.c_int
     lib.ddmpc_get_solution.argtypes = [vp, C.c_int, vp, C.c_int]
     lib.ddmpc_hankel.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int, C.c_int]
     lib.ddmpc_cost_model.argtypes = [vp, c_double_p, c_double_p]

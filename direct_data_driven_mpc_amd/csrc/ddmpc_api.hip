@@ -10,6 +10,7 @@
 #include "ddmpc_box_law.hpp"
 #include "ddmpc_setpoint_law.hpp"
 #include "ddmpc_setpoint_box_law.hpp"
+#include "ddmpc_instance_box_law.hpp"
 #include "ddmpc_setpoint_convex_law.hpp"
 #include "../../include/ddmpc.h"
 
@@ -312,6 +313,14 @@ struct ddmpc_handle {
   std::vector<double> umin_h, umax_h, ymin_h, ymax_h;
   bool bounded = false;
   DevBuf d_box_bd, d_ubnd, d_ybnd;         // ... [a | c | lo | hi | 1/d] of the box list (ddmpc_box_law.hpp); [u_min | u_max], [y_min | y_max] for the reconstruction
+  // per-instance bounds (ddmpc_set_instance_input_bounds / _output_bounds, Route::BoxLaw at most 271 rows): [batch][m] / [batch][p]
+  // rows, empty while the kind is shared or absent.  umin_h .. ymax_h above then hold, per channel, the smallest finite lower and
+  // the largest finite upper bound of the batch (infinite where no instance has one): which channels are boxed -- all that
+  // build_box_list and the shared [lo | hi] columns of d_box_bd are asked for on such a handle.  d_ibnd: the channel table
+  // [batch][lo (m+p) | hi (m+p)] of ddmpc_instance_box_law.hpp, kept while either kind is per instance (the shared kind broadcast
+  // into it, -+infinity without a bound).
+  std::vector<double> iumin_h, iumax_h, iymin_h, iymax_h;
+  DevBuf d_ibnd;
   DevBuf s_gain, s_prep_status, s_mcol, s_cwl_ref;   // ... the preparation of ddmpc_solve's own (solve_box): a kept ddmpc_prepare survives the solve
   int epoch = 0;                           // cold launches so far (KParams::epoch)
   int flag_epoch = 0;                      // latest stamp written into d_rflag
@@ -336,6 +345,9 @@ static Route select_route(const ddmpc_handle* h) {
   if (h->large_nominal) return phases ? Route::NominalPhases : Route::NominalOneWg;
   return phases ? Route::RobustPhases : Route::RobustOneWg;
 }
+
+// Bounds of either kind are per instance: the twins of ddmpc_instance_box_law.hpp serve the handle's steps and fused loops.
+static bool instance_bounds(const ddmpc_handle* h) { return !h->iumin_h.empty() || !h->iymin_h.empty(); }
 
 static bool nominal_route(Route r) { return r == Route::NominalPhases || r == Route::NominalOneWg; }
 
@@ -949,7 +961,7 @@ int ddmpc_destroy(ddmpc_handle* h) {
                     &h->d_lfac, &h->d_lfacT, &h->d_gain, &h->d_prep_status, &h->d_zero, &h->d_dmat, &h->d_need, &h->d_io, &h->d_rr, &h->d_alpha, &h->d_zws, &h->d_resc, &h->d_xws, &h->d_rflag, &h->d_rrmeta, &h->d_gpre, &h->d_perm, &h->d_rr2d, &h->d_rr2res, &h->d_rr2mt, &h->d_rr2v, &h->d_rr2zp, &h->d_rr2sc, &h->d_wz, &h->d_gz, &h->d_gres, &h->d_zvirt, &h->d_rr3w, &h->d_rr3k, &h->d_large_seed, &h->d_rr_fb, &h->d_rrmeta_fb, &h->d_rr2cand, &h->d_rr2tol, &h->d_rr2rank, &h->d_wd, &h->d_rr2y,
                     &h->d_mcol, &h->d_cwl_tab, &h->d_cwl_sg, &h->d_cwl_ref, &h->d_r3y, &h->d_r3res, &h->d_r3zp, &h->d_r3flag,
                     &h->d_box_bd, &h->d_ubnd, &h->d_ybnd, &h->d_r3bi, &h->d_r3bd, &h->s_gain, &h->s_prep_status, &h->s_mcol, &h->s_cwl_ref, &h->d_lwup, &h->d_lwyp,
-                    &h->d_box_seed, &h->d_sgain, &h->d_sptab, &h->d_sp, &h->d_uref, &h->d_yref, &h->d_chbnd};
+                    &h->d_box_seed, &h->d_ibnd, &h->d_sgain, &h->d_sptab, &h->d_sp, &h->d_uref, &h->d_yref, &h->d_chbnd};
   for (DevBuf* b : bufs) b->release();
   h->h_io.release();
   h->h_flag.release();
@@ -1711,11 +1723,13 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
 
 // Route::BoxLaw (input bounds): a control step on what ddmpc_prepare kept -- the law, M for the whole box list and the table.
 // seeded (DDMPC_OPT_BOX_WARM_START = 1 only): the iteration starts from the set in d_box_seed; with the option 1 every launch
-// leaves its set there.
+// leaves its set there.  Per-instance bounds (instance_bounds): the twins of ddmpc_instance_box_law.hpp with the channel table;
+// DDMPC_OPT_BOX_WARM_START is not honoured there -- from the empty set, no seed read or left.
 static int launch_box_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                            int32_t* iters, bool seeded) {
   if (int rc = reserve_beta(h)) return rc;
-  const bool warm = h->box_warm != 0;
+  const bool inst = instance_bounds(h);
+  const bool warm = h->box_warm != 0 && !inst;
   if (warm)
     if (int rc = h->d_box_seed.ensure((size_t)h->batch * (size_t)std::max(h->prep.cwl_nbox, 1))) return rc;
   // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard: its registers and LDS are the kernel's own)
@@ -1730,7 +1744,13 @@ static int launch_box_step(ddmpc_handle* h, const double* up, const double* yp, 
                        (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
                        h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, seed...);
   };
-  if (warm) {
+  if (inst) {
+    const double* chb = (const double*)h->d_ibnd.p;
+    if (yb && h->box_safeguard) launch(ddmpc_instance_box_step_kernel<true, true>, chb);
+    else if (yb) launch(ddmpc_instance_box_step_kernel<false, true>, chb);
+    else if (h->box_safeguard) launch(ddmpc_instance_box_step_kernel<true, false>, chb);
+    else launch(ddmpc_instance_box_step_kernel<false, false>, chb);
+  } else if (warm) {
     const BoxSeed seed{(signed char*)h->d_box_seed.p, seeded ? 1 : 0};
     if (yb && h->box_safeguard) launch(ddmpc_box_step_kernel<true, true, BoxSeed>, seed);
     else if (yb) launch(ddmpc_box_step_kernel<false, true, BoxSeed>, seed);
@@ -2931,6 +2951,9 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_SETPOINT_BOX_LAW must be 0 or 1");
       if (value == 1) {                                 // (the refusals of DDMPC_OPT_SETPOINT_LAW but the one of bounds)
         const char* pre = "DDMPC_OPT_SETPOINT_BOX_LAW";
+        if (instance_bounds(h))
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: not on a handle with per-instance bounds (ddmpc_set_instance_input_bounds / "
+                      "_output_bounds: the setpoint kernels read the bounds shared by the batch)", pre);
         if (h->prm.controller_type != DDMPC_ROBUST)
           return fail(DDMPC_ERR_UNSUPPORTED, "%s: ROBUST controllers only (a NOMINAL one fixes its outputs to the setpoint as hard rows)", pre);
         if (h->kp.convex)
@@ -2954,6 +2977,9 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_SETPOINT_CONVEX_LAW must be 0 or 1");
       if (value == 1) {                                 // (CONVEX only, so never on together with options 18 / 19, which refuse it)
         const char* pre = "DDMPC_OPT_SETPOINT_CONVEX_LAW";
+        if (instance_bounds(h))
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: not on a handle with per-instance bounds (ddmpc_set_instance_input_bounds / "
+                      "_output_bounds: the setpoint kernels read the bounds shared by the batch)", pre);
         if (h->prm.controller_type != DDMPC_ROBUST)
           return fail(DDMPC_ERR_UNSUPPORTED, "%s: ROBUST controllers only (a NOMINAL one fixes its outputs to the setpoint as hard rows)", pre);
         if (!h->kp.convex)
@@ -3094,6 +3120,120 @@ static const char* setpoint_outside_bounds(const ddmpc_handle* h, const double* 
   return nullptr;
 }
 
+static int apply_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max, bool any);
+static int apply_output_bounds(ddmpc_handle* h, const double* y_min, const double* y_max, bool any);
+
+// The channel table of ddmpc_instance_box_law.hpp from the handle's bounds of both kinds: [batch][lo (m+p) | hi (m+p)], inputs
+// first, a shared kind broadcast, -+infinity without a bound.  Released when neither kind is per instance.  Every bounds call ends
+// here (behind its stream synchronisation: nothing in flight reads the table).
+static int upload_instance_bounds(ddmpc_handle* h) {
+  if (!instance_bounds(h)) { h->d_ibnd.release(); return DDMPC_OK; }
+  const int m = h->prm.m, pp = h->prm.p, nch = m + pp;
+  const size_t B = (size_t)h->batch;
+  const double inf = std::numeric_limits<double>::infinity();
+  std::vector<double> t(B * 2 * (size_t)nch);
+  for (size_t b = 0; b < B; ++b) {
+    double* lo = t.data() + b * 2 * (size_t)nch;
+    double* hi = lo + nch;
+    for (int c = 0; c < m; ++c) {
+      lo[c] = !h->iumin_h.empty() ? h->iumin_h[b * m + c] : (h->umin_h.empty() ? -inf : h->umin_h[c]);
+      hi[c] = !h->iumin_h.empty() ? h->iumax_h[b * m + c] : (h->umin_h.empty() ? inf : h->umax_h[c]);
+    }
+    for (int c = 0; c < pp; ++c) {
+      lo[m + c] = !h->iymin_h.empty() ? h->iymin_h[b * pp + c] : (h->ymin_h.empty() ? -inf : h->ymin_h[c]);
+      hi[m + c] = !h->iymin_h.empty() ? h->iymax_h[b * pp + c] : (h->ymin_h.empty() ? inf : h->ymax_h[c]);
+    }
+  }
+  int rc = h->d_ibnd.ensure(t.size() * sizeof(double));
+  if (!rc && hipMemcpy(h->d_ibnd.p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(DDMPC_ERR_HIP, "per-instance bounds: the copy of the channel table failed");
+  if (rc) {                             // (no table: no launch may ask for it -- the handle keeps the per-channel summary as shared bounds)
+    h->iumin_h.clear(); h->iumax_h.clear(); h->iymin_h.clear(); h->iymax_h.clear();
+    h->d_ibnd.release();
+  }
+  return rc;
+}
+
+// With the terminal constraint: the handle's setpoint of one kind (`nm`: "u" / "y", nc channels) against every row of the
+// per-instance bounds of that kind.
+static int instance_setpoint_outside(const ddmpc_handle* h, const double* sp, const double* lo, const double* hi, int nc, const char* nm) {
+  if (!h->prm.use_terminal_constraint) return DDMPC_OK;
+  for (int64_t b = 0; b < h->batch; ++b)
+    for (int ch = 0; ch < nc; ++ch)
+      if (sp[ch] < lo[b * nc + ch] || sp[ch] > hi[b * nc + ch])
+        return fail(DDMPC_ERR_INVALID, "instance %lld, channel %d: %s_s lies outside [%s_min, %s_max] of that instance and the terminal constraint "
+                    "fixes the last n %s to it", (long long)b, ch, nm, nm, nm, nm[0] == 'u' ? "inputs" : "outputs");
+  return DDMPC_OK;
+}
+
+// The rows of a per-instance bounds call checked (nm: "u" / "y", nc channels), and their per-channel summary for the box list:
+// the smallest finite lower and the largest finite upper bound of the batch, infinite where no instance has one.
+static int check_instance_bounds(const ddmpc_handle* h, const double* lo, const double* hi, int nc, const char* nm,
+                                 std::vector<double>* slo, std::vector<double>* shi, bool* any) {
+  const double inf = std::numeric_limits<double>::infinity();
+  slo->assign((size_t)nc, -inf);
+  shi->assign((size_t)nc, inf);
+  *any = false;
+  for (int64_t b = 0; b < h->batch; ++b)
+    for (int ch = 0; ch < nc; ++ch) {
+      const double l = lo[b * nc + ch], u = hi[b * nc + ch];
+      if (l != l) return fail(DDMPC_ERR_INVALID, "%s_min is NaN at instance %lld, channel %d", nm, (long long)b, ch);
+      if (u != u) return fail(DDMPC_ERR_INVALID, "%s_max is NaN at instance %lld, channel %d", nm, (long long)b, ch);
+      if (l >= u)
+        return fail(DDMPC_ERR_INVALID, "%s_min >= %s_max at instance %lld, channel %d: the box is empty or a point", nm, nm, (long long)b, ch);
+      if (std::isfinite(l)) { (*slo)[ch] = std::isfinite((*slo)[ch]) ? std::min((*slo)[ch], l) : l; *any = true; }
+      if (std::isfinite(u)) { (*shi)[ch] = std::isfinite((*shi)[ch]) ? std::max((*shi)[ch], u) : u; *any = true; }
+    }
+  return DDMPC_OK;
+}
+
+// What per-instance bounds refuse beyond the refusals of the shared calls (`what`: "per-instance input bounds" / "... output bounds").
+static int instance_bounds_refusal(const ddmpc_handle* h, const char* what) {
+  if (h->large)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels; beyond them the "
+                "phase kernels read the bounds shared by the batch, also with DDMPC_OPT_LARGE_BOUNDS = 1)", what, h->kp.r);
+  if (h->setpoint_box_law || h->setpoint_convex_law)
+    return fail(DDMPC_ERR_UNSUPPORTED, "%s: not with %s = 1 (the setpoint kernels read the bounds shared by the batch)", what,
+                h->setpoint_box_law ? "DDMPC_OPT_SETPOINT_BOX_LAW" : "DDMPC_OPT_SETPOINT_CONVEX_LAW");
+  return DDMPC_OK;
+}
+
+int ddmpc_set_instance_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max) {
+  if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
+  if ((u_min == nullptr) != (u_max == nullptr))
+    return fail(DDMPC_ERR_INVALID, "%s is null: pass both u_min and u_max, or neither to remove the bounds", u_min ? "u_max" : "u_min");
+  if (!u_min) return ddmpc_set_input_bounds(h, nullptr, nullptr);
+  const int m = h->prm.m;
+  std::vector<double> slo, shi;
+  bool any = false;
+  if (int rc = check_instance_bounds(h, u_min, u_max, m, "u", &slo, &shi, &any)) return rc;
+  if (!any) return ddmpc_set_input_bounds(h, nullptr, nullptr);      // (no finite bound in the batch: a removal)
+  if (int rc = instance_setpoint_outside(h, h->us_h.data(), u_min, u_max, m, "u")) return rc;
+  if (int rc = instance_bounds_refusal(h, "per-instance input bounds")) return rc;
+  if (int rc = apply_input_bounds(h, slo.data(), shi.data(), true)) return rc;
+  h->iumin_h.assign(u_min, u_min + (size_t)h->batch * m);
+  h->iumax_h.assign(u_max, u_max + (size_t)h->batch * m);
+  return upload_instance_bounds(h);
+}
+
+int ddmpc_set_instance_output_bounds(ddmpc_handle* h, const double* y_min, const double* y_max) {
+  if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
+  if ((y_min == nullptr) != (y_max == nullptr))
+    return fail(DDMPC_ERR_INVALID, "%s is null: pass both y_min and y_max, or neither to remove the bounds", y_min ? "y_max" : "y_min");
+  if (!y_min) return ddmpc_set_output_bounds(h, nullptr, nullptr);
+  const int pp = h->prm.p;
+  std::vector<double> slo, shi;
+  bool any = false;
+  if (int rc = check_instance_bounds(h, y_min, y_max, pp, "y", &slo, &shi, &any)) return rc;
+  if (!any) return ddmpc_set_output_bounds(h, nullptr, nullptr);     // (no finite bound in the batch: a removal)
+  if (int rc = instance_setpoint_outside(h, h->ys_h.data(), y_min, y_max, pp, "y")) return rc;
+  if (int rc = instance_bounds_refusal(h, "per-instance output bounds")) return rc;
+  if (int rc = apply_output_bounds(h, slo.data(), shi.data(), true)) return rc;
+  h->iymin_h.assign(y_min, y_min + (size_t)h->batch * pp);
+  h->iymax_h.assign(y_max, y_max + (size_t)h->batch * pp);
+  return upload_instance_bounds(h);
+}
+
 int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max) {
   if (!h) return fail(DDMPC_ERR_INVALID, "null handle");
   if ((u_min == nullptr) != (u_max == nullptr))
@@ -3108,8 +3248,19 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
       any = any || std::isfinite(u_min[ch]) || std::isfinite(u_max[ch]);
     }
   }
-  if (any) {
+  if (any)
     if (const char* msg = setpoint_outside_bounds(h, h->us_h.data(), u_min, u_max)) return fail(DDMPC_ERR_INVALID, "u_min / u_max: %s", msg);
+  if (int rc = apply_input_bounds(h, u_min, u_max, any)) return rc;
+  h->iumin_h.clear();                   // (the last call wins: the input bounds are shared now)
+  h->iumax_h.clear();
+  return upload_instance_bounds(h);
+}
+
+// ... what the call does once its values are accepted: the refusals that depend on which channels are bounded (`any`: some
+// bound is finite), then the handle's state.  ddmpc_set_instance_input_bounds comes here with the per-channel summary of its rows.
+static int apply_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max, bool any) {
+  const ddmpc_params& p = h->prm;
+  if (any) {
     if (h->setpoint_law && !h->setpoint_box_law)
       return fail(DDMPC_ERR_UNSUPPORTED, "input bounds: not with DDMPC_OPT_SETPOINT_LAW = 1 (the setpoint step knows no bounds)");
     if (p.controller_type != DDMPC_ROBUST)
@@ -3177,8 +3328,18 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
       any = any || std::isfinite(y_min[ch]) || std::isfinite(y_max[ch]);
     }
   }
-  if (any) {
+  if (any)
     if (const char* msg = output_setpoint_outside_bounds(h, h->ys_h.data(), y_min, y_max)) return fail(DDMPC_ERR_INVALID, "y_min / y_max: %s", msg);
+  if (int rc = apply_output_bounds(h, y_min, y_max, any)) return rc;
+  h->iymin_h.clear();                   // (the last call wins: the output bounds are shared now)
+  h->iymax_h.clear();
+  return upload_instance_bounds(h);
+}
+
+// ... what the call does once its values are accepted (as apply_input_bounds).
+static int apply_output_bounds(ddmpc_handle* h, const double* y_min, const double* y_max, bool any) {
+  const ddmpc_params& p = h->prm;
+  if (any) {
     if (h->setpoint_law && !h->setpoint_box_law)
       return fail(DDMPC_ERR_UNSUPPORTED, "output bounds: not with DDMPC_OPT_SETPOINT_LAW = 1 (the setpoint step knows no bounds)");
     if (p.controller_type != DDMPC_ROBUST)
@@ -3235,10 +3396,16 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
 
 int ddmpc_set_setpoints(ddmpc_handle* h, const double* u_s, const double* y_s) {
   if (!h || !u_s || !y_s) return fail(DDMPC_ERR_INVALID, "null argument");
-  if (!h->umin_h.empty())
+  if (!h->iumin_h.empty()) {            // (per-instance bounds: against every row)
+    if (int rc = instance_setpoint_outside(h, u_s, h->iumin_h.data(), h->iumax_h.data(), h->prm.m, "u")) return rc;
+  } else if (!h->umin_h.empty()) {
     if (const char* msg = setpoint_outside_bounds(h, u_s, h->umin_h.data(), h->umax_h.data())) return fail(DDMPC_ERR_INVALID, "%s", msg);
-  if (!h->ymin_h.empty())
+  }
+  if (!h->iymin_h.empty()) {
+    if (int rc = instance_setpoint_outside(h, y_s, h->iymin_h.data(), h->iymax_h.data(), h->prm.p, "y")) return rc;
+  } else if (!h->ymin_h.empty()) {
     if (const char* msg = output_setpoint_outside_bounds(h, y_s, h->ymin_h.data(), h->ymax_h.data())) return fail(DDMPC_ERR_INVALID, "%s", msg);
+  }
   HIP_TRY(hipSetDevice(h->device));
   h->us_h.assign(u_s, u_s + h->prm.m);
   h->ys_h.assign(y_s, y_s + h->prm.p);
@@ -3312,12 +3479,15 @@ int ddmpc_get_solution(ddmpc_handle* h, int what, double* out, int mem) {
     HIP_TRY(hipGetLastError());
     l.x = XState::Written;
   }
+  const bool inst = instance_bounds(h);         // (per-instance bounds: both kinds are read from the channel table)
+  const double* ibnd = (const double*)h->d_ibnd.p;
   hipLaunchKernelGGL(ddmpc_reconstruct_kernel, dim3((unsigned)h->batch), dim3(256), 0, h->stream, k, 16 * h->kc.NT, what, h->ud,
                      h->yd, l.up, l.yp, (const double*)h->d_beta.p, (const signed char*)h->d_act.p, dst,
                      resc ? (const double*)h->d_zws.p : (const double*)nullptr, resc ? (const int*)h->d_resc.p : (const int*)nullptr,
                      resc ? (const double*)h->d_xws.p : (const double*)nullptr,
-                     !h->umin_h.empty() ? (const double*)h->d_ubnd.p : (const double*)nullptr,
-                     !h->ymin_h.empty() ? (const double*)h->d_ybnd.p : (const double*)nullptr);
+                     !h->umin_h.empty() ? (inst ? ibnd : (const double*)h->d_ubnd.p) : (const double*)nullptr,
+                     !h->ymin_h.empty() ? (inst ? ibnd + k.m : (const double*)h->d_ybnd.p) : (const double*)nullptr,
+                     inst ? 2LL * k.nch : 0LL);
   HIP_TRY(hipGetLastError());
   if (mem == DDMPC_MEM_HOST) {
     HIP_TRY(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -3464,7 +3634,8 @@ static int select_loop_path(ddmpc_handle* h, int n_mpc_step, LoopPath* path) {
 static int launch_fused_loop(ddmpc_handle* h, LoopPath path, LoopArgs a) {
   if (int rc = reserve_beta(h)) return rc;
   a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p;
-  const bool warm = path == LoopPath::FusedBox && h->box_warm != 0;       // DDMPC_OPT_BOX_WARM_START, as launch_box_step
+  const bool inst = path == LoopPath::FusedBox && instance_bounds(h);     // per-instance bounds: the twins, as launch_box_step
+  const bool warm = path == LoopPath::FusedBox && h->box_warm != 0 && !inst;   // DDMPC_OPT_BOX_WARM_START, as launch_box_step
   const int seeded = (warm && box_seed_valid(h)) ? 1 : 0;
   if (warm)
     if (int rc = h->d_box_seed.ensure((size_t)h->batch * (size_t)std::max(h->prep.cwl_nbox, 1))) return rc;
@@ -3487,7 +3658,13 @@ static int launch_fused_loop(ddmpc_handle* h, LoopPath path, LoopArgs a) {
   } else {    // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard, as launch_box_step)
     const double* bd = (const double*)h->d_box_bd.p;
     const int* ref = h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr;
-    if (warm) {                            // (the seed follows the window of the last solve)
+    if (inst) {                            // (the channel table follows the window of the last solve)
+      const double* chb = (const double*)h->d_ibnd.p;
+      if (yb && h->box_safeguard) launch(ddmpc_closed_loop_instance_box_kernel<true, true>, nbox, tab, bd, mcol, sg, ref, chb);
+      else if (yb) launch(ddmpc_closed_loop_instance_box_kernel<false, true>, nbox, tab, bd, mcol, sg, ref, chb);
+      else if (h->box_safeguard) launch(ddmpc_closed_loop_instance_box_kernel<true, false>, nbox, tab, bd, mcol, sg, ref, chb);
+      else launch(ddmpc_closed_loop_instance_box_kernel<false, false>, nbox, tab, bd, mcol, sg, ref, chb);
+    } else if (warm) {                     // (the seed follows the window of the last solve)
       const BoxSeed seed{(signed char*)h->d_box_seed.p, seeded};
       auto launch_warm = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(threads), 0, h->stream, h->kp, 16 * h->kc.NT,
@@ -3760,7 +3937,7 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
   }
   LoopPath path;
   if ((rc = select_loop_path(h, n_mpc_step, &path))) return rc;
-  h->loop_kernel = kLoopKernel[(int)path];
+  h->loop_kernel = (path == LoopPath::FusedBox && instance_bounds(h)) ? "ddmpc_closed_loop_instance_box_kernel" : kLoopKernel[(int)path];
   if ((rc = fused(path) ? launch_fused_loop(h, path, a) : run_step_loop(h, path, a, nb))) return rc;
   end_solve(h, a.lwup, a.lwyp);    // (the last solve's window: the per-step cold path re-solves there, the other paths wrote its beta)
   return copy_loop_outputs(h, mem, nb, a, user, status);

@@ -34,6 +34,8 @@ __global__ void ddmpc_hankel_kernel(const double* __restrict__ X, double* __rest
 // ddmpc_set_input_bounds; a free input row in the active set is held at its bound (t = bound, D = 0).  `ybnd` (null without
 // output bounds): [y_min (p) | y_max (p)] of ddmpc_set_output_bounds; the workspace then holds sa + 4 say per row (sa: slack or
 // input, say: output), and a K_WPRED row with say != 0 has ybar = its bound exactly, sigma = +- c eps_max or -lam beta / lamb_sigma.
+// `bnd_stride` (0: the shared bounds above): per-instance bounds (ddmpc_instance_box_law.hpp) -- ubnd is the channel table
+// [batch][lo (nch) | hi (nch)] and ybnd the same table moved on by m, bnd_stride = 2 nch doubles from one instance to the next.
 // --------------------------------------------------------------------------
 __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const double* __restrict__ u_d,
                                          const double* __restrict__ y_d, const double* __restrict__ u_past,
@@ -41,9 +43,10 @@ __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const dou
                                          const signed char* __restrict__ act_ws, double* __restrict__ out,
                                          const double* __restrict__ z_ws, const int* __restrict__ rescued,
                                          const double* __restrict__ x_ws, const double* __restrict__ ubnd,
-                                         const double* __restrict__ ybnd) {
+                                         const double* __restrict__ ybnd, long long bnd_stride) {
   const long long b = blockIdx.x;
   const int n = P.npu / P.m;
+  const int uhi = bnd_stride ? P.nch : P.m, yhi = bnd_stride ? P.nch : P.p;   // from a channel's lower bound to its upper one
   const bool resc = rescued != nullptr && rescued[b] != 0;
   if (resc && what != 0) {
     // NOMINAL instance solved by the rank-revealing kernel (exact data): it exports z = [ubar; ybar] per component and
@@ -92,7 +95,7 @@ __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const dou
       for (int j = 0; j < P.r; ++j) sdb += dr[j] * bw[j];
       z = t - P.lam * (D * bb + sdb);
     }
-    if (ubnd != nullptr && kind == K_UFREE && s_act != 0) z = ubnd[(s_act > 0 ? P.m : 0) + ch];
+    if (ubnd != nullptr && kind == K_UFREE && s_act != 0) z = ubnd[b * bnd_stride + (s_act > 0 ? uhi : 0) + ch];
     if (ch < P.m) {
       if (what == 1) out[b * (long long)(P.Ln * P.m) + k * P.m + ch] = z;
       continue;
@@ -101,7 +104,7 @@ __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const dou
     double sg = 0.0;
     if (y_act != 0 && kind == K_WPRED) {
       sg = (s_act != 0) ? s_act * P.bound : -P.lam * bb / P.lamb_sigma;
-      if (what == 2) out[b * (long long)(P.Ln * P.p) + k * P.p + cy] = ybnd[(y_act > 0 ? P.p : 0) + cy];
+      if (what == 2) out[b * (long long)(P.Ln * P.p) + k * P.p + cy] = ybnd[b * bnd_stride + (y_act > 0 ? yhi : 0) + cy];
       if (what == 3) out[b * (long long)(P.Ln * P.p) + k * P.p + cy] = sg;
       continue;
     }

@@ -492,6 +492,36 @@ class BatchedDDMPC:
         L.check(self._lib.ddmpc_set_output_bounds(self._h, C.c_void_p(lo.ctypes.data) if lo is not None else C.c_void_p(),
                                                   C.c_void_p(hi.ctypes.data) if hi is not None else C.c_void_p()))
 
+    def _instance_rows(self, lo, hi, nc: int, what: str):
+        """[batch, nc] float64 rows of a per-instance bounds call; None stays None (both: a removal, one: the library refuses it)."""
+        rows = []
+        for a in (lo, hi):
+            if a is not None:
+                a = np.asarray(a, dtype=np.float64)
+                if a.shape != (self.batch, nc):
+                    raise ValueError("%s: arrays of shape [batch, %d] = (%d, %d) expected, got %s" % (what, nc, self.batch, nc, a.shape))
+                a = np.ascontiguousarray(a)
+            rows.append(a)
+        return rows[0], rows[1]
+
+    def set_instance_input_bounds(self, u_min, u_max) -> None:
+        """Input bounds per instance, u_min[b][ch] <= ubar[k][ch] <= u_max[b][ch] (`ddmpc_set_instance_input_bounds`): arrays of
+        shape [batch, m], -inf / +inf = no bound on that side for that instance; `None, None` removes the input bounds.  Replaces,
+        and is replaced by, `set_input_bounds`; independent of the output bounds.  ROBUST controllers up to 271 rows with scalar /
+        diagonal weights; takes effect at the next solve and drops what `prepare` kept and the last solution.  The warm start of
+        `set_box_warm_start` is not honoured on such a handle."""
+        lo, hi = self._instance_rows(u_min, u_max, self.m, "set_instance_input_bounds")
+        L.check(self._lib.ddmpc_set_instance_input_bounds(self._h, C.c_void_p(lo.ctypes.data) if lo is not None else C.c_void_p(),
+                                                          C.c_void_p(hi.ctypes.data) if hi is not None else C.c_void_p()))
+
+    def set_instance_output_bounds(self, y_min, y_max) -> None:
+        """Output bounds per instance, y_min[b][ch] <= ybar[k][ch] <= y_max[b][ch] (`ddmpc_set_instance_output_bounds`): arrays of
+        shape [batch, p]; `None, None` removes the output bounds.  Replaces, and is replaced by, `set_output_bounds`; otherwise as
+        `set_instance_input_bounds`."""
+        lo, hi = self._instance_rows(y_min, y_max, self.p, "set_instance_output_bounds")
+        L.check(self._lib.ddmpc_set_instance_output_bounds(self._h, C.c_void_p(lo.ctypes.data) if lo is not None else C.c_void_p(),
+                                                           C.c_void_p(hi.ctypes.data) if hi is not None else C.c_void_p()))
+
     def set_large_bounds(self, on: bool) -> None:
         """ROBUST controllers beyond 271 rows: True = `set_input_bounds` / `set_output_bounds` are accepted on a handle of
         272 .. 1024 rows (phase kernels; at most the capacity, 64 by default, of boxed components active at once, an instance beyond that reports

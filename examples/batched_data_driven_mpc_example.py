@@ -67,6 +67,10 @@ def parse_args():
                          "(set_setpoint_box_law; --box_safeguard applies).  With slack Convex, bounded or not: "
                          "set_setpoint_convex_law.  With bounds and a long horizon, beyond 271 rows: "
                          "set_large_setpoint_bounds (--large_box_capacity / --large_box_safeguard apply)")
+    ap.add_argument("--bound_spread", type=float, default=None,
+                    help="a fleet with different limits: with --u_min/--u_max and / or --y_min/--y_max, the finite bounds of "
+                         "instance b are widened by S * b / (batch - 1) on both sides and set per instance "
+                         "(set_instance_input_bounds / set_instance_output_bounds; up to 271 rows, not with --setpoint_spread)")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     return ap.parse_args()
 
@@ -109,12 +113,28 @@ def main():
     if (a.u_min is None) != (a.u_max is None):
         raise ValueError("--u_min and --u_max go together (use inf / -inf for a side without a bound)")
     eng.set_large_bounds(True)                   # (bounds with a long horizon, beyond 271 rows: the phase kernels)
-    if a.u_min is not None:
-        eng.set_input_bounds(a.u_min if len(a.u_min) > 1 else a.u_min[0], a.u_max if len(a.u_max) > 1 else a.u_max[0])
     if (a.y_min is None) != (a.y_max is None):
         raise ValueError("--y_min and --y_max go together (use inf / -inf for a side without a bound)")
-    if a.y_min is not None:
-        eng.set_output_bounds(a.y_min if len(a.y_min) > 1 else a.y_min[0], a.y_max if len(a.y_max) > 1 else a.y_max[0])
+    if a.bound_spread is not None:
+        if a.u_min is None and a.y_min is None:
+            raise ValueError("--bound_spread widens the bounds of --u_min/--u_max and / or --y_min/--y_max: give at least one pair")
+        if a.setpoint_spread is not None:
+            raise ValueError("--bound_spread and --setpoint_spread do not go together (per-instance bounds with per-instance "
+                             "setpoints are not covered)")
+
+        def rows(lo, hi, nc):                    # instance b: [lo - S b / (B - 1), hi + S b / (B - 1)] on the finite sides
+            grow = a.bound_spread * np.arange(B)[:, None] / max(B - 1, 1)
+            return np.broadcast_to(np.asarray(lo, float), (nc,)) - grow, np.broadcast_to(np.asarray(hi, float), (nc,)) + grow
+
+        if a.u_min is not None:
+            eng.set_instance_input_bounds(*rows(a.u_min, a.u_max, m))
+        if a.y_min is not None:
+            eng.set_instance_output_bounds(*rows(a.y_min, a.y_max, p))
+    else:
+        if a.u_min is not None:
+            eng.set_input_bounds(a.u_min if len(a.u_min) > 1 else a.u_min[0], a.u_max if len(a.u_max) > 1 else a.u_max[0])
+        if a.y_min is not None:
+            eng.set_output_bounds(a.y_min if len(a.y_min) > 1 else a.y_min[0], a.y_max if len(a.y_max) > 1 else a.y_max[0])
     if a.box_safeguard:
         eng.set_box_safeguard(True)
     if a.box_warm_start:
@@ -202,6 +222,8 @@ def main():
         print(f"non-optimal instances: {n_bad}; final |y - y_s| mean {err_y.mean(axis=0)}, max {err_y.max(axis=0)}; "
               f"final |u - u_s| mean {err_u.mean(axis=0)}")
         print(f"instance 0: y[-1] = {y_sys[0, -1]}, u[-1] = {u_sys[0, -1]}")
+        if a.bound_spread is not None:
+            print(f"per-instance bounds (spread {a.bound_spread}): {eng.closed_loop_kernel_name()}")
         if us_b is not None:
             print(f"per-instance setpoints (spread {a.setpoint_spread}): instance 0 tracks y_s = {ys_b[0]}, u_s = {us_b[0]}; "
                   f"{eng.closed_loop_kernel_name()}")

@@ -647,6 +647,49 @@ int ddmpc_set_input_bounds(ddmpc_handle* h, const double* u_min, const double* u
  * bound exactly and sigma = (ybar + sigma) - bound, or +- c eps_max with both active. */
 int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* y_max);
 
+/* Input bounds per instance: u_min[b][ch] <= ubar[k][ch] <= u_max[b][ch] on every FREE prediction step of instance b -- the
+ * meaning of ddmpc_set_input_bounds with one row per instance, for a batch that is a fleet of controllers with different
+ * actuator ranges.  u_min, u_max: HOST, [batch][m]; -INFINITY / +INFINITY = instance b has no bound on that side of that
+ * channel; both NULL removes the input bounds.  The call replaces, and is replaced by, ddmpc_set_input_bounds: the last call
+ * of either wins.  Independent of the output bounds: one kind may be shared while the other is per instance.  Like the shared
+ * call it synchronises, forgets what ddmpc_prepare kept and the last solution (ddmpc_get_solution: DDMPC_ERR_NOT_READY) and
+ * takes effect at the next solve.
+ * The box list, and with it the columns of M, stays shared by the batch: a channel is boxed when ANY instance has a finite
+ * bound on it.  An instance whose own bound on a listed channel is infinite never activates those components.  When no
+ * instance has a finite bound the call is a removal: every result is bit-equal to a handle that never had it.  Rows that are
+ * all equal give results bit-equal to ddmpc_set_input_bounds with that row.
+ *   DDMPC_ERR_INVALID, with a message that names instance and channel: NaN in either array; u_min[b][ch] >= u_max[b][ch];
+ *     with the terminal constraint, the handle's u_s outside the interval of any instance (ddmpc_set_setpoints checks its
+ *     argument against every row on such a handle).  Only one pointer NULL.
+ *   DDMPC_ERR_UNSUPPORTED, with a message that names the reason: everything ddmpc_set_input_bounds refuses up to 271 rows
+ *     (NOMINAL, DDMPC_WEIGHT_DENSE, a zero weight on a boxed channel, DDMPC_REFINE_ALWAYS, n(m+p) > 256; a box list of more
+ *     than 288 components is named by ddmpc_set_instance_output_bounds or ddmpc_prepare; ddmpc_solve_from_host); more than 271
+ *     rows, also with DDMPC_OPT_LARGE_BOUNDS = 1 (the phase kernels read the shared bounds); a handle with
+ *     DDMPC_OPT_SETPOINT_BOX_LAW or DDMPC_OPT_SETPOINT_CONVEX_LAW on -- in the reverse order ddmpc_set_option refuses those two
+ *     on a handle that carries per-instance bounds of either kind.
+ * How it is served: Route::BoxLaw as under shared bounds, by twins of its two kernels that stage the instance's bounds in LDS
+ * (ddmpc_instance_box_law.hpp; the fused loop is "ddmpc_closed_loop_instance_box_kernel") -- ddmpc_solve with the cold contract
+ * and a preparation of the call's own, ddmpc_prepare + ddmpc_step (bit-equal to ddmpc_solve), ddmpc_closed_loop fused and per
+ * step, ddmpc_get_solution (an active input equals ITS INSTANCE's bound exactly).  Statuses, `iters`, the max_iter cap and
+ * optimal_inaccurate on refined laws are those of the shared-bounds kernels; DDMPC_OPT_BOX_SAFEGUARD applies.
+ * DDMPC_OPT_BOX_WARM_START is accepted and not honoured: every solve starts from the empty set and no seed is kept.  A handle
+ * without per-instance bounds launches exactly the kernels it launched before these calls existed.
+ * Not covered: more than 271 rows; per-instance setpoints on the same handle (options 19, 20, 22); the active-set warm start;
+ * keeping ddmpc_prepare's law and M across a call that changes bound values only; bounds per prediction step; NOMINAL
+ * controllers and dense weights. */
+int ddmpc_set_instance_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max);
+
+/* Output bounds per instance: y_min[b][ch] <= ybar[k][ch] <= y_max[b][ch] on every FREE prediction step of instance b -- the
+ * meaning of ddmpc_set_output_bounds (a bound on ybar, not on ybar + sigma; no infeasibility detection under the CONVEX slack
+ * box) with one row per instance.  y_min, y_max: HOST, [batch][p]; -INFINITY / +INFINITY = no bound on that side for that
+ * instance; both NULL removes the output bounds.  Replaces, and is replaced by, ddmpc_set_output_bounds; independent of the
+ * input bounds of either form.  Everything else -- side effects, the shared box list (a channel is boxed when any instance has
+ * a finite bound on it; no finite bound in the batch is a removal), DDMPC_ERR_INVALID with instance and channel (here y_s
+ * against every row under the terminal constraint), DDMPC_ERR_UNSUPPORTED (what ddmpc_set_output_bounds refuses up to 271 rows,
+ * the box list over 288 components included; more than 271 rows; options 19 / 20), how it is served, the options and what is
+ * not covered -- as ddmpc_set_instance_input_bounds.  In the solution an active output equals its instance's bound exactly. */
+int ddmpc_set_instance_output_bounds(ddmpc_handle* h, const double* y_min, const double* y_max);
+
 /* Values of the optimisation variables of the last ddmpc_solve, ddmpc_solve_from_host, ddmpc_step or ddmpc_closed_loop
  * (controller.py:434-445 `.value`); `out` sized as listed at DDMPC_SOL_*.  DDMPC_ERR_NOT_READY before any of them and after
  * ddmpc_set_data, ddmpc_set_setpoints or a ddmpc_prepare on the register-resident kernels ((m+p)(L+n) <= 271); a
