@@ -30,6 +30,7 @@ differing in some bit):
   test_nominal_affine_law                             the step kernel's cost from tabd[3] (ddmpc_rr2_solve.hpp)
   test_*_beyond_1024_rows                             the 1024-thread instances of the two one-workgroup kernels
   test_closed_loop_per_step                           prepare / step on the phase kernels with a moving window + ddmpc_plant_kernel
+  (the bounded kernels, up to 271 rows and beyond: tests/test_gpu_bounded_weights.py -- the per-component box table)
 
 Zero weights.  ROBUST: an unweighted output under the slack box has D0 = 1e25 + 1/lamb_sigma == D1 = 1e25 in fp64; its
 multiplier is ~1e-25, its slack 0, it never reaches the bound and so never enters the switched set whose Woodbury data divide
