@@ -1,4 +1,4 @@
-// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_setpoint_law.hpp, ddmpc_setpoint_box_law.hpp, ddmpc_setpoint_convex_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp, ddmpc_rr3_box.hpp).
+// ddmpc_api.hip -- C ABI (include/ddmpc.h) over the gfx950 kernels in ddmpc_cold2.hpp, ddmpc_aux_kernels.hpp, ddmpc_box_law.hpp, ddmpc_setpoint_law.hpp, ddmpc_setpoint_box_law.hpp, ddmpc_workspace_kernels.hpp and the phase pipelines (ddmpc_rr2*.hpp, ddmpc_rr3.hpp, ddmpc_rr3_box.hpp).
 // Host-side responsibilities: parameter validation with the reference's error
 // conditions (direct_data_driven_mpc_controller.py:165-168,211-222,298-343,664-670),
 // device buffer ownership, kernel-instance selection, launch.
@@ -10,8 +10,6 @@
 #include "ddmpc_box_law.hpp"
 #include "ddmpc_setpoint_law.hpp"
 #include "ddmpc_setpoint_box_law.hpp"
-#include "ddmpc_instance_box_law.hpp"
-#include "ddmpc_setpoint_convex_law.hpp"
 #include "../../include/ddmpc.h"
 
 #include <cmath>
@@ -301,7 +299,7 @@ struct ddmpc_handle {
   DevBuf d_sgain, d_sptab;                 // ... S [batch][m+p][r]; the m + p table copies with a unit setpoint (refined columns)
   int setpoint_box_law = 0;                // DDMPC_OPT_SETPOINT_BOX_LAW: the same on a handle that may carry bounds (ddmpc_setpoint_box_law.hpp); it governs when both are on
   DevBuf d_chbnd;                          // ... [lo (m+p) | hi (m+p)] per channel, +-infinity without a bound (ddmpc_prepare on Route::BoxLaw)
-  int setpoint_convex_law = 0;             // DDMPC_OPT_SETPOINT_CONVEX_LAW: the same under the CONVEX slack box, slack-only or bounded (ddmpc_setpoint_convex_law.hpp);
+  int setpoint_convex_law = 0;             // DDMPC_OPT_SETPOINT_CONVEX_LAW: the same under the CONVEX slack box, slack-only or bounded (the SLACK instantiations of ddmpc_setpoint_box_law.hpp);
                                            //   never on together with the two above (they refuse CONVEX, this one slack NONE)
   DevBuf d_sp, d_uref, d_yref;             // ... staging of host setpoints [u_s | y_s] (ddmpc_step_setpoints) and schedules (ddmpc_closed_loop_setpoints)
   const double *sp_us = nullptr, *sp_ys = nullptr;   // ... the device setpoints of the ddmpc_step_setpoints call in progress
@@ -317,7 +315,7 @@ struct ddmpc_handle {
   // rows, empty while the kind is shared or absent.  umin_h .. ymax_h above then hold, per channel, the smallest finite lower and
   // the largest finite upper bound of the batch (infinite where no instance has one): which channels are boxed -- all that
   // build_box_list and the shared [lo | hi] columns of d_box_bd are asked for on such a handle.  d_ibnd: the channel table
-  // [batch][lo (m+p) | hi (m+p)] of ddmpc_instance_box_law.hpp, kept while either kind is per instance (the shared kind broadcast
+  // [batch][lo (m+p) | hi (m+p)] of ddmpc_box_law.hpp (BoxChannels), kept while either kind is per instance (the shared kind broadcast
   // into it, -+infinity without a bound).
   std::vector<double> iumin_h, iumax_h, iymin_h, iymax_h;
   DevBuf d_ibnd;
@@ -346,7 +344,7 @@ static Route select_route(const ddmpc_handle* h) {
   return phases ? Route::RobustPhases : Route::RobustOneWg;
 }
 
-// Bounds of either kind are per instance: the twins of ddmpc_instance_box_law.hpp serve the handle's steps and fused loops.
+// Bounds of either kind are per instance: the BoxChannels instantiations of ddmpc_box_law.hpp serve the handle's steps and fused loops.
 static bool instance_bounds(const ddmpc_handle* h) { return !h->iumin_h.empty() || !h->iymin_h.empty(); }
 
 static bool nominal_route(Route r) { return r == Route::NominalPhases || r == Route::NominalOneWg; }
@@ -399,6 +397,17 @@ static int read_table(const DevBuf& d, size_t count, std::vector<T>* out) {
   out->resize(count);
   HIP_TRY(hipMemcpy(out->data(), d.p, count * sizeof(T), hipMemcpyDeviceToHost));
   return DDMPC_OK;
+}
+
+// The <SAFE, YB> template arguments of the bounded kernels from (DDMPC_OPT_BOX_SAFEGUARD, output bounds): f(std::bool_constant<SAFE>,
+// std::bool_constant<YB>), a generic lambda that names the instantiation and launches it.  Every bounded launch goes through here.
+template <class F>
+static void with_safe_yb(bool safe, bool yb, F&& f) {
+  if (safe) {
+    if (yb) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{});
+  } else {
+    if (yb) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{});
+  }
 }
 
 extern "C" {
@@ -1723,7 +1732,7 @@ static int launch_warm(ddmpc_handle* h, const double* up, const double* yp, doub
 
 // Route::BoxLaw (input bounds): a control step on what ddmpc_prepare kept -- the law, M for the whole box list and the table.
 // seeded (DDMPC_OPT_BOX_WARM_START = 1 only): the iteration starts from the set in d_box_seed; with the option 1 every launch
-// leaves its set there.  Per-instance bounds (instance_bounds): the twins of ddmpc_instance_box_law.hpp with the channel table;
+// leaves its set there.  Per-instance bounds (instance_bounds): the BoxChannels instantiations with the channel table;
 // DDMPC_OPT_BOX_WARM_START is not honoured there -- from the empty set, no seed read or left.
 static int launch_box_step(ddmpc_handle* h, const double* up, const double* yp, double* uo, double* cost, int32_t* status,
                            int32_t* iters, bool seeded) {
@@ -1736,32 +1745,20 @@ static int launch_box_step(ddmpc_handle* h, const double* up, const double* yp, 
   // (output bounds: the instantiations with the output components, block = max(r, nbox) rounded up to 64)
   const bool yb = !h->ymin_h.empty();
   // (DDMPC_OPT_BOX_WARM_START = 0 launches the instantiations without the seed argument: the kernels as they were)
-  auto launch = [&](auto kernel, auto... seed) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch),
-                       dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0, h->stream, h->kp,
-                       16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo,
-                       cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox,
-                       (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
-                       h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, seed...);
+  // (per-instance bounds launch the instantiations with the channel table as the trailing argument)
+  auto launch = [&](auto... extra) {
+    with_safe_yb(h->box_safeguard != 0, yb, [&](auto safe, auto ybt) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(ddmpc_box_step_kernel<safe(), ybt(), decltype(extra)...>), dim3((unsigned)h->batch),
+                         dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0, h->stream, h->kp,
+                         16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, up, yp, uo,
+                         cost, (int*)status, (int*)iters, (double*)h->d_beta.p, (signed char*)h->d_act.p, h->prep.cwl_nbox,
+                         (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                         h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, extra...);
+    });
   };
-  if (inst) {
-    const double* chb = (const double*)h->d_ibnd.p;
-    if (yb && h->box_safeguard) launch(ddmpc_instance_box_step_kernel<true, true>, chb);
-    else if (yb) launch(ddmpc_instance_box_step_kernel<false, true>, chb);
-    else if (h->box_safeguard) launch(ddmpc_instance_box_step_kernel<true, false>, chb);
-    else launch(ddmpc_instance_box_step_kernel<false, false>, chb);
-  } else if (warm) {
-    const BoxSeed seed{(signed char*)h->d_box_seed.p, seeded ? 1 : 0};
-    if (yb && h->box_safeguard) launch(ddmpc_box_step_kernel<true, true, BoxSeed>, seed);
-    else if (yb) launch(ddmpc_box_step_kernel<false, true, BoxSeed>, seed);
-    else if (h->box_safeguard) launch(ddmpc_box_step_kernel<true, false, BoxSeed>, seed);
-    else launch(ddmpc_box_step_kernel<false, false, BoxSeed>, seed);
-  } else {
-    if (yb && h->box_safeguard) launch(ddmpc_box_step_kernel<true, true>);
-    else if (yb) launch(ddmpc_box_step_kernel<false, true>);
-    else if (h->box_safeguard) launch(ddmpc_box_step_kernel<true, false>);
-    else launch(ddmpc_box_step_kernel<false, false>);
-  }
+  if (inst) launch(BoxChannels{(const double*)h->d_ibnd.p});
+  else if (warm) launch(BoxSeed{(signed char*)h->d_box_seed.p, seeded ? 1 : 0});
+  else launch();
   HIP_TRY(hipGetLastError());
   h->last.box_seed = warm;
   return DDMPC_OK;
@@ -2711,44 +2708,24 @@ static int setpoint_step_on_route(ddmpc_handle* h, const double* up, const doubl
     const Rr3Setpoint sp{h->sp_us, h->sp_ys, h->sp_su, h->sp_sy};
     return launch_rr3_solve(h, h->kp, up, yp, uo, cost, status, iters, nullptr, nullptr, false, &sp);
   }
-  if (h->setpoint_convex_law) {
-    // DDMPC_OPT_SETPOINT_CONVEX_LAW: ddmpc_setpoint_convex_step_kernel on the box list ddmpc_prepare kept -- the slack components
-    // alone (Route::Cold; no safeguard: the slack box does not cycle) or next to the bounded inputs / outputs (Route::BoxLaw)
-    const Route route = select_route(h);
+  const Route route = select_route(h);
+  if (h->setpoint_convex_law || route == Route::BoxLaw) {
+    // ddmpc_setpoint_box_step_kernel on the box list ddmpc_prepare kept.  DDMPC_OPT_SETPOINT_CONVEX_LAW: its SLACK instantiations --
+    // the slack components alone (Route::Cold; no safeguard: the slack box does not cycle) or next to the bounded inputs / outputs
     begin_solve(h, route);
     const bool yb = !h->ymin_h.empty(), safe = route == Route::BoxLaw && h->box_safeguard;
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0,
-                         h->stream, h->kp, 16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p,
-                         (const double*)h->d_sgain.p, (const int*)h->d_prep_status.p, up, yp, h->sp_us, h->sp_ys, uo, cost,
-                         (int*)status, (int*)iters, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p,
-                         (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
-                         h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
-                         (int)(h->prm.use_terminal_constraint != 0));
+    auto launch = [&](auto slack) {
+      with_safe_yb(safe, yb, [&](auto safet, auto ybt) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ddmpc_setpoint_box_step_kernel<safet(), ybt(), slack()>), dim3((unsigned)h->batch),
+                           dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0, h->stream, h->kp, 16 * h->kc.NT,
+                           h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const double*)h->d_sgain.p,
+                           (const int*)h->d_prep_status.p, up, yp, h->sp_us, h->sp_ys, uo, cost, (int*)status, (int*)iters,
+                           h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p,
+                           (double*)h->d_cwl_sg.p, h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr,
+                           (const double*)h->d_chbnd.p, (int)(h->prm.use_terminal_constraint != 0));
+      });
     };
-    if (yb && safe) launch(ddmpc_setpoint_convex_step_kernel<true, true>);
-    else if (yb) launch(ddmpc_setpoint_convex_step_kernel<false, true>);
-    else if (safe) launch(ddmpc_setpoint_convex_step_kernel<true, false>);
-    else launch(ddmpc_setpoint_convex_step_kernel<false, false>);
-    HIP_TRY(hipGetLastError());
-    return DDMPC_OK;
-  }
-  if (select_route(h) == Route::BoxLaw) {
-    begin_solve(h, Route::BoxLaw);
-    const bool yb = !h->ymin_h.empty();
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0,
-                         h->stream, h->kp, 16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p,
-                         (const double*)h->d_sgain.p, (const int*)h->d_prep_status.p, up, yp, h->sp_us, h->sp_ys, uo, cost,
-                         (int*)status, (int*)iters, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p,
-                         (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
-                         h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
-                         (int)(h->prm.use_terminal_constraint != 0));
-    };
-    if (yb && h->box_safeguard) launch(ddmpc_setpoint_box_step_kernel<true, true>);
-    else if (yb) launch(ddmpc_setpoint_box_step_kernel<false, true>);
-    else if (h->box_safeguard) launch(ddmpc_setpoint_box_step_kernel<true, false>);
-    else launch(ddmpc_setpoint_box_step_kernel<false, false>);
+    if (h->setpoint_convex_law) launch(std::true_type{}); else launch(std::false_type{});
     HIP_TRY(hipGetLastError());
     return DDMPC_OK;
   }
@@ -3123,7 +3100,7 @@ static const char* setpoint_outside_bounds(const ddmpc_handle* h, const double* 
 static int apply_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max, bool any);
 static int apply_output_bounds(ddmpc_handle* h, const double* y_min, const double* y_max, bool any);
 
-// The channel table of ddmpc_instance_box_law.hpp from the handle's bounds of both kinds: [batch][lo (m+p) | hi (m+p)], inputs
+// The channel table of ddmpc_box_law.hpp (BoxChannels) from the handle's bounds of both kinds: [batch][lo (m+p) | hi (m+p)], inputs
 // first, a shared kind broadcast, -+infinity without a bound.  Released when neither kind is per instance.  Every bounds call ends
 // here (behind its stream synchronisation: nothing in flight reads the table).
 static int upload_instance_bounds(ddmpc_handle* h) {
@@ -3634,7 +3611,7 @@ static int select_loop_path(ddmpc_handle* h, int n_mpc_step, LoopPath* path) {
 static int launch_fused_loop(ddmpc_handle* h, LoopPath path, LoopArgs a) {
   if (int rc = reserve_beta(h)) return rc;
   a.beta = (double*)h->d_beta.p; a.act = (signed char*)h->d_act.p;
-  const bool inst = path == LoopPath::FusedBox && instance_bounds(h);     // per-instance bounds: the twins, as launch_box_step
+  const bool inst = path == LoopPath::FusedBox && instance_bounds(h);     // per-instance bounds: the channel table, as launch_box_step
   const bool warm = path == LoopPath::FusedBox && h->box_warm != 0 && !inst;   // DDMPC_OPT_BOX_WARM_START, as launch_box_step
   const int seeded = (warm && box_seed_valid(h)) ? 1 : 0;
   if (warm)
@@ -3642,46 +3619,30 @@ static int launch_fused_loop(ddmpc_handle* h, LoopPath path, LoopArgs a) {
   begin_solve(h, path == LoopPath::FusedBox ? Route::BoxLaw : Route::Cold);
   const bool yb = path == LoopPath::FusedBox && !h->ymin_h.empty();
   const unsigned threads = yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r);
-  auto launch = [&](auto kernel, auto... tail) {
+  auto launch = [&](auto kernel, auto... tail) {       // (tail: what the kernel takes behind the beta / active-set workspace)
     hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(threads), 0, h->stream, h->kp, 16 * h->kc.NT,
                        h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps,
-                       a.n_mpc_step, a.x, a.up, a.yp, a.w, a.usys, a.ysys, a.stacc, a.beta, a.act, tail..., a.lwup, a.lwyp);
+                       a.n_mpc_step, a.x, a.up, a.yp, a.w, a.usys, a.ysys, a.stacc, a.beta, a.act, tail...);
   };
   const int nbox = h->prep.cwl_nbox;
   const int* tab = (const int*)h->d_cwl_tab.p;
   const double* mcol = (const double*)h->d_mcol.p;
   double* sg = (double*)h->d_cwl_sg.p;
   if (path == LoopPath::FusedAffine) {
-    launch(ddmpc_closed_loop_warm_kernel);
+    launch(ddmpc_closed_loop_warm_kernel, a.lwup, a.lwyp);
   } else if (path == LoopPath::FusedConvex) {
-    launch(ddmpc_closed_loop_convex_warm_kernel, nbox, tab, mcol, sg);
+    launch(ddmpc_closed_loop_convex_warm_kernel, nbox, tab, mcol, sg, a.lwup, a.lwyp);
   } else {    // (DDMPC_OPT_BOX_SAFEGUARD = 0 launches the instantiation without the safeguard, as launch_box_step)
     const double* bd = (const double*)h->d_box_bd.p;
     const int* ref = h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr;
-    if (inst) {                            // (the channel table follows the window of the last solve)
-      const double* chb = (const double*)h->d_ibnd.p;
-      if (yb && h->box_safeguard) launch(ddmpc_closed_loop_instance_box_kernel<true, true>, nbox, tab, bd, mcol, sg, ref, chb);
-      else if (yb) launch(ddmpc_closed_loop_instance_box_kernel<false, true>, nbox, tab, bd, mcol, sg, ref, chb);
-      else if (h->box_safeguard) launch(ddmpc_closed_loop_instance_box_kernel<true, false>, nbox, tab, bd, mcol, sg, ref, chb);
-      else launch(ddmpc_closed_loop_instance_box_kernel<false, false>, nbox, tab, bd, mcol, sg, ref, chb);
-    } else if (warm) {                     // (the seed follows the window of the last solve)
-      const BoxSeed seed{(signed char*)h->d_box_seed.p, seeded};
-      auto launch_warm = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(threads), 0, h->stream, h->kp, 16 * h->kc.NT,
-                           h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps,
-                           a.n_mpc_step, a.x, a.up, a.yp, a.w, a.usys, a.ysys, a.stacc, a.beta, a.act, nbox, tab, bd, mcol, sg, ref,
-                           a.lwup, a.lwyp, seed);
-      };
-      if (yb && h->box_safeguard) launch_warm(ddmpc_closed_loop_box_kernel<true, true, BoxSeed>);
-      else if (yb) launch_warm(ddmpc_closed_loop_box_kernel<false, true, BoxSeed>);
-      else if (h->box_safeguard) launch_warm(ddmpc_closed_loop_box_kernel<true, false, BoxSeed>);
-      else launch_warm(ddmpc_closed_loop_box_kernel<false, false, BoxSeed>);
-    } else {
-      if (yb && h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true, true>, nbox, tab, bd, mcol, sg, ref);
-      else if (yb) launch(ddmpc_closed_loop_box_kernel<false, true>, nbox, tab, bd, mcol, sg, ref);
-      else if (h->box_safeguard) launch(ddmpc_closed_loop_box_kernel<true, false>, nbox, tab, bd, mcol, sg, ref);
-      else launch(ddmpc_closed_loop_box_kernel<false, false>, nbox, tab, bd, mcol, sg, ref);
-    }
+    auto launch_box = [&](auto... extra) {   // (the seed or the channel table follows the window of the last solve)
+      with_safe_yb(h->box_safeguard != 0, yb, [&](auto safe, auto ybt) {
+        launch(ddmpc_closed_loop_box_kernel<safe(), ybt(), decltype(extra)...>, nbox, tab, bd, mcol, sg, ref, a.lwup, a.lwyp, extra...);
+      });
+    };
+    if (inst) launch_box(BoxChannels{(const double*)h->d_ibnd.p});
+    else if (warm) launch_box(BoxSeed{(signed char*)h->d_box_seed.p, seeded});
+    else launch_box();
     h->last.box_seed = warm;
   }
   HIP_TRY(hipGetLastError());
@@ -3790,43 +3751,24 @@ static int copy_loop_outputs(ddmpc_handle* h, int mem, const LoopBytes& nb, cons
 // the device).  The loop's last solve leaves nothing ddmpc_get_solution could reconstruct.
 // DDMPC_OPT_SETPOINT_BOX_LAW on a handle with finite bounds (Route::BoxLaw): ddmpc_closed_loop_setpoint_box_kernel, from the empty set.
 static int launch_setpoint_loop(ddmpc_handle* h, const LoopArgs& a, const double* u_ref, const double* y_ref) {
-  if (h->setpoint_convex_law) {            // DDMPC_OPT_SETPOINT_CONVEX_LAW: slack-only (Route::Cold) or bounded (Route::BoxLaw), as setpoint_step_on_route
-    const Route route = select_route(h);
+  const Route route = select_route(h);
+  if (h->setpoint_convex_law || route == Route::BoxLaw) {
+    // (DDMPC_OPT_SETPOINT_CONVEX_LAW: the SLACK instantiations, slack-only (Route::Cold) or bounded (Route::BoxLaw), as setpoint_step_on_route)
     begin_solve(h, route);
     const bool yb = !h->ymin_h.empty(), safe = route == Route::BoxLaw && h->box_safeguard;
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0,
-                         h->stream, h->kp, 16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p,
-                         (const double*)h->d_sgain.p, (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps, a.n_mpc_step, a.x, a.up,
-                         a.yp, a.w, u_ref, y_ref, a.usys, a.ysys, a.stacc, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,
-                         (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
-                         h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
-                         (int)(h->prm.use_terminal_constraint != 0));
+    auto launch = [&](auto slack) {
+      with_safe_yb(safe, yb, [&](auto safet, auto ybt) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ddmpc_closed_loop_setpoint_box_kernel<safet(), ybt(), slack()>), dim3((unsigned)h->batch),
+                           dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0, h->stream, h->kp, 16 * h->kc.NT,
+                           h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const double*)h->d_sgain.p,
+                           (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps, a.n_mpc_step, a.x, a.up, a.yp, a.w, u_ref, y_ref,
+                           a.usys, a.ysys, a.stacc, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p,
+                           (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
+                           h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
+                           (int)(h->prm.use_terminal_constraint != 0));
+      });
     };
-    if (yb && safe) launch(ddmpc_closed_loop_setpoint_convex_kernel<true, true>);
-    else if (yb) launch(ddmpc_closed_loop_setpoint_convex_kernel<false, true>);
-    else if (safe) launch(ddmpc_closed_loop_setpoint_convex_kernel<true, false>);
-    else launch(ddmpc_closed_loop_setpoint_convex_kernel<false, false>);
-    HIP_TRY(hipGetLastError());
-    h->last.setpoint_call = true;
-    return DDMPC_OK;
-  }
-  if (select_route(h) == Route::BoxLaw) {
-    begin_solve(h, Route::BoxLaw);
-    const bool yb = !h->ymin_h.empty();
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)h->batch), dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0,
-                         h->stream, h->kp, 16 * h->kc.NT, h->prm.n * h->kp.nch, (const double*)h->d_gain.p,
-                         (const double*)h->d_sgain.p, (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps, a.n_mpc_step, a.x, a.up,
-                         a.yp, a.w, u_ref, y_ref, a.usys, a.ysys, a.stacc, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p,
-                         (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
-                         h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
-                         (int)(h->prm.use_terminal_constraint != 0));
-    };
-    if (yb && h->box_safeguard) launch(ddmpc_closed_loop_setpoint_box_kernel<true, true>);
-    else if (yb) launch(ddmpc_closed_loop_setpoint_box_kernel<false, true>);
-    else if (h->box_safeguard) launch(ddmpc_closed_loop_setpoint_box_kernel<true, false>);
-    else launch(ddmpc_closed_loop_setpoint_box_kernel<false, false>);
+    if (h->setpoint_convex_law) launch(std::true_type{}); else launch(std::false_type{});
     HIP_TRY(hipGetLastError());
     h->last.setpoint_call = true;
     return DDMPC_OK;
@@ -3930,6 +3872,7 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
   }
   if (u_ref) {
     // DDMPC_OPT_SETPOINT_LAW: one fused launch, no per-step fall-back (DDMPC_OPT_CLOSED_LOOP_PATH / _GRAPH are not looked at)
+    // (the names are labels of the path: "..._setpoint_convex_kernel" is the SLACK instantiation of ddmpc_closed_loop_setpoint_box_kernel)
     h->loop_kernel = h->setpoint_convex_law ? "ddmpc_closed_loop_setpoint_convex_kernel"
                      : select_route(h) == Route::BoxLaw ? "ddmpc_closed_loop_setpoint_box_kernel" : "ddmpc_closed_loop_setpoint_kernel";
     if ((rc = launch_setpoint_loop(h, a, u_ref, y_ref))) return rc;
@@ -3937,6 +3880,7 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
   }
   LoopPath path;
   if ((rc = select_loop_path(h, n_mpc_step, &path))) return rc;
+  // ("ddmpc_closed_loop_instance_box_kernel" labels the channel-bounds (BoxChannels) instantiation of ddmpc_closed_loop_box_kernel)
   h->loop_kernel = (path == LoopPath::FusedBox && instance_bounds(h)) ? "ddmpc_closed_loop_instance_box_kernel" : kLoopKernel[(int)path];
   if ((rc = fused(path) ? launch_fused_loop(h, path, a) : run_step_loop(h, path, a, nb))) return rc;
   end_solve(h, a.lwup, a.lwyp);    // (the last solve's window: the per-step cold path re-solves there, the other paths wrote its beta)

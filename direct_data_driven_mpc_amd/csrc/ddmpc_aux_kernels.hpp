@@ -34,7 +34,7 @@ __global__ void ddmpc_hankel_kernel(const double* __restrict__ X, double* __rest
 // ddmpc_set_input_bounds; a free input row in the active set is held at its bound (t = bound, D = 0).  `ybnd` (null without
 // output bounds): [y_min (p) | y_max (p)] of ddmpc_set_output_bounds; the workspace then holds sa + 4 say per row (sa: slack or
 // input, say: output), and a K_WPRED row with say != 0 has ybar = its bound exactly, sigma = +- c eps_max or -lam beta / lamb_sigma.
-// `bnd_stride` (0: the shared bounds above): per-instance bounds (ddmpc_instance_box_law.hpp) -- ubnd is the channel table
+// `bnd_stride` (0: the shared bounds above): per-instance bounds (ddmpc_box_law.hpp, BoxChannels) -- ubnd is the channel table
 // [batch][lo (nch) | hi (nch)] and ybnd the same table moved on by m, bnd_stride = 2 nch doubles from one instance to the next.
 // --------------------------------------------------------------------------
 __global__ void ddmpc_reconstruct_kernel(KParams P, int RPs, int what, const double* __restrict__ u_d,

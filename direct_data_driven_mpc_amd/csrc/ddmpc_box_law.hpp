@@ -26,6 +26,21 @@
 // instantiations without YB never look beyond [box_rho | box_of]: col(s) = s there.
 // The k x k system lives in LDS up to CWL_KLDS components and in the instance's slice of `sg` beyond; M = K0^-1 E_box is
 // nbox * r doubles per instance (122 KB at L = 30, n = 4, m = p = 2, CONVEX, both channels bounded: 0.5 GB at 4096 instances).
+//
+// Per-instance bounds (ddmpc_set_instance_input_bounds, ddmpc_set_instance_output_bounds; slack NONE or the CONVEX slack box):
+// the instantiations of the two kernels below with a BoxChannels element, whose bounds come from a per-instance channel table
+// instead of the shared [lo | hi] columns of `bd`.  M = K0^-1 E_box, the law and the box list depend on WHICH rows are boxed,
+// not on the bound values: the list is the union over the batch (a channel is listed when any instance has a finite bound on
+// it) and stays shared.  The bound values enter the solve through BoxTab::lo / BoxTab::hi only -- the violation test, the
+// shifts, the safeguard's ratios and the output stage's "held at its bound exactly".  The kernels keep blo[s] / bhi[s] in LDS by
+// boxed component, filled once per launch (the loop kernel: once per instance, not per solve), and point their copy of the
+// table at them: box_iterate, box_solve_set, box_safeguard, box_beta, box_component and box_component_y are used as they stand.
+// An instance whose own bound on a listed component is infinite never activates it (hat > +inf and hat < -inf are false), so
+// its shift is never formed.
+//     chb [batch][lo (nch) | hi (nch)], inputs first, -+infinity where the instance has no bound on the channel;
+//     a slack component (CONVEX) keeps -+ c eps_max from the shared `bd`; an input or output component takes its channel's entry.
+// With the channel table the iteration always starts from the empty set (no instantiation takes a seed and a table).  beta and
+// the signed active set are written as with shared bounds: ddmpc_get_solution reconstructs with the same channel table.
 #pragma once
 #include <type_traits>
 
@@ -416,14 +431,39 @@ __device__ int box_iterate_seeded(const KParams& P, const BoxTabT<YB>& T, const 
   return st;
 }
 
-// The seed as a kernel argument.  The box kernels take it as a parameter pack: empty in the instantiations launched with the
-// option 0, whose signature, kernel arguments and code are then those of the kernels without the option; one BoxSeed in the WARM ones.
+// The seed, or the per-instance channel table, as a kernel argument.  The box kernels take it as a trailing parameter pack: empty
+// in the instantiations launched with shared bounds and the option 0, whose signature, kernel arguments and code are then those of
+// the kernels without either; one BoxSeed in the WARM ones, one BoxChannels in the INST ones (never both: DDMPC_OPT_BOX_WARM_START
+// is not honoured on a handle with per-instance bounds).
 struct BoxSeed {
   signed char* ws;            // [batch][nbox]: the signed set every instance's last solve ended with; written by every WARM launch
   int use;                    // 0: `ws` is not read (nothing valid in it) and every instance starts from the empty set
 };
+struct BoxChannels {
+  const double* chb;          // [batch][lo (nch) | hi (nch)]: the bounds of every instance by channel (see the head of this file)
+};
 __device__ __forceinline__ BoxSeed box_seed_of() { return BoxSeed{nullptr, 0}; }
 __device__ __forceinline__ BoxSeed box_seed_of(BoxSeed s) { return s; }
+__device__ __forceinline__ BoxSeed box_seed_of(BoxChannels) { return BoxSeed{nullptr, 0}; }
+__device__ __forceinline__ BoxChannels box_channels_of() { return BoxChannels{nullptr}; }
+__device__ __forceinline__ BoxChannels box_channels_of(BoxSeed) { return BoxChannels{nullptr}; }
+__device__ __forceinline__ BoxChannels box_channels_of(BoxChannels c) { return c; }
+
+// blo / bhi of one instance by the whole workgroup (no barrier after it).  T still points at the shared `bd` here.  Component j
+// on row rho: an input row (rho mod nch < m) carries an input component; on an output row the output component is the one
+// T.ofy names (YB), any other is the slack of a CONVEX handle.
+template <bool YB>
+__device__ __forceinline__ void instance_box_fill(const KParams& P, const BoxTabT<YB>& T, const double* __restrict__ cb,
+                                                  double* blo, double* bhi) {
+  const int nch = P.nch;
+  for (int j = threadIdx.x; j < T.nbox; j += blockDim.x) {
+    const int rho = T.rho[j], ch = rho % nch;
+    bool chan = ch < P.m;
+    if constexpr (YB) chan = chan || T.ofy[rho] == j;
+    blo[j] = chan ? cb[ch] : T.lo[j];
+    bhi[j] = chan ? cb[nch + ch] : T.hi[j];
+  }
+}
 
 // Output stage of one component with its active flag (j: its place in the box list, or -1): cwl_component, and an input row
 // held at a bound is that bound exactly (t = bound, D1 = 0); its cost term is the K_UFREE one.
@@ -473,30 +513,41 @@ __device__ __forceinline__ double box_component_y(const KParams& P, int RPs, con
 // its solves.  The host launches <false> when the option is 0: that instantiation is the kernel as it was.
 // YB (ddmpc_set_output_bounds): the table with the output components; block = max(r, nbox) rounded up to 64; the active-set
 // workspace holds sa + 4 say per row (sa: slack or input, say: output).  Without YB the kernel is the one it was.
-// Seed = BoxSeed (DDMPC_OPT_BOX_WARM_START = 1, "WARM"): box_iterate_seeded from the set in seed.ws when seed.use, and the set this
+// Extra = BoxSeed (DDMPC_OPT_BOX_WARM_START = 1, "WARM"): box_iterate_seeded from the set in seed.ws when seed.use, and the set this
 // solve ended with goes there (empty when nothing was iterated or the solve failed).  The host launches the empty pack when the
 // option is 0: that instantiation is the kernel as it was.
-template <bool SAFE, bool YB, class... Seed>
+// Extra = BoxChannels (per-instance bounds, "INST"): the same stages, statuses and iters with the instance's own bounds -- blo, bhi
+// [WARM_MAX_R] in LDS (nbox <= WARM_MAX_R is checked by ddmpc_prepare), filled before the law, behind the table's lo / hi.
+template <bool SAFE, bool YB, class... Extra>
 __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                       const int* __restrict__ prep_status, const double* __restrict__ u_past,
                                       const double* __restrict__ y_past, double* __restrict__ u_opt, double* __restrict__ cost,
                                       int* __restrict__ status, int* __restrict__ iters, double* __restrict__ beta_ws,
                                       signed char* __restrict__ act_ws, int nbox, const int* __restrict__ tab,
                                       const double* __restrict__ bd, const double* __restrict__ Mcol, double* __restrict__ sg,
-                                      const int* __restrict__ refined, Seed... seed_arg) {
-  constexpr bool WARM = sizeof...(Seed) != 0;
-  [[maybe_unused]] const BoxSeed seed = box_seed_of(seed_arg...);
+                                      const int* __restrict__ refined, Extra... extra) {
+  constexpr bool WARM = (std::is_same_v<Extra, BoxSeed> || ...);
+  constexpr bool INST = (std::is_same_v<Extra, BoxChannels> || ...);
+  [[maybe_unused]] const BoxSeed seed = box_seed_of(extra...);
+  [[maybe_unused]] const BoxChannels chan = box_channels_of(extra...);
   __shared__ double pv[WARM_MAX_NF];
   __shared__ double red[32];
   __shared__ double bsh[WARM_MAX_R];
   __shared__ CwlLds s;
   const int r = P.r;
-  const BoxTabT<YB> T = box_table<YB>(nbox, tab, bd, r);
+  BoxTabT<YB> T = box_table<YB>(nbox, tab, bd, r);
   const long long b = blockIdx.x;
   const int tid = threadIdx.x, nrhs = nf + 1;
   const int nyp = nf - P.npu;
   for (int f = tid; f < nf; f += blockDim.x)
     pv[f] = (f < P.npu) ? u_past[b * P.npu + f] : y_past[b * nyp + (f - P.npu)];
+  if constexpr (INST) {
+    __shared__ double blo[WARM_MAX_R];                // the bounds of this instance, by boxed component
+    __shared__ double bhi[WARM_MAX_R];
+    instance_box_fill<YB>(P, T, chan.chb + b * (long long)(2 * P.nch), blo, bhi);
+    T.lo = blo;
+    T.hi = bhi;
+  }
   __syncthreads();
   const double* g = gain + b * (long long)nrhs * r;
   int viol = 0;
@@ -598,9 +649,10 @@ __global__ void ddmpc_box_step_kernel(KParams P, int RPs, int nf, const double* 
 // (same fixed-size arrays and the same checks of ddmpc_closed_loop behind them).  Per solve the law on the boxed rows and the
 // n_mpc_step * m input rows in use, the iteration of ddmpc_box_step_kernel, the M_A ev correction of those rows, then the
 // plant / FIFO steps of ddmpc_plant_kernel; everything on the last solve.  SAFE: as in ddmpc_box_step_kernel; an instance the
-// safeguard finishes carries on with the loop.  YB: as in ddmpc_box_step_kernel.  Seed = BoxSeed: the set stays in s.act from one
+// safeguard finishes carries on with the loop.  YB: as in ddmpc_box_step_kernel.  Extra = BoxSeed: the set stays in s.act from one
 // solve of the loop to the next; the first solve takes the handle's seed when seed.use, the last one leaves its set in seed.ws.
-template <bool SAFE, bool YB, class... Seed>
+// Extra = BoxChannels: as in ddmpc_box_step_kernel; blo / bhi are filled once, before the first solve.
+template <bool SAFE, bool YB, class... Extra>
 __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                              const int* __restrict__ prep_status, int ns, const double* __restrict__ pl,
                                              int n_steps, int n_mpc_step, double* __restrict__ x, double* __restrict__ u_past,
@@ -609,16 +661,18 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
                                              signed char* __restrict__ act_ws, int nbox, const int* __restrict__ tab,
                                              const double* __restrict__ bd, const double* __restrict__ Mcol, double* __restrict__ sg,
                                              const int* __restrict__ refined, double* __restrict__ lw_up, double* __restrict__ lw_yp,
-                                             Seed... seed_arg) {
-  constexpr bool WARM = sizeof...(Seed) != 0;
-  [[maybe_unused]] const BoxSeed seed = box_seed_of(seed_arg...);
+                                             Extra... extra) {
+  constexpr bool WARM = (std::is_same_v<Extra, BoxSeed> || ...);
+  constexpr bool INST = (std::is_same_v<Extra, BoxChannels> || ...);
+  [[maybe_unused]] const BoxSeed seed = box_seed_of(extra...);
+  [[maybe_unused]] const BoxChannels chan = box_channels_of(extra...);
   __shared__ double pv[WARM_MAX_NF];
   __shared__ double uo[WARM_MAX_NF];      // the first n_mpc_step*m entries of optimal_u
   __shared__ double xs[16], xn[16];       // (ns <= 16 is checked by ddmpc_closed_loop)
   __shared__ double bsh[WARM_MAX_R];
   __shared__ CwlLds s;
   const int r = P.r;
-  const BoxTabT<YB> T = box_table<YB>(nbox, tab, bd, r);
+  BoxTabT<YB> T = box_table<YB>(nbox, tab, bd, r);
   const long long b = blockIdx.x;
   const int tid = threadIdx.x, nrhs = nf + 1, m = P.m, p = P.p;
   const int n = P.npu / m, nyp = nf - P.npu;
@@ -629,6 +683,13 @@ __global__ void ddmpc_closed_loop_box_kernel(KParams P, int RPs, int nf, const d
   for (int f = tid; f < nf; f += blockDim.x)
     pv[f] = (f < P.npu) ? u_past[b * P.npu + f] : y_past[b * nyp + (f - P.npu)];
   if (tid < ns) xs[tid] = x[b * ns + tid];
+  if constexpr (INST) {                               // (visible behind the barrier that opens the first solve)
+    __shared__ double blo[WARM_MAX_R];                // the bounds of this instance, by boxed component
+    __shared__ double bhi[WARM_MAX_R];
+    instance_box_fill<YB>(P, T, chan.chb + b * (long long)(2 * P.nch), blo, bhi);
+    T.lo = blo;
+    T.hi = bhi;
+  }
   const int st0 = prep_status[b];
   const bool refd = refined != nullptr && refined[b] != 0;
   const double nanv = __longlong_as_double(0x7ff8000000000000LL);

@@ -16,7 +16,20 @@
 // inputs / outputs are fixed to it: the per-instance form of the DDMPC_ERR_INVALID of ddmpc_set_input_bounds / _set_setpoints).
 // The iteration always starts from the empty set (no DDMPC_OPT_BOX_WARM_START), and beta / the active set are not written
 // (ddmpc_get_solution reconstructs with the shared table and is refused after these kernels).
-// Included by the API translation unit only; nothing here is launched by a handle with the option 0.
+//
+// DDMPC_OPT_SETPOINT_CONVEX_LAW (the SLACK instantiations of the two kernels): the same on a ROBUST handle with the CONVEX slack
+// box, slack-only or next to input / output bounds.  The one thing the slack box changes: the box list holds components of two kinds,
+//   * input / output components, whose offset is the instance's setpoint of their channel, a_s = s_b[rho_s mod (m+p)];
+//   * slack components, sigma_s = c beta_rho with c = -lam / lamb_sigma inside +- c_param eps_max: their offset is 0 whatever the
+//     setpoint (setpoint_convex_offset).  On a K_WPRED / K_WTERM row the slack component is T.of[rho]; the output component of
+//     the same row, if the channel is bounded, is T.ofy[rho].
+// A slack-only handle runs the same table-driven kernels (the instantiations without YB) on a box list of slack components alone
+// -- ddmpc_prepare forms that list, its [a | c | lo | hi | 1/d] table and M for it whether or not DDMPC_OPT_CONVEX_WARM_LAW is on
+// --, not setpoint twins of ddmpc_warm_convex_step_kernel: box_iterate with such a table IS cwl_iterate (same rule, same count of
+// solves), and one pair of kernels serves every CONVEX handle.  The channel bounds `chb` are +-infinity there, so the only
+// per-instance refusal left is the non-finite setpoint.  The output stage needs nothing more: the box_component /
+// box_component_y overloads below carry the K_WPRED / K_WTERM branches with the slack flag and the K_WINT rows.
+// Included by the API translation unit only; nothing here is launched by a handle with both options 0.
 #pragma once
 #include "ddmpc_box_law.hpp"
 #include "ddmpc_setpoint_law.hpp"
@@ -71,6 +84,16 @@ __device__ __forceinline__ int setpoint_box_refusal(int nch, int tec, const doub
   return bad ? 4 : ((tec && out) ? 2 : 0);
 }
 
+// The offset a_j of boxed component j of a CONVEX handle at the setpoint [us (m) ; ys (p)] of the instance: 0 for a slack component.
+__device__ __forceinline__ double setpoint_convex_offset(const KParams& P, int RPs, const BoxTab& T, int j, const double* us,
+                                                         const double* ys) {
+  const int rho = T.rho[j];
+  const int kind = P.tabi[0 * RPs + rho];
+  if ((kind == K_WPRED || kind == K_WTERM) && T.of[rho] == j) return 0.0;
+  const int c = rho % P.nch;
+  return (c < P.m) ? us[c] : ys[c - P.m];
+}
+
 // One control step of a bounded handle with a setpoint per instance: grid = batch, block = r (YB: max(r, nbox)) rounded up to 64,
 // the geometry of ddmpc_box_step_kernel.  Four stages: the law with S against the instance's setpoint; the violation test with
 // the instance's offsets; the iteration of ddmpc_box_step_kernel on M (same rule, same max_iter cap, status 4 at the cap or on a
@@ -79,7 +102,9 @@ __device__ __forceinline__ int setpoint_box_refusal(int nch, int tec, const doub
 // u_s [batch][m], y_s [batch][p]; everything else as in ddmpc_box_step_kernel, whose `bd` serves [c | lo | hi | 1/d] here.
 // Fixed-size arrays: pv, sv [WARM_MAX_NF] (nf <= WARM_MAX_NF, m + p <= nf), bsh, as [WARM_MAX_R] (r <= 271, nbox <= WARM_MAX_R:
 // checked by ddmpc_prepare).
-template <bool SAFE, bool YB>
+// SLACK (DDMPC_OPT_SETPOINT_CONVEX_LAW): the offsets of a CONVEX handle's box list (setpoint_convex_offset); nothing else differs.
+// SAFE is then launched on bounded handles only.
+template <bool SAFE, bool YB, bool SLACK = false>
 __global__ void ddmpc_setpoint_box_step_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                                const double* __restrict__ sgain, const int* __restrict__ prep_status,
                                                const double* __restrict__ u_past, const double* __restrict__ y_past,
@@ -106,8 +131,12 @@ __global__ void ddmpc_setpoint_box_step_kernel(KParams P, int RPs, int nf, const
   for (int c = tid; c < nch; c += blockDim.x)
     sv[c] = (c < P.m) ? u_s[b * P.m + c] : y_s[b * P.p + (c - P.m)];
   for (int j = tid; j < nbox; j += blockDim.x) {
-    const int c = T.rho[j] % nch;
-    as[j] = (c < P.m) ? u_s[b * P.m + c] : y_s[b * P.p + (c - P.m)];
+    if constexpr (SLACK) {
+      as[j] = setpoint_convex_offset(P, RPs, T, j, u_s + b * P.m, y_s + b * P.p);
+    } else {
+      const int c = T.rho[j] % nch;
+      as[j] = (c < P.m) ? u_s[b * P.m + c] : y_s[b * P.p + (c - P.m)];
+    }
   }
   __syncthreads();
   const int refuse = setpoint_box_refusal(nch, tec, sv, chb);
@@ -199,8 +228,8 @@ __global__ void ddmpc_setpoint_box_step_kernel(KParams P, int RPs, int nf, const
 // outside its channel's bounds under the terminal constraint.  A stopped instance makes no further solves.  SAFE, YB: as in
 // ddmpc_setpoint_box_step_kernel; an instance the safeguard finishes carries on.  Nothing is kept for ddmpc_get_solution.
 // Fixed-size arrays as in ddmpc_closed_loop_box_kernel plus sv [WARM_MAX_NF] and as [WARM_MAX_R]; ddmpc_closed_loop_setpoints
-// checks n_mpc_step * m <= WARM_MAX_NF and ns <= 16.
-template <bool SAFE, bool YB>
+// checks n_mpc_step * m <= WARM_MAX_NF and ns <= 16.  SLACK: as in ddmpc_setpoint_box_step_kernel.
+template <bool SAFE, bool YB, bool SLACK = false>
 __global__ void ddmpc_closed_loop_setpoint_box_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                                       const double* __restrict__ sgain, const int* __restrict__ prep_status, int ns,
                                                       const double* __restrict__ pl, int n_steps, int n_mpc_step,
@@ -253,8 +282,12 @@ __global__ void ddmpc_closed_loop_setpoint_box_kernel(KParams P, int RPs, int nf
     if (stc <= 1) {
       for (int c = tid; c < nch; c += blockDim.x) sv[c] = (c < m) ? ur[c] : yr[c - m];
       for (int j = tid; j < nbox; j += blockDim.x) {
-        const int c = T.rho[j] % nch;
-        as[j] = (c < m) ? ur[c] : yr[c - m];
+        if constexpr (SLACK) {
+          as[j] = setpoint_convex_offset(P, RPs, T, j, ur, yr);
+        } else {
+          const int c = T.rho[j] % nch;
+          as[j] = (c < m) ? ur[c] : yr[c - m];
+        }
       }
     }
     __syncthreads();                                  // the setpoint, the offsets and the window of the last plant steps visible; bsh, uo free

@@ -346,8 +346,9 @@ extern "C" {
                                          M = K0^-1 E_box, whether or not DDMPC_OPT_CONVEX_WARM_LAW is on: L p r doubles per instance
                                          (65 KB at L = 30, n = 4, m = p = 2: 0.27 GB at 4096 instances; an allocation failure is
                                          DDMPC_ERR_HIP); a bounded handle has them already.  ddmpc_step_setpoints is one launch of
-                                         "ddmpc_setpoint_convex_step_kernel", ddmpc_closed_loop_setpoints one fused launch of
-                                         "ddmpc_closed_loop_setpoint_convex_kernel" (n_mpc_step * m > 256: DDMPC_ERR_UNSUPPORTED):
+                                         ddmpc_setpoint_box_step_kernel, ddmpc_closed_loop_setpoints one fused launch of
+                                         ddmpc_closed_loop_setpoint_box_kernel, each in its slack-box instantiation (the loop is
+                                         labelled "ddmpc_closed_loop_setpoint_convex_kernel"; n_mpc_step * m > 256: DDMPC_ERR_UNSUPPORTED):
                                          the primal-dual iteration of ddmpc_step on the law, S and M -- same rule, max_iter cap,
                                          statuses and count of `iters`; DDMPC_OPT_BOX_SAFEGUARD is honoured on bounded handles.  Per
                                          instance the setpoint enters the law, the offsets of the input and output components (a
@@ -667,8 +668,9 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
  *     rows, also with DDMPC_OPT_LARGE_BOUNDS = 1 (the phase kernels read the shared bounds); a handle with
  *     DDMPC_OPT_SETPOINT_BOX_LAW or DDMPC_OPT_SETPOINT_CONVEX_LAW on -- in the reverse order ddmpc_set_option refuses those two
  *     on a handle that carries per-instance bounds of either kind.
- * How it is served: Route::BoxLaw as under shared bounds, by twins of its two kernels that stage the instance's bounds in LDS
- * (ddmpc_instance_box_law.hpp; the fused loop is "ddmpc_closed_loop_instance_box_kernel") -- ddmpc_solve with the cold contract
+ * How it is served: Route::BoxLaw as under shared bounds, by the channel-bounds instantiations of its two kernels, which stage
+ * the instance's bounds in LDS (ddmpc_box_law.hpp; the fused loop is labelled "ddmpc_closed_loop_instance_box_kernel": the
+ * name is the label of the path, the kernel is that instantiation of ddmpc_closed_loop_box_kernel) -- ddmpc_solve with the cold contract
  * and a preparation of the call's own, ddmpc_prepare + ddmpc_step (bit-equal to ddmpc_solve), ddmpc_closed_loop fused and per
  * step, ddmpc_get_solution (an active input equals ITS INSTANCE's bound exactly).  Statuses, `iters`, the max_iter cap and
  * optimal_inaccurate on refined laws are those of the shared-bounds kernels; DDMPC_OPT_BOX_SAFEGUARD applies.
@@ -812,7 +814,10 @@ const char* ddmpc_kernel_name(ddmpc_handle* h);
  * "ddmpc_closed_loop_convex_warm_kernel" / "ddmpc_closed_loop_box_kernel" (input bounds) when the whole loop ran fused in one launch, "ddmpc_plant_kernel" when it ran
  * per step (DDMPC_PATH_COLD, shapes beyond the fused loops' bounds, NOMINAL instances without a law, laws taken from
  * refining solves under DDMPC_OPT_CONVEX_WARM_LAW, handles beyond 271 rows -- ddmpc_closed_loop_setpoints included there); "ddmpc_closed_loop_setpoint_kernel" /
- * "ddmpc_closed_loop_setpoint_box_kernel" / "ddmpc_closed_loop_setpoint_convex_kernel" after ddmpc_closed_loop_setpoints; "" before the first loop.  Read-only. */
+ * "ddmpc_closed_loop_setpoint_box_kernel" / "ddmpc_closed_loop_setpoint_convex_kernel" after ddmpc_closed_loop_setpoints; "" before the first loop.
+ * The names are labels of the path taken: "ddmpc_closed_loop_instance_box_kernel" (per-instance bounds) is the channel-bounds
+ * instantiation of ddmpc_closed_loop_box_kernel, "ddmpc_closed_loop_setpoint_convex_kernel" the slack-box instantiation of
+ * ddmpc_closed_loop_setpoint_box_kernel.  Read-only. */
 const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h);
 
 /* Diagnostics only: in-kernel phase stamps (shader-clock ticks) of the next solves.

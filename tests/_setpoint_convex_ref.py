@@ -1,5 +1,5 @@
 """Cases, references and a numpy model for DDMPC_OPT_SETPOINT_CONVEX_LAW: per-instance, per-step setpoints under the CONVEX slack
-box, slack-only or next to input / output bounds (csrc/ddmpc_setpoint_convex_law.hpp).
+box, slack-only or next to input / output bounds (the SLACK instantiations of csrc/ddmpc_setpoint_box_law.hpp).
 
 A helper, not a test.  The references are `_setpoint_box_ref.solve` / `_setpoint_box_ref.schedule_loop` with a CONVEX spec: their
 union box holds the slack components next to the bounded inputs and outputs, and the slack components alone without bounds.

@@ -27,7 +27,8 @@ the box acting):
   test_small_safeguard                               ddmpc_box_step_kernel<1, 0> and <1, 1>: iters > max_iter on the capped rows
   test_small_warm_start                              the seeded instantiation: iters of the second step = the seeded reference's
   test_small_fused_loop                              ddmpc_closed_loop_box_kernel (name asserted)
-  test_small_instance_bounds                         ddmpc_instance_box_step_kernel; ddmpc_closed_loop_instance_box_kernel (name)
+  test_small_instance_bounds                         the channel-table (BoxChannels) instantiations of ddmpc_box_step_kernel and of
+                                                     ddmpc_closed_loop_box_kernel (label "ddmpc_closed_loop_instance_box_kernel" asserted)
   test_small_m_ne_p                                  ddmpc_box_step_kernel<0, 1> and ddmpc_closed_loop_box_kernel (name) at 45 rows
   test_small_zero_weight_next_to_a_box               the same kernels with 1e25 on the diagonal of K0 next to the box
   test_large_solve_step_and_solution                 rr3_solve_box_kernel<REFINE_PASS>, both values (route record: phases)

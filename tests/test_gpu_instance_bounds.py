@@ -1,5 +1,22 @@
 """Per-instance input and output bounds (ddmpc_set_instance_input_bounds / ddmpc_set_instance_output_bounds) on Route::BoxLaw:
-the twins of the box kernels that stage every instance's own bounds in LDS (csrc/ddmpc_instance_box_law.hpp).
+the channel-table (BoxChannels) instantiations of the two box kernels, which stage every instance's own bounds in LDS
+(csrc/ddmpc_box_law.hpp).  "ddmpc_closed_loop_instance_box_kernel" below is the label ddmpc_closed_loop_kernel_name gives that path.
+
+The eight instantiations and the tests that reach them (step = ddmpc_box_step_kernel<SAFE, YB, BoxChannels>, loop =
+ddmpc_closed_loop_box_kernel<SAFE, YB, BoxChannels>; SAFE: DDMPC_OPT_BOX_SAFEGUARD, YB: output bounds on the handle):
+  step <0, 0>  test_solve_and_step_against_every_instances_own_reference[A], test_one_hard_row_leaves_its_neighbours_bit_equal,
+               test_uniform_rows_are_bit_equal_to_the_shared_call[u02]
+  step <1, 0>  test_one_hard_row_leaves_its_neighbours_bit_equal (the safeguard finishes row 7), test_uniform_rows...[u02]
+  step <0, 1>  test_solve_and_step_against_every_instances_own_reference[B, C], test_channel_indexing_on_a_plant_with_m_ne_p,
+               test_one_kind_per_instance_and_the_other_shared, test_uniform_rows...[u+y]
+  step <1, 1>  test_uniform_rows_are_bit_equal_to_the_shared_call[u+y]
+  loop <0, 0>  test_fused_loop_against_the_cold_path_and_the_reference, test_uniform_rows...[u02]
+  loop <1, 0>  test_uniform_rows_are_bit_equal_to_the_shared_call[u02]
+  loop <0, 1>  test_no_read_of_the_trajectories_after_prepare, test_the_warm_start_option_is_accepted_and_not_honoured,
+               test_uniform_rows...[u+y]
+  loop <1, 1>  test_uniform_rows_are_bit_equal_to_the_shared_call[u+y]
+(test_uniform_rows... runs solve, step and the fused loop with the safeguard off and on, bit for bit against the shared-bounds
+instantiations, which tests/test_gpu_box_safeguard.py and tests/test_gpu_output_bounds.py hold against their references.)
 
 Fixture and boxes: tests/_instance_bounds_cases.py (four-tank, L = 30, n = 4, N = 400, 32 instances, seeds 500 .. 531, data-tail
 windows; boxes A, B, C; modes `none` and `convex-tec`).  Every instance is compared with the full-space reference of

@@ -1,6 +1,6 @@
 """DDMPC_OPT_SETPOINT_CONVEX_LAW: per-instance, per-step setpoints under the CONVEX slack box, slack-only and next to input /
-output bounds (ddmpc_step_setpoints, ddmpc_closed_loop_setpoints, ddmpc_get_setpoint_gain; kernels in
-csrc/ddmpc_setpoint_convex_law.hpp).
+output bounds (ddmpc_step_setpoints, ddmpc_closed_loop_setpoints, ddmpc_get_setpoint_gain; kernels: the
+SLACK instantiations of csrc/ddmpc_setpoint_box_law.hpp; "ddmpc_closed_loop_setpoint_convex_kernel" is the label of their fused loop).
 
 Four-tank, L = 30, n = 4, N = 400 (136 rows), batch 8; data, windows and setpoints of `_setpoint_box_ref.tank()`.  References: the
 full-space bounded solve and the schedule loop of tests/_setpoint_box_ref.py with a CONVEX spec (tests/_setpoint_convex_ref.py).

@@ -1,8 +1,8 @@
 """Dev timing (GPU): what per-instance bounds cost -- ddmpc_step and the fused 101-step closed loop at 4096 four-tank controllers
 (L = 30, 136 rows, CONVEX slack box, data-tail windows) with the input boxes [-4, 6] (few active components) and [0, 2] (k > 16)
   * on a handle with the bounds shared by the batch (ddmpc_set_input_bounds: ddmpc_box_step_kernel / ddmpc_closed_loop_box_kernel),
-  * on a handle given the same bounds in every row (ddmpc_set_instance_input_bounds: the twins of ddmpc_instance_box_law.hpp,
-    whose only extra work is the fill of the two LDS arrays),
+  * on a handle given the same bounds in every row (ddmpc_set_instance_input_bounds: the channel-table (BoxChannels)
+    instantiations of the same two kernels, whose only extra work is the fill of the two LDS arrays),
 in one process, the two handles timed alternately.  HIP-event timing after warm-up; median with min / max over the repeats, and
 the per-instance / shared ratio of the medians.  The outputs of the two handles are compared bit for bit.
 

@@ -1,5 +1,5 @@
-"""Dev timing (GPU): DDMPC_OPT_SETPOINT_CONVEX_LAW on four-tank controllers with the CONVEX slack box (L = 30, N = 400, 136 rows),
-HIP events, median of `--reps` repeats, the compared versions alternating in one process after a warm-up of every version.
+"""Dev timing (GPU): DDMPC_OPT_SETPOINT_CONVEX_LAW on four-tank controllers with the CONVEX slack box (L = 30, N = 400, 136 rows;
+the setpoint calls run the SLACK instantiations of ddmpc_setpoint_box_step_kernel / ddmpc_closed_loop_setpoint_box_kernel), HIP events, median of `--reps` repeats, the compared versions alternating in one process after a warm-up of every version.
 Per case (slack-only; u in [-4, 6]: few active inputs; u in [0, 2]: 30 .. 50 of them) and batch:
 
   * ddmpc_step with the option 0 -- twice, as two entries of the alternation: their difference is the run-to-run spread -- and
