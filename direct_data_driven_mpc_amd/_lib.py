@@ -40,6 +40,7 @@ OPT_SETPOINT_BOX_LAW = 19
 OPT_SETPOINT_CONVEX_LAW = 20
 OPT_LARGE_SETPOINTS = 21
 OPT_LARGE_SETPOINT_BOUNDS = 22
+OPT_INSTANCE_SETPOINT_BOUNDS = 23
 PIPELINE_ONE_WORKGROUP, PIPELINE_PHASES = 0, 1
 REFINE_OFF, REFINE_AUTO, REFINE_ALWAYS = 0, 1, 2
 PATH_AUTO, PATH_COLD, PATH_WARM = 0, 1, 2

@@ -319,6 +319,8 @@ struct ddmpc_handle {
   // into it, -+infinity without a bound).
   std::vector<double> iumin_h, iumax_h, iymin_h, iymax_h;
   DevBuf d_ibnd;
+  int instance_setpoint_bounds = 0;        // DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS: per-instance bounds and DDMPC_OPT_SETPOINT_BOX_LAW / _CONVEX_LAW on one handle
+                                           //   (the BoxChannels instantiations of ddmpc_setpoint_box_law.hpp read d_ibnd); 0: the two refuse each other
   DevBuf s_gain, s_prep_status, s_mcol, s_cwl_ref;   // ... the preparation of ddmpc_solve's own (solve_box): a kept ddmpc_prepare survives the solve
   int epoch = 0;                           // cold launches so far (KParams::epoch)
   int flag_epoch = 0;                      // latest stamp written into d_rflag
@@ -2713,19 +2715,25 @@ static int setpoint_step_on_route(ddmpc_handle* h, const double* up, const doubl
     // ddmpc_setpoint_box_step_kernel on the box list ddmpc_prepare kept.  DDMPC_OPT_SETPOINT_CONVEX_LAW: its SLACK instantiations --
     // the slack components alone (Route::Cold; no safeguard: the slack box does not cycle) or next to the bounded inputs / outputs
     begin_solve(h, route);
+    // Per-instance bounds (instance_bounds, DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS = 1): the BoxChannels instantiations with the channel table.
     const bool yb = !h->ymin_h.empty(), safe = route == Route::BoxLaw && h->box_safeguard;
-    auto launch = [&](auto slack) {
+    auto launch = [&](auto slack, auto... extra) {
       with_safe_yb(safe, yb, [&](auto safet, auto ybt) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ddmpc_setpoint_box_step_kernel<safet(), ybt(), slack()>), dim3((unsigned)h->batch),
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ddmpc_setpoint_box_step_kernel<safet(), ybt(), slack(), decltype(extra)...>), dim3((unsigned)h->batch),
                            dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0, h->stream, h->kp, 16 * h->kc.NT,
                            h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const double*)h->d_sgain.p,
                            (const int*)h->d_prep_status.p, up, yp, h->sp_us, h->sp_ys, uo, cost, (int*)status, (int*)iters,
                            h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p, (const double*)h->d_mcol.p,
                            (double*)h->d_cwl_sg.p, h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr,
-                           (const double*)h->d_chbnd.p, (int)(h->prm.use_terminal_constraint != 0));
+                           (const double*)h->d_chbnd.p, (int)(h->prm.use_terminal_constraint != 0), extra...);
       });
     };
-    if (h->setpoint_convex_law) launch(std::true_type{}); else launch(std::false_type{});
+    if (instance_bounds(h)) {
+      const BoxChannels chan{(const double*)h->d_ibnd.p};
+      if (h->setpoint_convex_law) launch(std::true_type{}, chan); else launch(std::false_type{}, chan);
+    } else {
+      if (h->setpoint_convex_law) launch(std::true_type{}); else launch(std::false_type{});
+    }
     HIP_TRY(hipGetLastError());
     return DDMPC_OK;
   }
@@ -2928,7 +2936,7 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_SETPOINT_BOX_LAW must be 0 or 1");
       if (value == 1) {                                 // (the refusals of DDMPC_OPT_SETPOINT_LAW but the one of bounds)
         const char* pre = "DDMPC_OPT_SETPOINT_BOX_LAW";
-        if (instance_bounds(h))
+        if (instance_bounds(h) && !h->instance_setpoint_bounds)
           return fail(DDMPC_ERR_UNSUPPORTED, "%s: not on a handle with per-instance bounds (ddmpc_set_instance_input_bounds / "
                       "_output_bounds: the setpoint kernels read the bounds shared by the batch)", pre);
         if (h->prm.controller_type != DDMPC_ROBUST)
@@ -2954,7 +2962,7 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_SETPOINT_CONVEX_LAW must be 0 or 1");
       if (value == 1) {                                 // (CONVEX only, so never on together with options 18 / 19, which refuse it)
         const char* pre = "DDMPC_OPT_SETPOINT_CONVEX_LAW";
-        if (instance_bounds(h))
+        if (instance_bounds(h) && !h->instance_setpoint_bounds)
           return fail(DDMPC_ERR_UNSUPPORTED, "%s: not on a handle with per-instance bounds (ddmpc_set_instance_input_bounds / "
                       "_output_bounds: the setpoint kernels read the bounds shared by the batch)", pre);
         if (h->prm.controller_type != DDMPC_ROBUST)
@@ -3036,6 +3044,25 @@ int ddmpc_set_option(ddmpc_handle* h, int option, int value) {
           return fail(DDMPC_ERR_UNSUPPORTED, "%s: n*(m+p) = %d, the limit is %d", pre, h->prm.n * h->kp.nch, WARM_MAX_NF);
       }
       h->large_setpoint_bounds = value;   // (which calls are accepted: the kept factor does not depend on the setpoint, nothing prepared differs)
+      return DDMPC_OK;
+    case DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS:
+      if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS must be 0 or 1");
+      if (value == 1) {
+        const char* pre = "DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS";
+        if (h->prm.controller_type != DDMPC_ROBUST)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: ROBUST controllers only (a NOMINAL one has neither bounds nor the setpoint law)", pre);
+        if (h->prm.weight_kind == DDMPC_WEIGHT_DENSE)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: DDMPC_WEIGHT_DENSE is not supported (scalar / diagonal weights only)", pre);
+        if (h->large)
+          return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels; beyond them the "
+                      "bounds stay shared by the batch)", pre, h->kp.r);
+      } else if (instance_bounds(h) && (h->setpoint_box_law || h->setpoint_convex_law)) {
+        return fail(DDMPC_ERR_UNSUPPORTED, "DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS = 0: the handle carries per-instance bounds and %s = 1 together; remove "
+                    "the per-instance bounds (ddmpc_set_instance_input_bounds / _output_bounds with null) or set %s = 0 first",
+                    h->setpoint_box_law ? "DDMPC_OPT_SETPOINT_BOX_LAW" : "DDMPC_OPT_SETPOINT_CONVEX_LAW",
+                    h->setpoint_box_law ? "DDMPC_OPT_SETPOINT_BOX_LAW" : "DDMPC_OPT_SETPOINT_CONVEX_LAW");
+      }
+      h->instance_setpoint_bounds = value;   // (which calls are accepted and which instantiation is launched: the law, S, the box list and M do not depend on it)
       return DDMPC_OK;
     case DDMPC_OPT_GRAM_LAUNCH:
       if (value != 0 && value != 1) return fail(DDMPC_ERR_INVALID, "Gram launch must be 0 (matrix pipe) or 1 (ddmpc_gram_tiles_kernel)");
@@ -3169,7 +3196,7 @@ static int instance_bounds_refusal(const ddmpc_handle* h, const char* what) {
   if (h->large)
     return fail(DDMPC_ERR_UNSUPPORTED, "%s: (m+p)(L+n) = %d rows, the limit is 271 (the register-resident kernels; beyond them the "
                 "phase kernels read the bounds shared by the batch, also with DDMPC_OPT_LARGE_BOUNDS = 1)", what, h->kp.r);
-  if (h->setpoint_box_law || h->setpoint_convex_law)
+  if ((h->setpoint_box_law || h->setpoint_convex_law) && !h->instance_setpoint_bounds)
     return fail(DDMPC_ERR_UNSUPPORTED, "%s: not with %s = 1 (the setpoint kernels read the bounds shared by the batch)", what,
                 h->setpoint_box_law ? "DDMPC_OPT_SETPOINT_BOX_LAW" : "DDMPC_OPT_SETPOINT_CONVEX_LAW");
   return DDMPC_OK;
@@ -3756,19 +3783,24 @@ static int launch_setpoint_loop(ddmpc_handle* h, const LoopArgs& a, const double
     // (DDMPC_OPT_SETPOINT_CONVEX_LAW: the SLACK instantiations, slack-only (Route::Cold) or bounded (Route::BoxLaw), as setpoint_step_on_route)
     begin_solve(h, route);
     const bool yb = !h->ymin_h.empty(), safe = route == Route::BoxLaw && h->box_safeguard;
-    auto launch = [&](auto slack) {
+    auto launch = [&](auto slack, auto... extra) {
       with_safe_yb(safe, yb, [&](auto safet, auto ybt) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ddmpc_closed_loop_setpoint_box_kernel<safet(), ybt(), slack()>), dim3((unsigned)h->batch),
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ddmpc_closed_loop_setpoint_box_kernel<safet(), ybt(), slack(), decltype(extra)...>), dim3((unsigned)h->batch),
                            dim3(yb ? (unsigned)h->prep.box_threads : warm_threads(h->kp.r)), 0, h->stream, h->kp, 16 * h->kc.NT,
                            h->prm.n * h->kp.nch, (const double*)h->d_gain.p, (const double*)h->d_sgain.p,
                            (const int*)h->d_prep_status.p, a.ns, a.pl, a.n_steps, a.n_mpc_step, a.x, a.up, a.yp, a.w, u_ref, y_ref,
                            a.usys, a.ysys, a.stacc, h->prep.cwl_nbox, (const int*)h->d_cwl_tab.p, (const double*)h->d_box_bd.p,
                            (const double*)h->d_mcol.p, (double*)h->d_cwl_sg.p,
                            h->prep.cwl_nref > 0 ? (const int*)h->d_cwl_ref.p : (const int*)nullptr, (const double*)h->d_chbnd.p,
-                           (int)(h->prm.use_terminal_constraint != 0));
+                           (int)(h->prm.use_terminal_constraint != 0), extra...);
       });
     };
-    if (h->setpoint_convex_law) launch(std::true_type{}); else launch(std::false_type{});
+    if (instance_bounds(h)) {      // (DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS = 1: the BoxChannels instantiations, as setpoint_step_on_route)
+      const BoxChannels chan{(const double*)h->d_ibnd.p};
+      if (h->setpoint_convex_law) launch(std::true_type{}, chan); else launch(std::false_type{}, chan);
+    } else {
+      if (h->setpoint_convex_law) launch(std::true_type{}); else launch(std::false_type{});
+    }
     HIP_TRY(hipGetLastError());
     h->last.setpoint_call = true;
     return DDMPC_OK;
@@ -3873,8 +3905,11 @@ static int closed_loop_impl(ddmpc_handle* h, const char* what, const ddmpc_plant
   if (u_ref) {
     // DDMPC_OPT_SETPOINT_LAW: one fused launch, no per-step fall-back (DDMPC_OPT_CLOSED_LOOP_PATH / _GRAPH are not looked at)
     // (the names are labels of the path: "..._setpoint_convex_kernel" is the SLACK instantiation of ddmpc_closed_loop_setpoint_box_kernel)
-    h->loop_kernel = h->setpoint_convex_law ? "ddmpc_closed_loop_setpoint_convex_kernel"
-                     : select_route(h) == Route::BoxLaw ? "ddmpc_closed_loop_setpoint_box_kernel" : "ddmpc_closed_loop_setpoint_kernel";
+    // ("ddmpc_closed_loop_instance_setpoint_box_kernel" / "..._instance_setpoint_convex_kernel": its BoxChannels instantiations)
+    const bool inst = instance_bounds(h);
+    h->loop_kernel = h->setpoint_convex_law ? (inst ? "ddmpc_closed_loop_instance_setpoint_convex_kernel" : "ddmpc_closed_loop_setpoint_convex_kernel")
+                     : select_route(h) == Route::BoxLaw ? (inst ? "ddmpc_closed_loop_instance_setpoint_box_kernel" : "ddmpc_closed_loop_setpoint_box_kernel")
+                                                         : "ddmpc_closed_loop_setpoint_kernel";
     if ((rc = launch_setpoint_loop(h, a, u_ref, y_ref))) return rc;
     return copy_loop_outputs(h, mem, nb, a, user, status);
   }

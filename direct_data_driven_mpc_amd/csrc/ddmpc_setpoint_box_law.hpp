@@ -29,6 +29,13 @@
 // solves), and one pair of kernels serves every CONVEX handle.  The channel bounds `chb` are +-infinity there, so the only
 // per-instance refusal left is the non-finite setpoint.  The output stage needs nothing more: the box_component /
 // box_component_y overloads below carry the K_WPRED / K_WTERM branches with the slack flag and the K_WINT rows.
+//
+// DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS (the BoxChannels instantiations of the two kernels, on a handle that carries per-instance bounds):
+// next to the offsets as[] the kernels keep blo[s] / bhi[s], the instance's own bounds by boxed component, in LDS -- filled by
+// instance_box_fill from the instance's row of the channel table (ddmpc_box_law.hpp), once per launch (the loop kernel: once per
+// instance, the bounds do not move with the schedule) -- and point the table's lo / hi at them.  The fill reads the shared lo / hi
+// for the slack components of a CONVEX handle, so it runs before the pointers are swapped, and a barrier stands between it and the
+// first BoxTab::test.  The per-instance refusal reads the instance's own row instead of the shared `chb`.  Nothing else differs.
 // Included by the API translation unit only; nothing here is launched by a handle with both options 0.
 #pragma once
 #include "ddmpc_box_law.hpp"
@@ -104,7 +111,11 @@ __device__ __forceinline__ double setpoint_convex_offset(const KParams& P, int R
 // checked by ddmpc_prepare).
 // SLACK (DDMPC_OPT_SETPOINT_CONVEX_LAW): the offsets of a CONVEX handle's box list (setpoint_convex_offset); nothing else differs.
 // SAFE is then launched on bounded handles only.
-template <bool SAFE, bool YB, bool SLACK = false>
+// Extra = BoxChannels (DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS = 1 on a handle with per-instance bounds, "INST"): the same stages, statuses
+// and iters with the instance's own bounds -- blo, bhi [WARM_MAX_R] in LDS behind the table's lo / hi, as in ddmpc_box_step_kernel --
+// and the refusal against the instance's own row of the channel table (`chb` is not read).  The host launches the empty pack
+// otherwise: that instantiation is the kernel as it was.
+template <bool SAFE, bool YB, bool SLACK = false, class... Extra>
 __global__ void ddmpc_setpoint_box_step_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                                const double* __restrict__ sgain, const int* __restrict__ prep_status,
                                                const double* __restrict__ u_past, const double* __restrict__ y_past,
@@ -112,7 +123,10 @@ __global__ void ddmpc_setpoint_box_step_kernel(KParams P, int RPs, int nf, const
                                                double* __restrict__ u_opt, double* __restrict__ cost, int* __restrict__ status,
                                                int* __restrict__ iters, int nbox, const int* __restrict__ tab,
                                                const double* __restrict__ bd, const double* __restrict__ Mcol, double* __restrict__ sg,
-                                               const int* __restrict__ refined, const double* __restrict__ chb, int tec) {
+                                               const int* __restrict__ refined, const double* __restrict__ chb, int tec,
+                                               Extra... extra) {
+  constexpr bool INST = (std::is_same_v<Extra, BoxChannels> || ...);
+  [[maybe_unused]] const BoxChannels chan = box_channels_of(extra...);
   __shared__ double pv[WARM_MAX_NF];
   __shared__ double sv[WARM_MAX_NF];
   __shared__ double red[32];
@@ -137,6 +151,14 @@ __global__ void ddmpc_setpoint_box_step_kernel(KParams P, int RPs, int nf, const
       const int c = T.rho[j] % nch;
       as[j] = (c < P.m) ? u_s[b * P.m + c] : y_s[b * P.p + (c - P.m)];
     }
+  }
+  if constexpr (INST) {                               // (the fill reads the shared lo / hi of slack components: before the swap)
+    __shared__ double blo[WARM_MAX_R];                // the bounds of this instance, by boxed component
+    __shared__ double bhi[WARM_MAX_R];
+    instance_box_fill<YB>(P, T, chan.chb + b * (long long)(2 * nch), blo, bhi);
+    T.lo = blo;
+    T.hi = bhi;
+    chb = chan.chb + b * (long long)(2 * nch);        // the refusal reads the instance's own row
   }
   __syncthreads();
   const int refuse = setpoint_box_refusal(nch, tec, sv, chb);
@@ -229,7 +251,9 @@ __global__ void ddmpc_setpoint_box_step_kernel(KParams P, int RPs, int nf, const
 // ddmpc_setpoint_box_step_kernel; an instance the safeguard finishes carries on.  Nothing is kept for ddmpc_get_solution.
 // Fixed-size arrays as in ddmpc_closed_loop_box_kernel plus sv [WARM_MAX_NF] and as [WARM_MAX_R]; ddmpc_closed_loop_setpoints
 // checks n_mpc_step * m <= WARM_MAX_NF and ns <= 16.  SLACK: as in ddmpc_setpoint_box_step_kernel.
-template <bool SAFE, bool YB, bool SLACK = false>
+// Extra = BoxChannels: as in ddmpc_setpoint_box_step_kernel; blo / bhi are filled once, before the first solve (the bounds do not
+// move with the schedule).
+template <bool SAFE, bool YB, bool SLACK = false, class... Extra>
 __global__ void ddmpc_closed_loop_setpoint_box_kernel(KParams P, int RPs, int nf, const double* __restrict__ gain,
                                                       const double* __restrict__ sgain, const int* __restrict__ prep_status, int ns,
                                                       const double* __restrict__ pl, int n_steps, int n_mpc_step,
@@ -240,7 +264,9 @@ __global__ void ddmpc_closed_loop_setpoint_box_kernel(KParams P, int RPs, int nf
                                                       int* __restrict__ status_out, int nbox, const int* __restrict__ tab,
                                                       const double* __restrict__ bd, const double* __restrict__ Mcol,
                                                       double* __restrict__ sg, const int* __restrict__ refined,
-                                                      const double* __restrict__ chb, int tec) {
+                                                      const double* __restrict__ chb, int tec, Extra... extra) {
+  constexpr bool INST = (std::is_same_v<Extra, BoxChannels> || ...);
+  [[maybe_unused]] const BoxChannels chan = box_channels_of(extra...);
   __shared__ double pv[WARM_MAX_NF];
   __shared__ double sv[WARM_MAX_NF];
   __shared__ double uo[WARM_MAX_NF];      // the first n_mpc_step*m entries of optimal_u
@@ -261,6 +287,14 @@ __global__ void ddmpc_closed_loop_setpoint_box_kernel(KParams P, int RPs, int nf
   for (int f = tid; f < nf; f += blockDim.x)
     pv[f] = (f < P.npu) ? u_past[b * P.npu + f] : y_past[b * nyp + (f - P.npu)];
   if (tid < ns) xs[tid] = x[b * ns + tid];
+  if constexpr (INST) {                               // (visible behind the barrier that opens the first solve)
+    __shared__ double blo[WARM_MAX_R];                // the bounds of this instance, by boxed component
+    __shared__ double bhi[WARM_MAX_R];
+    instance_box_fill<YB>(P, T, chan.chb + b * (long long)(2 * nch), blo, bhi);
+    T.lo = blo;
+    T.hi = bhi;
+    chb = chan.chb + b * (long long)(2 * nch);        // the refusal reads the instance's own row
+  }
   const int st0 = prep_status[b];
   const bool refd = refined != nullptr && refined[b] != 0;
   const double nanv = __longlong_as_double(0x7ff8000000000000LL);

@@ -364,6 +364,23 @@ class BatchedDDMPC:
         n(m+p) > 256.  `set_large_setpoints(True)` keeps refusing bounds."""
         L.check(self._lib.ddmpc_set_option(self._h, L.OPT_LARGE_SETPOINT_BOUNDS, 1 if on else 0))
 
+    def set_instance_setpoint_bounds(self, on: bool) -> None:
+        """Per-instance bounds (`set_instance_input_bounds` / `set_instance_output_bounds`) together with per-instance, per-step
+        setpoints (`set_setpoint_box_law` / `set_setpoint_convex_law`) on one handle of at most 271 rows
+        (DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS): True = the two are accepted on the same handle, in either order, and
+        `step_setpoints` / `closed_loop_setpoints` run the iteration of `step` with the instance's own setpoint AND its own
+        bounds ('ddmpc_closed_loop_instance_setpoint_box_kernel', under the CONVEX slack box
+        'ddmpc_closed_loop_instance_setpoint_convex_kernel').  Per instance: with the terminal constraint a setpoint outside
+        that instance's own bounds is infeasible (NaN outputs, iters 0), also when a neighbour's wider box holds it; an active
+        input or output equals its instance's bound exactly.  Rows that are all equal give results bit-equal to the shared
+        bounds.  `set_box_safeguard` applies; `set_box_warm_start` is not honoured.  `solve`, `step`, `closed_loop`, `gain`,
+        `setpoint_gain` and `get_solution` are those of the handle with False (default), with which the two features refuse
+        each other as before; changing the value forgets nothing `prepare` kept.  With the terminal constraint the handle's
+        own setpoint must still lie inside every instance's row.  Raises ERR_UNSUPPORTED on more than 271 rows (bounds stay
+        shared there), NOMINAL controllers and dense weights, and for False while the handle carries per-instance bounds and
+        one of the two setpoint options together (remove one first)."""
+        L.check(self._lib.ddmpc_set_option(self._h, L.OPT_INSTANCE_SETPOINT_BOUNDS, 1 if on else 0))
+
     def step_setpoints(self, u_past, y_past, u_s, y_s, u_opt=None, cost=None, status=None, iters=None):
         """Warm control step with one setpoint per instance (`ddmpc_step_setpoints`): u_s [batch,m], y_s [batch,p], in the
         memory space of the windows; same outputs and array / tensor handling as `solve`.  The handle's own setpoints are not

@@ -70,7 +70,8 @@ def parse_args():
     ap.add_argument("--bound_spread", type=float, default=None,
                     help="a fleet with different limits: with --u_min/--u_max and / or --y_min/--y_max, the finite bounds of "
                          "instance b are widened by S * b / (batch - 1) on both sides and set per instance "
-                         "(set_instance_input_bounds / set_instance_output_bounds; up to 271 rows, not with --setpoint_spread)")
+                         "(set_instance_input_bounds / set_instance_output_bounds; up to 271 rows).  Together with --setpoint_spread every "
+                         "instance tracks its own setpoint inside its own box (set_instance_setpoint_bounds; up to 271 rows)")
     ap.add_argument("--verbose", type=int, choices=[0, 1, 2], default=1)
     return ap.parse_args()
 
@@ -118,9 +119,11 @@ def main():
     if a.bound_spread is not None:
         if a.u_min is None and a.y_min is None:
             raise ValueError("--bound_spread widens the bounds of --u_min/--u_max and / or --y_min/--y_max: give at least one pair")
-        if a.setpoint_spread is not None:
-            raise ValueError("--bound_spread and --setpoint_spread do not go together (per-instance bounds with per-instance "
-                             "setpoints are not covered)")
+        if a.setpoint_spread is not None:        # per-instance bounds with per-instance setpoints: DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS
+            if (m + p) * (Lh + n) > 271:
+                raise ValueError("--bound_spread together with --setpoint_spread is limited to 271 rows: (m+p)(L+n) = "
+                                 f"{(m + p) * (Lh + n)} (beyond that the bounds stay shared by the batch)")
+            eng.set_instance_setpoint_bounds(True)
 
         def rows(lo, hi, nc):                    # instance b: [lo - S b / (B - 1), hi + S b / (B - 1)] on the finite sides
             grow = a.bound_spread * np.arange(B)[:, None] / max(B - 1, 1)

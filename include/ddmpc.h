@@ -438,6 +438,38 @@ extern "C" {
                                          has, bounds included, whether or not this option is on.  Not covered: NOMINAL controllers,
                                          dense weights, more than 1024 rows, per-instance bounds, a setpoint form of the large box
                                          law, the active-set warm start for these calls, a fused loop kernel */
+#define DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS 23 /* Per-instance bounds (ddmpc_set_instance_input_bounds / _output_bounds) together with
+                                         per-instance, per-step setpoints (DDMPC_OPT_SETPOINT_BOX_LAW / _SETPOINT_CONVEX_LAW) on one
+                                         handle of at most 271 rows: a fleet whose plants differ in equilibrium AND in actuator range
+                                         or safety limits.  1 = the per-instance bounds calls are accepted on a handle with option 19
+                                         or 20 on, and options 19 / 20 on a handle that carries per-instance bounds (either order);
+                                         every other refusal of those four calls stays.  ddmpc_step_setpoints and
+                                         ddmpc_closed_loop_setpoints then launch the channel-table (BoxChannels) instantiations of
+                                         ddmpc_setpoint_box_step_kernel / ddmpc_closed_loop_setpoint_box_kernel (the loop is labelled
+                                         "ddmpc_closed_loop_instance_setpoint_box_kernel", under the CONVEX slack box
+                                         "ddmpc_closed_loop_instance_setpoint_convex_kernel"), which stage the instance's bounds in LDS
+                                         once per launch -- the bounds do not move with the schedule -- next to its offsets: the
+                                         violation test, the shifts, the safeguard's ratios and "held at its bound exactly" use the
+                                         instance's own bound, and with the terminal constraint a setpoint outside THAT INSTANCE's
+                                         bounds is DDMPC_STATUS_INFEASIBLE (NaN outputs, iters 0, in the loop the instance stops
+                                         there; neighbours untouched, also one whose wider box holds the same setpoint).  The law,
+                                         S, the box list and M do not depend on the option: changing it forgets nothing
+                                         ddmpc_prepare kept.  Rows that are all equal give results bit-equal to the shared bounds
+                                         under option 19 / 20.  DDMPC_OPT_BOX_SAFEGUARD applies; DDMPC_OPT_BOX_WARM_START stays
+                                         accepted and not honoured.  ddmpc_solve, ddmpc_step, ddmpc_closed_loop, ddmpc_get_solution,
+                                         ddmpc_get_gain and ddmpc_get_setpoint_gain do what they do with 0 (the BoxChannels box
+                                         kernels with the handle's shared setpoint); ddmpc_get_solution after a setpoint call stays
+                                         DDMPC_ERR_NOT_READY.  0 (default): every call, error text and launched kernel is what it
+                                         was before the option existed -- the two features refuse each other.  Values other than
+                                         0 / 1: DDMPC_ERR_INVALID.  Setting 1 is DDMPC_ERR_UNSUPPORTED, with a message that names the
+                                         reason, beyond 271 rows (bounds stay shared there), on NOMINAL controllers and with
+                                         DDMPC_WEIGHT_DENSE; setting 0 is DDMPC_ERR_UNSUPPORTED while the handle carries
+                                         per-instance bounds and option 19 or 20 together (remove one of the two first).  Not
+                                         covered: with the terminal constraint the handle's own shared setpoint must still lie inside
+                                         EVERY instance's row (ddmpc_solve / ddmpc_step use it; the bounds calls and
+                                         ddmpc_set_setpoints check it), also when only the setpoint calls are used; more than 271
+                                         rows; bounds per prediction step; the active-set warm start on the setpoint calls;
+                                         ddmpc_get_solution after them */
 #define DDMPC_REFINE_RES_DEFAULT 107  /* 2e-11: benchmark data stays below ~2e-12, the parity bars are missed from ~1.3e-10 on */
 
 typedef struct ddmpc_handle ddmpc_handle;
@@ -667,7 +699,8 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
  *     than 288 components is named by ddmpc_set_instance_output_bounds or ddmpc_prepare; ddmpc_solve_from_host); more than 271
  *     rows, also with DDMPC_OPT_LARGE_BOUNDS = 1 (the phase kernels read the shared bounds); a handle with
  *     DDMPC_OPT_SETPOINT_BOX_LAW or DDMPC_OPT_SETPOINT_CONVEX_LAW on -- in the reverse order ddmpc_set_option refuses those two
- *     on a handle that carries per-instance bounds of either kind.
+ *     on a handle that carries per-instance bounds of either kind -- unless DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS = 1, which admits
+ *     both orders (the setpoint calls then run the channel-bounds instantiations of the setpoint-box kernels: see the option).
  * How it is served: Route::BoxLaw as under shared bounds, by the channel-bounds instantiations of its two kernels, which stage
  * the instance's bounds in LDS (ddmpc_box_law.hpp; the fused loop is labelled "ddmpc_closed_loop_instance_box_kernel": the
  * name is the label of the path, the kernel is that instantiation of ddmpc_closed_loop_box_kernel) -- ddmpc_solve with the cold contract
@@ -676,7 +709,9 @@ int ddmpc_set_output_bounds(ddmpc_handle* h, const double* y_min, const double* 
  * optimal_inaccurate on refined laws are those of the shared-bounds kernels; DDMPC_OPT_BOX_SAFEGUARD applies.
  * DDMPC_OPT_BOX_WARM_START is accepted and not honoured: every solve starts from the empty set and no seed is kept.  A handle
  * without per-instance bounds launches exactly the kernels it launched before these calls existed.
- * Not covered: more than 271 rows; per-instance setpoints on the same handle (options 19, 20, 22); the active-set warm start;
+ * Not covered: more than 271 rows; per-instance setpoints on the same handle without DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS = 1
+ * (options 19, 20) and beyond 271 rows (option 22); with that option and the terminal constraint, a shared setpoint of the handle
+ * outside any instance's row (it stays DDMPC_ERR_INVALID: ddmpc_solve / ddmpc_step use it); the active-set warm start;
  * keeping ddmpc_prepare's law and M across a call that changes bound values only; bounds per prediction step; NOMINAL
  * controllers and dense weights. */
 int ddmpc_set_instance_input_bounds(ddmpc_handle* h, const double* u_min, const double* u_max);
@@ -688,7 +723,8 @@ int ddmpc_set_instance_input_bounds(ddmpc_handle* h, const double* u_min, const 
  * input bounds of either form.  Everything else -- side effects, the shared box list (a channel is boxed when any instance has
  * a finite bound on it; no finite bound in the batch is a removal), DDMPC_ERR_INVALID with instance and channel (here y_s
  * against every row under the terminal constraint), DDMPC_ERR_UNSUPPORTED (what ddmpc_set_output_bounds refuses up to 271 rows,
- * the box list over 288 components included; more than 271 rows; options 19 / 20), how it is served, the options and what is
+ * the box list over 288 components included; more than 271 rows; options 19 / 20 without DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS = 1),
+ * how it is served, the options and what is
  * not covered -- as ddmpc_set_instance_input_bounds.  In the solution an active output equals its instance's bound exactly. */
 int ddmpc_set_instance_output_bounds(ddmpc_handle* h, const double* y_min, const double* y_max);
 
@@ -817,7 +853,9 @@ const char* ddmpc_kernel_name(ddmpc_handle* h);
  * "ddmpc_closed_loop_setpoint_box_kernel" / "ddmpc_closed_loop_setpoint_convex_kernel" after ddmpc_closed_loop_setpoints; "" before the first loop.
  * The names are labels of the path taken: "ddmpc_closed_loop_instance_box_kernel" (per-instance bounds) is the channel-bounds
  * instantiation of ddmpc_closed_loop_box_kernel, "ddmpc_closed_loop_setpoint_convex_kernel" the slack-box instantiation of
- * ddmpc_closed_loop_setpoint_box_kernel.  Read-only. */
+ * ddmpc_closed_loop_setpoint_box_kernel, "ddmpc_closed_loop_instance_setpoint_box_kernel" /
+ * "ddmpc_closed_loop_instance_setpoint_convex_kernel" (DDMPC_OPT_INSTANCE_SETPOINT_BOUNDS = 1 on a handle with per-instance bounds)
+ * the channel-bounds instantiations of the same kernel.  Read-only. */
 const char* ddmpc_closed_loop_kernel_name(ddmpc_handle* h);
 
 /* Diagnostics only: in-kernel phase stamps (shader-clock ticks) of the next solves.
